@@ -12,6 +12,9 @@ reported beside it.  With N > 1 every rank owns a model replica and its own 1M-p
 corpus and the passage stream partition by rank).  The encode leg has no collective; the search leg has
 the path's one real exchange step: the query embeddings are all-gathered, every rank searches its shard, the per-rank
 top-k lists are all-gathered and merged on the device (parallel.search_sharded_device, BASELINE configs[3]).
+A plain run sets up, warms up, times the steps and prints the line; --full adds what the line does not need (power state,
+the roofline kernel under the profiler, the extra legs, the CPU baseline).  --dump-outputs DIR writes the last timed step's
+embeddings and top-k (scores, ids) as .npy files; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -287,6 +290,18 @@ def synthetic_tokens(n, L, seed, device):
     ids = torch.randint(3, 50000, (n, L), generator=g, device=device, dtype=torch.int32)
     ids[:, 0] = 0
     return ids
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy on the host; floating arrays keep float32 / float64, integer
+    ones (top-k ids) become float64, which holds them exactly."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy() if t.dtype in (torch.float16, torch.bfloat16) else t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(nq, d, k, L, budget_s=9.0):
@@ -945,6 +960,12 @@ def main():
                          "epoch / precompute pass) instead of a teacher forward per step; not the reference flow")
     ap.add_argument("--train-dropout", type=float, default=0.1,
                     help="student dropout of the train_kd workload (the reference's training configuration: 0.1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline line does not need: the power state, the roofline kernel under the "
+                         "profiler (child passes), the extra legs (see --no-extras) and the CPU baseline (see --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (embeddings, top-k scores and ids) "
+                         "as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
     _launch_ranks_if_needed(args)
     if os.environ.get("CONVDR_BENCH_LAUNCH_DRYRUN"):       # (tests/test_bench_launcher_cpu.py: the launcher without a GPU)
@@ -968,8 +989,10 @@ def main():
     from convdr_amd.search import FlatIPIndex
     L_ = _lib.lib()
     if world == 1 and not dist_on and not args.no_extras:
+        # (the train_kd / train_rank legs of --full: see train.reserve_streams; done without --full too, so that the timed
+        #  steps' streams land on the same hardware queues either way)
         from convdr_amd import train as _TR
-        _TR.reserve_streams(dev)      # (the train_kd / train_rank legs below: see train.reserve_streams)
+        _TR.reserve_streams(dev)
 
     n, nq, k, d, EB, SL = args.passages, args.queries, args.topk, D_OUT, args.enc_batch, args.seq_len
     model = random_rdot_model().to(dev).eval()
@@ -997,12 +1020,14 @@ def main():
           for _ in range(args.steps)]
 
     retried = [0]
+    last_emb = [None]
 
     def step(i, timers=None):
         with torch.no_grad():
             if timers:
                 timers[0].record()
             emb = tower.embed(pool[i % len(pool)], None, head=head, seq_lens=lens)
+            last_emb[0] = emb
             if timers:
                 timers[1].record()
             building.update_rows((i % slots) * EB, emb)
@@ -1058,6 +1083,8 @@ def main():
     cp = cp[cp[:, 3] > cp[:, 1]]                                 # the slots that were written (one per timed FFN1 launch)
     mhz = (cp[:, 2] - cp[:, 0]) / ((cp[:, 3] - cp[:, 1]) / 100.0) if len(cp) else np.zeros(0)      # s_memrealtime: 100 MHz
     clock_mhz = float(np.median(mhz)) if len(mhz) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"embeddings": last_emb[0], "topk_scores": out[0], "topk_ids": out[1]})
     status_bad = int((out[2] != 0).sum().item()) if out[2] is not None else 0    # (after certification: always 0)
     first_pass_retries = retried[0]
     emitted, band = (t.float().mean().item() for t in index.last_counts(nq, k))
@@ -1141,8 +1168,8 @@ def main():
         roof["clock_mhz_min_max"] = [float(mhz.min()), float(mhz.max())]
         roof["peak_at_delivered_clock"] = MFMA_BF16_PEAK_TFLOPS * clock_mhz / 2400.0
         roof["frac_at_delivered_clock"] = dom_tf / roof["peak_at_delivered_clock"]
-    roof["power"] = _power_state() if not args.no_extras else None     # (not in the profiler's child passes: rocm-smi is an exec)
-    if not args.no_extras and not dist_on and roof["power"] is not None:
+    roof["power"] = _power_state() if args.full and not args.no_extras else None     # (not in the profiler's child passes: rocm-smi is an exec)
+    if args.full and not args.no_extras and not dist_on and roof["power"] is not None:
         roof["power_under_load"] = power_under_load(lambda n: [step(i) for i in range(n)])
     try:
         kname = "k_gemm<8, convdr::TileCfg<2, 4, 4, 2>"      # EPI_GELU_BLK on 256 x 256 tiles (k_gemm<1, ..> before round 3)
@@ -1167,8 +1194,8 @@ def main():
     except Exception:
         pass
     roof["frac_hipevent"] = roof["frac"]
-    roof["frac_source"] = "hipEvent pairs on the launch stream around every timed FFN1 launch (no profiler pass was possible in this run)"
-    if world == 1 and not dist_on and not args.no_extras and EB * SL == 262144:
+    roof["frac_source"] = "hipEvent pairs on the launch stream around every timed FFN1 launch (no profiler pass in this run: it needs --full)"
+    if args.full and world == 1 and not dist_on and not args.no_extras and EB * SL == 262144:
         # `achieved` / `frac` = the kernel's average dispatch duration on the PROFILER's clock, measured in this run by a child
         # pass under rocprofv3 --kernel-trace: the number `rocprofv3 --kernel-trace --stats -- python bench.py` reproduces
         # (profiles/r05_bench_default.kernel_stats.txt).  The hipEvent figure of the timed region stays beside it
@@ -1191,7 +1218,7 @@ def main():
             roof["traffic_source"] = ("measured in this run: child passes of this script under rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE "
                                       "(separate passes, %d dispatches each); FETCH_SIZE doubled and both in KB per MI355X_MICROARCH.md" % lt["FETCH_SIZE"][1])
             roof["traffic_over_algorithmic"] = roof["traffic"] / float(rows * H * 2 + rows * I * 2 + H * I * 2)
-    if world == 1 and not dist_on and not args.no_extras:
+    if args.full and world == 1 and not dist_on and not args.no_extras:
         try:
             line.update(extras(dev, index, model, tower, head, building, min(slots, args.steps + args.warmup) * EB, nq, k, d, Q))
             del index, building, model
@@ -1212,7 +1239,7 @@ def main():
             line["search_38m_1gpu"] = extras_search_38m(dev, nq, k, d)
         except Exception as e:      # the extras must never cost the headline line
             line["extras_error"] = "%s: %s" % (type(e).__name__, e)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(nq, d, k, SL)
     print(json.dumps(line))
 

@@ -15,5 +15,5 @@ src = src.replace("    L_.convdr_set_option(b\"clock_probe\", 0)\n", "    L_.con
 src = src.replace("        # ---- (1b) a-11 the way the reference runs it", "        _kd_probe('after block_load leg', dev)\n        # ---- (1b) a-11 the way the reference runs it", 1)
 src = src.replace("    out.update(extras_search(dev, index, tower, head, building, filled_rows, nq, k, d))\n    return out", "    _kd_probe('after search_one_by_one_files leg', dev)\n    out.update(extras_search(dev, index, tower, head, building, filled_rows, nq, k, d))\n    _kd_probe('after extras_search', dev)\n    return out", 1)
 src = src.replace("    roof[\"power\"] = _power_state()", "    _kd_probe('before rocm-smi', dev)\n    roof[\"power\"] = _power_state()\n    _kd_probe('after rocm-smi', dev)", 1)
-sys.argv = ["bench.py", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline"]
 exec(compile(src, os.path.join(ROOT, "bench.py"), "exec"), {"__name__": "__main__", "__file__": os.path.join(ROOT, "bench.py")})

@@ -6,6 +6,6 @@ sys.path.insert(0, ROOT)
 import torch
 if os.environ.get("NO_EMPTY_CACHE"):
     torch.cuda.empty_cache = lambda: None
-sys.argv = ["bench.py", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline"]
 src = open(os.path.join(ROOT, "bench.py")).read()
 exec(compile(src, os.path.join(ROOT, "bench.py"), "exec"), {"__name__": "__main__", "__file__": os.path.join(ROOT, "bench.py")})
