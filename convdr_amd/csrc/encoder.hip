@@ -186,7 +186,7 @@ int encoder_layer_forward(const convdr_encoder_config* c, const convdr_layer_wei
   g2.rows = n; g2.W = (const bf16_t*)w->w1; g2.X = x1; g2.N = I; g2.K = H; g2.bias = w->b1; g2.Cb = p.Hm;
   // FFN1 -> FFN2 through the blocked activation layout (EPI_GELU_BLK) whenever FFN2 is the row-complete kernel that can
   // read it: the 1.6 GB tile output of FFN1 then leaves its registers in whole lines without passing through LDS.
-  // (CONVDR_HM_BLOCKED=0: row-major Hm, the round-2 path; A/B switch)
+  // (convdr_set_option("hm_blocked", 0): row-major Hm, the round-2 path; A/B switch)
   const bool blocked = blk_on && !cls_only && fused_ln_applies(n, H, I) && I % 256 == 0 && (I / 256) * ceil_div64(n, 256) >= 192;
   if (blocked) {
     if (int e = launch_gemm<EPI_GELU_BLK>(g2, st, "gemm_ffn1")) return e;

@@ -639,18 +639,6 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a)
   auto decode = [&](uint32_t i) {
     const uint32_t logical = chunk_base + i;
     int tt = logical / a.tilesN, tn = logical - tt * a.tilesN;
-#ifdef CONVDR_GEMM_PANEL   // A/B builds only (make VARIANT=panelN EXTRA=-DCONVDR_GEMM_PANEL=N; profiles/r05_gemm_raster_ab.txt):
-    // weight-set-aware raster -- an XCD sweeps its token tiles once per PANEL of CONVDR_GEMM_PANEL feature tiles, so that the
-    // weights its 32 workgroups have live at any time are PANEL tiles (6 x 393 KB = 2.4 MB of FFN1's 4.7 MB) instead of all
-    // of them, at the price of re-reading the XCD's activation tiles once per panel.  Shapes whose tile counts do not divide
-    // keep the default order.
-    if (a.tilesN % CONVDR_GEMM_PANEL == 0 && a.tilesN > CONVDR_GEMM_PANEL && (a.tilesT & 7) == 0) {
-      const uint32_t nT = a.tilesT >> 3, per_panel = CONVDR_GEMM_PANEL * nT;      // token tiles of this XCD's chunk
-      const uint32_t panel = i / per_panel, r = i - panel * per_panel;
-      tt = xcd * nT + r / CONVDR_GEMM_PANEL;
-      tn = panel * CONVDR_GEMM_PANEL + r % CONVDR_GEMM_PANEL;
-    }
-#endif
     if (a.dbg_same_tile) { tt = 0; tn = 0; }
     Coord c;
     c.t0 = (int64_t)tt * T::TL;      // the launcher lays tiles out as [tilesT][tilesN] with TR == TL

@@ -29,8 +29,10 @@ inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
   a.dbg_skip_epi = dbg_epi;
   static const int dbg_pre = getenv("CONVDR_DBG_PRELANDED") ? atoi(getenv("CONVDR_DBG_PRELANDED")) : 0;
   a.dbg_prelanded = dbg_pre;
-#endif
   static const int trace_epi = getenv("CONVDR_TRACE_EPI") ? atoi(getenv("CONVDR_TRACE_EPI")) : (int)EPI_GELU_BF16;
+#else
+  constexpr int trace_epi = EPI_GELU_BF16;
+#endif
   a.trace = (EPI == trace_epi) ? (unsigned long long*)g_gemm_trace : nullptr;
   a.clock_probe = nullptr;
   if (g_clock_probe && strcmp(prof_name, "gemm_ffn1") == 0) {
@@ -49,10 +51,9 @@ inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
   }
   ProfScope prof(prof_name, st);
   // persistent walk: at most one workgroup per resident slot (Tile256: 1 per CU, Tile128: 2 per CU)
-  static const int dbg_np = getenv("CONVDR_DBG_NONPERSISTENT") ? atoi(getenv("CONVDR_DBG_NONPERSISTENT")) : 0;
   const int64_t slots = (int64_t)device_cu_count() * (T::SMEM_BYTES > 80 * 1024 ? 1 : 2);
   int64_t grid = (int64_t)a.tilesN * a.tilesT;
-  if (!dbg_np && splits == 1 && grid > slots) grid = slots;
+  if (splits == 1 && grid > slots) grid = slots;
   const size_t lds = T::WAVES == 8 ? 160 * 1024 : T::SMEM_BYTES + T::TR * 4;
   hipLaunchKernelGGL((k_gemm<EPI, T>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
 #ifdef CONVDR_ENABLE_TRACE
@@ -84,7 +85,7 @@ inline int64_t g_embed_bwd_det = getenv("CONVDR_EMBED_BWD_DETERMINISTIC") ? atoi
 inline int64_t g_gelu_gp = 1;
 // convdr_set_option "ln_bwd_rows": LayerNorm backward of the encoder layers (H = 768): 0 = the general kernel, 1 = the straight-line
 // form (k_layernorm_bwd_rows) without, 2 (default) = with the register prefetch of the next row.  Same formulas; rounding-level differences.
-inline int64_t g_ln_bwd_rows = getenv("CONVDR_LN_BWD_ROWS") ? atoi(getenv("CONVDR_LN_BWD_ROWS")) : 2;
+inline int64_t g_ln_bwd_rows = 2;
 struct TileCost { double step_us, epi_us; int per_cu; };
 inline double gemm_tile_cost(int64_t tiles, int nk, const TileCost& c) {
   const int64_t slots = (int64_t)device_cu_count() * c.per_cu;
@@ -100,14 +101,12 @@ inline int launch_gemm(GemmArgs a, hipStream_t st, const char* prof_name) {
   int splits = 1;
   if (EPI == EPI_SLAB_F32 && a.k_split_len) splits = a.K / a.k_split_len;
   const int64_t tiles256 = (int64_t)(a.N / 256) * ceil_div64(a.rows, 256) * splits;
-  static const int force128 = getenv("CONVDR_DBG_TILE128") ? atoi(getenv("CONVDR_DBG_TILE128")) : 0;
-  static const int min256 = getenv("CONVDR_TILE256_MIN_TILES") ? atoi(getenv("CONVDR_TILE256_MIN_TILES")) : 192;   // A/B knob
   constexpr bool WIDE_OK = EPI == EPI_BF16 || EPI == EPI_RESID_F32 || EPI == EPI_GELU_SAVE || EPI == EPI_GELU_BF16 || EPI == EPI_F32 ||
                            EPI == EPI_GELU_GP || EPI == EPI_MUL_GP;
-  int choice = (fits && tiles256 >= min256) ? 256 : 128;
-  if (fits && !force128 && g_gemm_tile_policy == 1) choice = 256;
-  else if (fits && !force128 && g_gemm_tile_policy == 3) choice = 128;
-  else if (fits && WIDE_OK && !force128) {
+  int choice = (fits && tiles256 >= 192) ? 256 : 128;
+  if (fits && g_gemm_tile_policy == 1) choice = 256;
+  else if (fits && g_gemm_tile_policy == 3) choice = 128;
+  else if (fits && WIDE_OK) {
     if (g_gemm_tile_policy == 2) choice = 192;
     else {
       const int nk = (EPI == EPI_SLAB_F32 && a.k_split_len ? a.k_split_len : a.K) / GEMM_BK;
@@ -119,7 +118,6 @@ inline int launch_gemm(GemmArgs a, hipStream_t st, const char* prof_name) {
     }
   }
   if (fits && a.tile_hint == 256) choice = 256;
-  if (force128) choice = 128;
   if (choice == 256) return launch_gemm_t<EPI, Tile256>(a, st, prof_name);
   if constexpr (WIDE_OK) {
     if (choice == 192) return launch_gemm_t<EPI, TileWide>(a, st, prof_name);

@@ -163,23 +163,6 @@ __global__ void __launch_bounds__(512, 2) k_gemm_resid_ln(const GemmLnArgs a) {
     const char* tR = sW + wslot * LN_R_BYTES + offR;
     const char* tL = sA + (kt & 1) * LN_L_BYTES + offL;
     wslot = wslot == 2 ? 0 : wslot + 1;
-#ifdef CONVDR_LN_FRAG_JIT   // the round 1-4 form (A/B builds): hipcc read each weight fragment right before the MFMA pair that uses it
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int ch = ((2 * s + w.hi) ^ sw) * 16;
-      bf16x8 fa[T::MT], fb[T::NT];
-#pragma unroll
-      for (int j = 0; j < T::NT; ++j) fb[j] = *(const bf16x8*)(tL + j * 32 * 64 + ch);
-#pragma unroll
-      for (int i = 0; i < T::MT; ++i) fa[i] = *(const bf16x8*)(tR + i * 32 * 64 + ch);
-#pragma unroll
-      for (int i = 0; i < T::MT; ++i) {
-#pragma unroll
-        for (int j = 0; j < T::NT; ++j)
-          acc.c[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc.c[i][j], 0, 0, 0);
-      }
-    }
-#else
     // Round 5: ROLLING fragment prefetch.  A slice is 12 (weight fragment, MFMA pair) units (2 sub-steps x 6 feature blocks);
     // with 192 accumulators there is no room for a second fragment set, and left to itself hipcc read each weight fragment
     // right before its MFMA pair and waited for it at once (`ds_read x 2; s_waitcnt lgkmcnt(1); mfma x 2`): one exposed LDS
@@ -216,7 +199,6 @@ __global__ void __launch_bounds__(512, 2) k_gemm_resid_ln(const GemmLnArgs a) {
         __builtin_amdgcn_sched_group_barrier(0x008, T::NT, 0);                      // the unit's MFMA pair
       }
     }
-#endif
     // the weight slice of step t + 2 once this wave's MFMAs of the step are in the pipe: the ~60-cycle issue stalls then
     // cost no matrix-pipe time (two steps of slack for the landing)
     if (issue_w) ln_stage32<T::TR, LN_W_WAVES, LN_W_FIRST>(srcW, kt + 2, w_dst, w.wave, w_slice_stride);

@@ -280,15 +280,11 @@ __device__ __forceinline__ int gemm_nt_mainloop(const TileSrc<T>& src, int K, ch
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if (s + 1 < 4) load_frags(s + 1, (s + 1) & 1);
-#if defined(CONVDR_FRAG_BLOCK) || defined(CONVDR_FRAG_BLOCK_2STAGE)
-      __builtin_amdgcn_sched_barrier(0);   // the prefetch stays ahead of this sub-step's MFMAs
-#endif
 #pragma unroll
       for (int i = 0; i < T::MT; ++i)
 #pragma unroll
         for (int j = 0; j < T::NT; ++j)
           acc.c[i][j] = mfma_32x32x16<F16>(fa[s & 1][i], fb[s & 1][j], acc.c[i][j]);
-#if !defined(CONVDR_FRAG_BLOCK) && !defined(CONVDR_FRAG_BLOCK_2STAGE)
       if (s + 1 < 4) {   // fragment reads of sub-step s + 1 threaded between this sub-step's MFMAs (see the R3 loop below)
 #pragma unroll
         for (int r = 0; r < T::MT + T::NT && r < T::MT * T::NT; ++r) {
@@ -298,7 +294,6 @@ __device__ __forceinline__ int gemm_nt_mainloop(const TileSrc<T>& src, int K, ch
         __builtin_amdgcn_sched_group_barrier(0x100, T::MT + T::NT, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, T::MT * T::NT, 0);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
     CONVDR_STEP_TRACE(4)
@@ -423,19 +418,14 @@ __device__ __forceinline__ R3Slots gemm_nt_mainloop_r3(const TileSrcAll<T>& src,
     // six reads of all eight waves hit the LDS together (48 KB per sub-step at once) and every wave's first MFMA of the
     // sub-step waited out that queue; threaded, the LDS sees one read per wave per ~32 cycles.  Main loop of the stand-alone
     // prototype (tools/proto/w16_proto.hip): 2,744 -> 2,569 ticks per K step (2,485 with no fragment reads at all).
-    // CONVDR_FRAG_BLOCK=1 at compile time gives the round-2..4 form back (A/B builds).
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       if (s + 1 < 4) load_frags(s + 1, (s + 1) & 1);
-#ifdef CONVDR_FRAG_BLOCK
-      __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
       for (int i = 0; i < T::MT; ++i)
 #pragma unroll
         for (int j = 0; j < T::NT; ++j)
           acc.c[i][j] = mfma_32x32x16<F16>(fa[s & 1][i], fb[s & 1][j], acc.c[i][j]);
-#ifndef CONVDR_FRAG_BLOCK
       if (s + 1 < 4) {
 #pragma unroll
         for (int r = 0; r < T::MT + T::NT && r < T::MT * T::NT; ++r) {
@@ -445,7 +435,6 @@ __device__ __forceinline__ R3Slots gemm_nt_mainloop_r3(const TileSrcAll<T>& src,
         __builtin_amdgcn_sched_group_barrier(0x100, T::MT + T::NT, 0);   // (tiles with fewer MFMAs than reads: the rest of the reads)
         __builtin_amdgcn_sched_group_barrier(0x008, T::MT * T::NT, 0);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
     CONVDR_R3_STEP(4)

@@ -269,17 +269,9 @@ __device__ __forceinline__ void gemm_tn_mainloop_r3(const TnStageSrc<T::TR, T::W
     // the L chunk of step t + 1 under the first fragments' LDS round trip (its slot was read in step t - 1: free since the barrier)
     if (!r_wave && kt + 1 < nk) srcL.issue(kt + 1, sL + (ls ^ 1) * C::L_BYTES, iw);
     tn_wait_frags<NFRAG_READS, T::MT, T::NT>(fa[0], fb[0]);
-#ifdef CONVDR_TN_FRAG_BLOCK
-    CONVDR_TN_MMA(0)
-    CONVDR_TN_LOAD(2, 0)
-    tn_wait_frags<NFRAG_READS, T::MT, T::NT>(fa[1], fb[1]);
-    CONVDR_TN_MMA(1)
-    CONVDR_TN_LOAD(3, 1)
-#else
     CONVDR_TN_MMA_LOAD(0, 2)
     tn_wait_frags<NFRAG_READS, T::MT, T::NT>(fa[1], fb[1]);
     CONVDR_TN_MMA_LOAD(1, 3)
-#endif
     tn_wait_frags<NFRAG_READS, T::MT, T::NT>(fa[0], fb[0]);
     CONVDR_TN_MMA(0)
     tn_wait_frags<0, T::MT, T::NT>(fa[1], fb[1]);
@@ -313,15 +305,7 @@ struct GemmTnArgs {
   int64_t rows;        // contraction length (common to the batch)
   int steps_per_split; // K steps (of 64 rows) per blockIdx.y
   int nsplit;
-  // Ordered in-place accumulation (nsplit > 1 and flags != nullptr): slice y of a tile adds its partial product into dW
-  // itself, AFTER slice y - 1 has (flags[tile] counts the slices that are done; zeroed before the launch).  The sum is
-  // evaluated in slice order whatever the timing -- deterministic like the slab form -- without the slab round trip
-  // (write + re-read of nsplit x the gradient) and its reduction launches.  It is what lets a contraction of ~140 K steps
-  // (configs[2]: 9 k token rows) be cut in two: 108 tiles of 256^2 fill 42 % of the CUs, 216 fill 84 %.  No deadlock:
-  // workgroups are dispatched in (y, x) order, so a waiting slice-y workgroup implies every slice-(y - 1) workgroup is
-  // already resident or done, and those never wait for anything younger.
-  int* flags;
-  // nsplit == 1 / ordered slices: the first slice STORES its product instead of adding it to what dW holds (the caller promises a
+  // nsplit == 1: the kernel STORES its product instead of adding it to what dW holds (the caller promises a
   // gradient buffer nobody has written yet: convdr_encoder_backward_fresh) -- no read of dW, and no fill of it before the backward
   int overwrite;
 };
@@ -347,12 +331,7 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm_tn(const GemmTnAr
   GemmAcc<T> acc;
   acc.zero();
   if (nk > 0) {
-#ifdef CONVDR_TN_TWO_STAGE
-    constexpr bool USE_R3 = false;
-#else
-    constexpr bool USE_R3 = TnCfg<T>::R3;
-#endif
-    if constexpr (USE_R3) {
+    if constexpr (TnCfg<T>::R3) {
       const int iw = w.wave < T::WAVES / 2 ? w.wave : w.wave - T::WAVES / 2;         // index among the waves of its role
       const TnStageSrc<T::TR, T::WAVES / 2> srcR(q.Rm, q.ldr, q.NR, r0, t_begin, a.rows, iw, w.lane);
       const TnStageSrc<T::TL, T::WAVES / 2> srcL(q.Lm, q.ldl, q.NL, l0, t_begin, a.rows, iw, w.lane);
@@ -364,18 +343,8 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm_tn(const GemmTnAr
       gemm_tn_mainloop<T>(srcR, srcL, nk, smem, acc, w);
     }
   }
-  const bool ordered = a.nsplit > 1 && a.flags != nullptr;
-  const bool slab = a.nsplit > 1 && !ordered;
+  const bool slab = a.nsplit > 1;
   float* out = q.out + (slab ? (size_t)blockIdx.y * q.NL * q.NR : (size_t)0);
-  if (ordered && blockIdx.y > 0) {
-    // wait for the previous slice of this tile (cdna guide, Guideline 16: poll relaxed, fence once, then plain loads)
-    if (threadIdx.x == 0) {
-      while (__hip_atomic_load(&a.flags[tile_g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (int)blockIdx.y)
-        __builtin_amdgcn_s_sleep(4);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-  }
 #pragma unroll
   for (int nt = 0; nt < T::NT; ++nt) {
     const int n = l0 + w.l_index(nt);
@@ -389,22 +358,13 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm_tn(const GemmTnAr
           const f32x16& v = acc.c[mt][nt];
           float4 o = make_float4(v[4 * gq + 0], v[4 * gq + 1], v[4 * gq + 2], v[4 * gq + 3]);
           float4* dst = (float4*)(out + (size_t)n * q.NR + k);
-          if (!slab && !(a.overwrite && blockIdx.y == 0)) {
+          if (!slab && !a.overwrite) {
             const float4 c = *dst;
             o.x += c.x; o.y += c.y; o.z += c.z; o.w += c.w;
           }
           *dst = o;
         }
       }
-  }
-  if (ordered && blockIdx.y + 1 < gridDim.y) {   // publish: this slice's sums are in dW
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(&a.flags[tile_g], (int)blockIdx.y + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
   }
 }
 

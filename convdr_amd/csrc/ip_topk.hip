@@ -988,10 +988,10 @@ __global__ void __launch_bounds__(1024) k_ip_finish(int64_t n, int k, int cap, c
 // ------------------------------------------------------------------------------------------
 // host-side plan shared by workspace sizing and the search call
 // ------------------------------------------------------------------------------------------
-constexpr int IP_TILE_128 = 0, IP_TILE_256 = 1, IP_TILE_TALL = 2;
+constexpr int IP_TILE_256 = 1, IP_TILE_TALL = 2;
 struct IpPlan {
   int big;           // scan tile class: IP_TILE_256 (more than 128 queries), IP_TILE_TALL (256 passages x 128 queries: the
-                     // HBM-bound regime), IP_TILE_128 (CONVDR_DBG_SCAN_TILE128: the round-1/2 small tile)
+                     // HBM-bound regime)
   int tr, tl;        // tile extent over passages / queries
   int nq_pad, nQt, nPt;
   int mode;          // -1: no threshold pass (n <= cap), else IP_MODE_FULL / IP_MODE_TOP2
@@ -1005,10 +1005,9 @@ int64_t g_ip_fused_finish = 1;   // convdr_set_option("ip_fused_finish"): 1 = k_
 
 static IpPlan ip_plan(int nq, int64_t n, int d, int k, int cap) {
   IpPlan p;
-  static const bool dbg_small = getenv("CONVDR_DBG_SCAN_TILE128") != nullptr;
-  p.big = dbg_small ? IP_TILE_128 : (nq > 128 ? IP_TILE_256 : IP_TILE_TALL);
-  p.tr = p.big == IP_TILE_128 ? Tile128::TR : Tile256::TR;
-  p.tl = p.big == IP_TILE_256 ? Tile256::TL : Tile128::TL;
+  p.big = nq > 128 ? IP_TILE_256 : IP_TILE_TALL;
+  p.tr = Tile256::TR;   // = TileTall::TR
+  p.tl = p.big == IP_TILE_256 ? Tile256::TL : TileTall::TL;
   p.nq_pad = (nq + p.tl - 1) / p.tl * p.tl;
   p.nQt = p.nq_pad / p.tl;
   p.nPt = (int)ceil_div64(n, p.tr);
@@ -1049,40 +1048,36 @@ static IpPlan ip_plan(int nq, int64_t n, int d, int k, int cap) {
 
 template <int MODE, class T, bool X3, bool F16>
 static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
-  static DeviceOnce attr_done;  // > 48 KB dynamic LDS needs the opt-in once per kernel and device
-  if (attr_done.first())
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, X3, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         T::SMEM_BYTES));
   const unsigned tiles = (unsigned)a.nPt * (unsigned)a.nQt;
-  static const bool r3 = getenv("CONVDR_DBG_SCAN_NO_R3") == nullptr;   // A/B switch: the two-stage loop
-  if constexpr (MODE == IP_MODE_EMIT && !X3 && T::TR == 256) {
-    if (r3) {
-      constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
-      static DeviceOnce attr3;
-      if (attr3.first())
-        CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, R3_SMEM));
-      ScanArgs b = a;
+  if constexpr (MODE == IP_MODE_EMIT && !X3) {   // the two-stage loop
+    constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
+    static DeviceOnce attr3;  // > 48 KB dynamic LDS needs the opt-in once per kernel and device
+    if (attr3.first())
+      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, R3_SMEM));
+    ScanArgs b = a;
 #ifdef CONVDR_ENABLE_TRACE   // timing only (every threshold = +inf: results are garbage): `make TRACE=1` library only
-      if (getenv("CONVDR_DBG_SCAN_NOEMIT")) b.nq = 0;
-      if (getenv("CONVDR_DBG_PRELANDED")) b.dbg_prelanded = 1;
+    if (getenv("CONVDR_DBG_SCAN_NOEMIT")) b.nq = 0;
+    if (getenv("CONVDR_DBG_PRELANDED")) b.dbg_prelanded = 1;
 #endif
-      ProfScope prof("ip_scan_emit", st);
-      hipLaunchKernelGGL((k_ip_scan_r3<T, F16>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS), R3_SMEM, st, b);
-      CONVDR_CHECK_LAUNCH("k_ip_scan_r3");
-      return 0;
-    }
-  }
-  static const bool one_tile_per_wg = getenv("CONVDR_DBG_SCAN_NONPERSISTENT") != nullptr;   // A/B switch for the walk
-  const unsigned slots = (unsigned)device_cu_count() * (T::SMEM_BYTES > 80 * 1024 ? 1u : 2u);
-  const unsigned grid = one_tile_per_wg ? tiles : std::min(tiles, slots);
-  ProfScope prof(MODE == IP_MODE_EMIT ? "ip_scan_emit" : "ip_scan_sample", st);
-  ScanArgs b = a;
+    ProfScope prof("ip_scan_emit", st);
+    hipLaunchKernelGGL((k_ip_scan_r3<T, F16>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS), R3_SMEM, st, b);
+    CONVDR_CHECK_LAUNCH("k_ip_scan_r3");
+  } else {
+    static DeviceOnce attr_done;
+    if (attr_done.first())
+      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, X3, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           T::SMEM_BYTES));
+    const unsigned slots = (unsigned)device_cu_count() * (T::SMEM_BYTES > 80 * 1024 ? 1u : 2u);
+    const unsigned grid = std::min(tiles, slots);
+    ProfScope prof(MODE == IP_MODE_EMIT ? "ip_scan_emit" : "ip_scan_sample", st);
+    ScanArgs b = a;
 #ifdef CONVDR_ENABLE_TRACE
-  static const bool no_emit = getenv("CONVDR_DBG_SCAN_NOEMIT") != nullptr;   // timing only: every threshold = +inf
-  if (no_emit) b.nq = 0;
+    static const bool no_emit = getenv("CONVDR_DBG_SCAN_NOEMIT") != nullptr;   // timing only: every threshold = +inf
+    if (no_emit) b.nq = 0;
 #endif
-  hipLaunchKernelGGL((k_ip_scan<MODE, T, X3, F16>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
-  CONVDR_CHECK_LAUNCH("k_ip_scan");
+    hipLaunchKernelGGL((k_ip_scan<MODE, T, X3, F16>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
+    CONVDR_CHECK_LAUNCH("k_ip_scan");
+  }
   return 0;
 }
 
@@ -1094,8 +1089,7 @@ static int launch_scan_t(const ScanArgs& a, hipStream_t st) {
 template <int MODE, bool F16>
 static int launch_scan_k(const ScanArgs& a, int tile, hipStream_t st) {
   if (tile == IP_TILE_256) return launch_scan_t<MODE, Tile256, F16>(a, st);
-  if (tile == IP_TILE_TALL) return launch_scan_t<MODE, TileTall, F16>(a, st);
-  return launch_scan_t<MODE, Tile128, F16>(a, st);
+  return launch_scan_t<MODE, TileTall, F16>(a, st);
 }
 template <int MODE>
 static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) {

@@ -53,10 +53,7 @@ struct TrainBufs {
 
 constexpr int TRAIN_MAX_LAYERS = 48;
 constexpr int CLS_MAX_SPLIT = 16;   // contraction slices of the compact (CLS-row) projections of the last layer
-#ifndef CONVDR_LN_BWD_BLOCKS
-#define CONVDR_LN_BWD_BLOCKS 768
-#endif
-constexpr int LN_BWD_BLOCKS = CONVDR_LN_BWD_BLOCKS;
+constexpr int LN_BWD_BLOCKS = 768;
 constexpr int EMB_BWD_BLOCKS = 512;   // (k_embed_bwd keeps a 48 KB staging image per workgroup: three per CU)
 static_assert(EMB_BWD_BLOCKS <= LN_BWD_BLOCKS, "p.part is sized by LN_BWD_BLOCKS");
 constexpr int COLSUM_CHUNKS = 64;
@@ -239,9 +236,9 @@ struct WgradFork {
     CONVDR_CHECK_HIP(hipStreamWaitEvent(main, fin, 0));
     return 0;
   }
-  int layer_done(int l, hipStream_t side_or_main) {   // both chains have enqueued the last gradient writes of layer l
+  int layer_done(int l) {   // both chains have enqueued the last gradient writes of layer l
     CONVDR_CHECK_HIP(hipEventRecord(layer_main[l], main));
-    CONVDR_CHECK_HIP(hipEventRecord(layer_side[l], side_or_main));
+    CONVDR_CHECK_HIP(hipEventRecord(layer_side[l], side));
     return 0;
   }
 };
@@ -300,12 +297,6 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
   }
   const int steps = (int)ceil_div64(rows, 64);
   int nsplit = 1;
-  bool ordered = false;
-  // Ordered in-place slices are OFF by default: at the configs[2] size they cut the launch from 3.5 to 2.2 ms of kernel
-  // time per step (216 instead of 108 workgroups) and make the STEP 2 % slower (12.09 vs 11.85 ms, A/B on one box, round
-  // 3) -- the branch runs beside the activation-gradient chain, which is the critical path and loses the compute units
-  // the wider launch takes.  CONVDR_WGRAD_SPLIT=1 turns them on (convdr_wgrad callers with nothing running beside).
-  static const bool no_ordered = !(getenv("CONVDR_WGRAD_SPLIT") && atoi(getenv("CONVDR_WGRAD_SPLIT")));
   if (tail_split > 1 && slab && steps < 512) {
     // the last branch of a backward pass has nothing left to hide behind: one tile's whole contraction (~250 us at
     // configs[2]) is the tail of the step, so it is cut into slab slices that fill the idle chip
@@ -318,16 +309,6 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
     if (nsplit > steps / 256) nsplit = steps / 256;
     if ((size_t)nsplit * elems > slab_elems) nsplit = (int)(slab_elems / elems);
     if (nsplit < 1) nsplit = 1;
-  } else if (slab && !no_ordered && steps >= 64 && 2 * tiles <= device_cu_count() * (TnCfg<T>::SMEM_BYTES > 80 * 1024 ? 1 : 2) &&
-             (size_t)tiles * sizeof(int) <= slab_elems * sizeof(float)) {
-    // short contraction, the tiles fill at most half of the chip (configs[2]: 141 K steps, 108 tiles on 256 CUs):
-    // ordered in-place slices of >= 32 K steps, all workgroups resident at once (see GemmTnArgs::flags)
-    const int slots = device_cu_count() * (TnCfg<T>::SMEM_BYTES > 80 * 1024 ? 1 : 2);
-    nsplit = slots / tiles;
-    if (nsplit > steps / 32) nsplit = steps / 32;
-    if (nsplit > 4) nsplit = 4;
-    ordered = nsplit > 1;
-    if (!ordered) nsplit = 1;
   }
   // the operand windows are addressed with 32-bit byte offsets (buffer descriptors): a contraction slice must stay below
   // 2 GiB -- very long row counts are cut into more slab slices by themselves (when there is a slab to hold them)
@@ -336,7 +317,7 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
   const int64_t window_steps = (((int64_t)1 << 31) - 1) / (64 * max_ld * 2);
   if (window_steps >= 1 && steps > window_steps * nsplit && slab) {
     const int need = (int)ceil_div64(steps, window_steps);
-    if ((size_t)need * elems <= slab_elems) { nsplit = need; ordered = false; }
+    if ((size_t)need * elems <= slab_elems) nsplit = need;
   }
   g.steps_per_split = (steps + nsplit - 1) / nsplit;
   if (g.steps_per_split < 1) g.steps_per_split = 1;
@@ -345,12 +326,8 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
   CONVDR_REQUIRE((int64_t)g.steps_per_split * 64 * max_ld * 2 < ((int64_t)1 << 31),
                  "wgrad: a contraction slice of %d x 64 rows x %lld columns exceeds the 2 GiB operand window (pass a slab so "
                  "that it can be split)", g.steps_per_split, (long long)max_ld);
-  g.flags = nullptr;
   g.overwrite = t_bwd_overwrite ? 1 : 0;
-  if (ordered && nsplit > 1) {
-    g.flags = (int*)slab;
-    CONVDR_CHECK_HIP(hipMemsetAsync(g.flags, 0, (size_t)tiles * sizeof(int), st));
-  } else if (nsplit > 1) {
+  if (nsplit > 1) {
     size_t o = 0;
     for (int i = 0; i < count; ++i) {
       g.p[i].out = slab + o;
@@ -361,11 +338,11 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
     ProfScope prof("gemm_wgrad", st);
     if (!(dbg_skip() & 8))
       hipLaunchKernelGGL((k_gemm_tn<T>), dim3((unsigned)tiles, (unsigned)nsplit), dim3(T::THREADS), TnCfg<T>::SMEM_BYTES, st, g);
-    if ((dbg_double() & 4) && t_bwd_overwrite && !g.flags)   // (stores or slabs: idempotent)
+    if ((dbg_double() & 4) && t_bwd_overwrite)   // (stores or slabs: idempotent)
       hipLaunchKernelGGL((k_gemm_tn<T>), dim3((unsigned)tiles, (unsigned)nsplit), dim3(T::THREADS), TnCfg<T>::SMEM_BYTES, st, g);
     CONVDR_CHECK_LAUNCH("k_gemm_tn");
   }
-  if (nsplit > 1 && !g.flags)
+  if (nsplit > 1)
     for (int i = 0; i < count; ++i) {
       const int64_t n = (int64_t)g.p[i].NL * g.p[i].NR;
       hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)(ceil_div64(n / 4, 256) < 2048 ? ceil_div64(n / 4, 256) : 2048)),
@@ -409,14 +386,12 @@ static int ln_bwd_kernel(const float* dY, const bf16_t* dYadd, const float* Yin,
   if (!(dbg_skip() & 2))
   for (int rep = 0; rep < ((dbg_double() & 64) ? 2 : 1); ++rep)
   {
-    // g_ln_bwd_rows (option "ln_bwd_rows" / CONVDR_LN_BWD_ROWS): 0 = the general kernel everywhere (A/B), 1 = straight-line form without, 2 (default) = with the
-    // register prefetch of the next row; CONVDR_LN_BWD_GRID: workgroups of the straight-line form.  configs[2] step, medians of
-    // three alternations on one box: 9.16 ms (0) -> 8.96 (2), 8.93-8.96 for (1) and for grids 384 / 444 / 512 -- the 24
-    // launches of a step 0.94 -> 0.74 ms (profiles/r05_ab_ln_bwd_rows.txt).
+    // g_ln_bwd_rows (option "ln_bwd_rows"): 0 = the general kernel everywhere (A/B), 1 = straight-line form without, 2 (default) = with the
+    // register prefetch of the next row.  configs[2] step, medians of three alternations on one box: 9.16 ms (0) -> 8.96 (2),
+    // 8.93-8.96 for (1) and for straight-line grids of 384 / 444 / 512 workgroups -- the 24 launches of a step 0.94 -> 0.74 ms
+    // (profiles/r05_ab_ln_bwd_rows.txt).
     const int mode = (int)g_ln_bwd_rows;
-    static const int grid_env = getenv("CONVDR_LN_BWD_GRID") ? atoi(getenv("CONVDR_LN_BWD_GRID")) : 0;
     if (mode && H == 768 && dY && dYadd && dXf && dXb && !row_map) {
-      if (grid_env > 0 && grid_env < blocks) blocks = grid_env;
       if (mode == 2)
         hipLaunchKernelGGL((k_layernorm_bwd_rows<3, true, 3>), dim3(blocks), dim3(256), 0, st, dY, dYadd, Yin, rows, g, eps, dXf, dXb, part, drop);
       else
@@ -647,17 +622,15 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
   const float* dcls = d_out;  // gradient w.r.t. LayerNorm2(cls rows) of the last layer
 
   WgradFork& wf = WgradFork::get();
-  static const bool fork_wgrad = !(getenv("CONVDR_NO_WGRAD_FORK") && atoi(getenv("CONVDR_NO_WGRAD_FORK")));
   if (int e = wf.init(st)) return e;
-  hipStream_t ss = fork_wgrad ? wf.side : st;   // stream of the weight-gradient branches
+  hipStream_t ss = wf.side;   // stream of the weight-gradient branches
   // The head and the CLS-row LayerNorm are a chain of ~6 launches of a few microseconds each in front of the first big kernel:
   // what only FINISHES parameter gradients (the two partial-sum reductions, the head's weight gradient) goes to the
-  // weight-gradient stream, off that chain (round 5; CONVDR_HEAD_WGRAD_INLINE=1: on the main stream as in rounds 1-4).
-  static const bool head_inline = getenv("CONVDR_HEAD_WGRAD_INLINE") && atoi(getenv("CONVDR_HEAD_WGRAD_INLINE"));
+  // weight-gradient stream, off that chain (round 5).
   // (the two LayerNorm backwards keep their partial sums apart: the second one starts while the first one's reduction may
   //  still be pending on the other stream)
   const int64_t part2_off = (int64_t)ceil_div64(B, 4) * 3 * 1024;
-  const bool side_ok = fork_wgrad && !head_inline && 2 * ceil_div64(B, 4) <= LN_BWD_BLOCKS;
+  const bool side_ok = 2 * ceil_div64(B, 4) <= LN_BWD_BLOCKS;
   hipStream_t hs = side_ok ? ss : st;
   float* part2 = side_ok ? p.part + part2_off : p.part;
 
@@ -749,11 +722,10 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
           // tile of the four weight matrices: 108 for roberta-base) owns its CUs while this kernel runs: at 9.2 k rows 108
           // big tiles fit the ~148 free CUs in one round where 432 small ones need two.  Step 9.36 -> 9.21 ms (three
           // alternations, profiles/r05_ab_dgrad_tiles.txt); the QKV data-gradient GEMM the same way: -0.10 alone, nothing
-          // on top of this one.  CONVDR_DGRAD_FFN1_256=0: the cost model's choice (A/B).
-        static const bool off = getenv("CONVDR_DGRAD_FFN1_256") && !atoi(getenv("CONVDR_DGRAD_FFN1_256"));
+          // on top of this one.
         const int64_t wg_tiles = (int64_t)((I + 255) / 256) * ((H + 255) / 256) * 2 + (int64_t)((3 * H + 255) / 256 + (H + 255) / 256) * ((H + 255) / 256);
         const int64_t free_cus = device_cu_count() - (wg_tiles < device_cu_count() / 2 ? wg_tiles : device_cu_count() / 2);
-        if (!off && fork_wgrad && H % 256 == 0 && (int64_t)(H / 256) * ceil_div64(rows, 256) <= free_cus) g.tile_hint = 256;
+        if (H % 256 == 0 && (int64_t)(H / 256) * ceil_div64(rows, 256) <= free_cus) g.tile_hint = 256;
       }
       if (int e = launch_gemm<EPI_BF16>(g, st, "gemm_dgrad")) return e;
       // ---- LayerNorm1: dY1 = LN'(dY2 + dXb1) ----
@@ -830,8 +802,7 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
       CONVDR_CHECK_LAUNCH("k_attention_bwd");
     }
     // ---- the layer's weight-gradient branch: every operand is complete now; it runs beside the layers below ----
-    if (fork_wgrad)
-      if (int e = wf.fork()) return e;
+    if (int e = wf.fork()) return e;
     for (int rep = 0; rep < ((dbg_double() & 128) && t_bwd_overwrite ? 2 : 1); ++rep) {
       if (dbg_skip() & 32) {   // (timing bound only: zero partials instead of the column sums)
         CONVDR_CHECK_HIP(hipMemsetAsync(d.part_bqkv, 0, sizeof(float) * (size_t)chunks * 3 * H, ss));
@@ -859,8 +830,8 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
                                   {d.dYb, H, H, s.Hm, I, I, lg->w2},            // Y2 = Hm W2^T
                                   {d.dQKV, 3 * H, 3 * H, s.Xin, H, H, lg->wqkv},   // QKV = Xin Wqkv^T
                                   {d.dYb2, H, H, s.ctx, H, H, lg->wo}};         // Y1 = ctx Wo^T
-      static const int tail_split = getenv("CONVDR_WGRAD_TAIL_SPLIT") ? atoi(getenv("CONVDR_WGRAD_TAIL_SPLIT")) : 2;
-      if (int e = wgrad_batch(items, 4, rows, p.slab, p.slab_elems, ss, l == 0 && fork_wgrad ? tail_split : 0)) return e;
+      // (the last branch of the pass goes out as two slab slices: wgrad_launch, tail_split)
+      if (int e = wgrad_batch(items, 4, rows, p.slab, p.slab_elems, ss, l == 0 ? 2 : 0)) return e;
     } else {
       // three of the four products contract over the B CLS rows only (one 64-token K step); the QKV projection saw every row
       const WgradItem items_c[3] = {{p.c_dHpre, I, I, p.c_X1, H, H, lg->w1}, {p.c_dYb, H, H, p.c_Hm, I, I, lg->w2},
@@ -874,7 +845,7 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
     g.rows = rows; g.W = (const bf16_t*)lt->wqkv_t; g.X = d.dQKV; g.N = H; g.K = 3 * H; g.Cb = p.dXb2;
     if (int e = launch_gemm<EPI_BF16>(g, st, "gemm_dgrad")) return e;
     cur_f = dY1; cur_b = p.dXb2;   // d(output of layer l - 1) = dY1 + dXb2
-    if (int e = wf.layer_done(l, ss)) return e;
+    if (int e = wf.layer_done(l)) return e;
   }
   wf.layers_recorded = NL;
   // ---- embeddings ----
@@ -901,8 +872,7 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
     if (int e = r.launch(st)) return e;
   }
   CONVDR_CHECK_HIP(hipEventRecord(wf.emb_main, st));   // convdr_backward_wait_layer(-1): the embedding gradients, ahead of the join
-  if (fork_wgrad)
-    if (int e = wf.join()) return e;   // every weight gradient is complete for whatever follows on `stream`
+  if (int e = wf.join()) return e;   // every weight gradient is complete for whatever follows on `stream`
   return 0;
 }
 

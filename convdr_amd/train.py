@@ -86,9 +86,6 @@ def _arena_owner(P):
     return tower
 
 
-_PACKT_FROM_BF16 = os.environ.get("CONVDR_PACKT_FROM_BF16", "1") != "0"      # 0: from the fp32 master weights (A/B)
-
-
 def _packed_t(tower, head):
     """Transposed bf16 weights for the data-gradient GEMMs (cached with the forward packing)."""
     c, w, keep = tower.packed(head)
@@ -108,23 +105,17 @@ def _packed_t(tower, head):
             mats.append((head[0].weight, 1))
         n = (C.c_int32 * len(mats))(*[p.shape[0] * mul for p, mul in mats])
         k = (C.c_int32 * len(mats))(*[p.shape[1] for p, _ in mats])
-        src = (C.c_int64 * len(mats))(*[flat["off"][id(p)] for p, _ in mats])
         dsts = np.concatenate([[0], np.cumsum([int(a) * int(b) for a, b in zip(n, k)])]).astype(np.int64)
         dst = (C.c_int64 * len(mats))(*dsts[:-1].tolist())
         T = flat.get("Pt")
         if T is None:
             T = flat["Pt"] = torch.empty(int(dsts[-1]), dtype=torch.bfloat16, device=dev)
         with torch.cuda.device(dev):
-            Pb = flat.get("Pb")
-            if Pb is not None and _PACKT_FROM_BF16:
-                # tower.packed() above made sure the bf16 copy of the weight range is current (cast, or rewritten by the optimizer
-                # step itself): transposing THAT moves a third less data than re-rounding the fp32 master weights, same bits
-                srcb = (C.c_int64 * len(mats))(*[flat["off"][id(p)] - flat["w0"] for p, _ in mats])
-                _lib.check(L.convdr_pack_transposed_bf16(_lib.ptr(Pb), len(mats), srcb, n, k, dst, _lib.ptr(T), _lib.stream_ptr()),
-                           "convdr_pack_transposed_bf16")
-            else:
-                _lib.check(L.convdr_pack_transposed(_lib.ptr(flat["P"]), len(mats), src, n, k, dst, _lib.ptr(T), _lib.stream_ptr()),
-                           "convdr_pack_transposed")
+            # tower.packed() above made sure the bf16 copy of the weight range is current (cast, or rewritten by the optimizer
+            # step itself): transposing THAT moves a third less data than re-rounding the fp32 master weights, same bits
+            srcb = (C.c_int64 * len(mats))(*[flat["off"][id(p)] - flat["w0"] for p, _ in mats])
+            _lib.check(L.convdr_pack_transposed_bf16(_lib.ptr(flat["Pb"]), len(mats), srcb, n, k, dst, _lib.ptr(T), _lib.stream_ptr()),
+                       "convdr_pack_transposed_bf16")
         arr = (_lib.LayerWeightsT * len(tower.encoder.layer))()
         for i in range(len(tower.encoder.layer)):
             arr[i].wqkv_t, arr[i].wo_t, arr[i].w1_t, arr[i].w2_t = [T.data_ptr() + 2 * int(dsts[4 * i + j]) for j in range(4)]
@@ -322,7 +313,6 @@ def _lens_and_check(ids, mask, vocab, seq_lens=None):
     return lens_dev, lens_host
 
 
-_FRESH_BWD = os.environ.get("CONVDR_FRESH_BWD", "1") != "0"      # 0: the whole arena filled + convdr_encoder_backward (rounds 2-5; A/B)
 _POISON_FRESH_ARENA = False      # tests: NaN in every gradient the backward is supposed to STORE (convdr_encoder_backward_fresh)
 
 
@@ -381,10 +371,7 @@ class _EncoderFn(torch.autograd.Function):
                 ctx.packed_t = _packed_t(tower, head)
                 if _POISON_FRESH_ARENA:
                     ctx.grad_arena.fill_(float("nan"))
-                if _FRESH_BWD:
-                    ctx.grad_arena[:ctx.fresh_prefix].zero_()
-                else:
-                    ctx.grad_arena.zero_()
+                ctx.grad_arena[:ctx.fresh_prefix].zero_()
                 ctx.packed_t_ready = side.record_event()
         ctx.tower, ctx.head, ctx.dropout = tower, head, dropout
         ctx.packed = (c, w, _keep)           # the weights cannot change between a forward and its backward
@@ -435,7 +422,7 @@ class _EncoderFn(torch.autograd.Function):
             dropout = ctx.dropout
             drop = None if dropout is None else C.byref(_lib.Dropout(float(dropout[0]), float(dropout[1]), int(dropout[2]) & 0xffffffff))
             # (`flat` is this call's own arena: nothing else has written it -- autograd adds the views to existing .grad itself)
-            _lib.check((L_.convdr_encoder_backward_fresh if _FRESH_BWD else L_.convdr_encoder_backward)(C.byref(c), C.byref(w), wt, _lib.ptr(cu), _lib.ptr(seq_lens),
+            _lib.check(L_.convdr_encoder_backward_fresh(C.byref(c), C.byref(w), wt, _lib.ptr(cu), _lib.ptr(seq_lens),
                                                         C.c_void_p(head_t) if head_t else None, B, rows, max_len, _lib.ptr(ws),
                                                         ws.numel(), _lib.ptr(go), C.byref(gr), drop, _lib.stream_ptr()),
                        "convdr_encoder_backward_fresh")
@@ -641,9 +628,6 @@ def _flat_view(tensors):
     return torch.as_strided(base, (n,), (1,), base.storage_offset())
 
 
-_EMB_SUMSQ_MAIN = os.environ.get("CONVDR_EMB_SUMSQ_MAIN", "0") == "1"     # A/B: the embedding slice's sum behind the backward's join (rounds 3-4)
-
-
 def _overlapped_sumsq(flat, tower, scratch, dev):
     """Sum of squares of a FRESH gradient arena, piece by piece: every encoder layer's slice on a side stream as soon as
     the backward's completion events say it is final (convdr_backward_wait_layer) -- under the backward of the layers
@@ -669,7 +653,7 @@ def _overlapped_sumsq(flat, tower, scratch, dev):
     b0, e1 = int(offs[5]), int(offs[5 + 16 * nl])
     with torch.cuda.stream(side):
         for l in reversed(range(nl)):
-            if l == 0 and not _EMB_SUMSQ_MAIN:
+            if l == 0:
                 # the embedding slice (a third of the arena) is written by the main chain's last kernels, BEFORE that chain
                 # waits for layer 0's weight-gradient branch: summed here, beside that branch, instead of behind the join
                 # (and ahead of layer 0's slice on this stream, whose event is that branch's end)
@@ -680,8 +664,6 @@ def _overlapped_sumsq(flat, tower, scratch, dev):
             _lib.check(L.convdr_backward_wait_layer(l, side.cuda_stream), "convdr_backward_wait_layer")
             _lib.check(L.convdr_grad_sumsq(C.c_void_p(base + 4 * b), e - b, C.c_void_p(sbase + 4 * l * per), per, side.cuda_stream),
                        "convdr_grad_sumsq")
-    if _EMB_SUMSQ_MAIN:
-        _lib.check(L.convdr_grad_sumsq(C.c_void_p(base), b0, C.c_void_p(sbase + 4 * nl * per), nb_emb, main.cuda_stream), "convdr_grad_sumsq")
     _lib.check(L.convdr_grad_sumsq(C.c_void_p(base + 4 * e1), flat.numel() - e1, C.c_void_p(sbase + 4 * (nl * per + nb_emb)), nb_head,
                                    main.cuda_stream), "convdr_grad_sumsq")
     main.wait_stream(side)
@@ -1349,7 +1331,7 @@ def train_step(args, model, teacher_model, optimizer, scheduler, batch, doc_ids=
     # the stored gradient by it -- a fill and an elementwise launch on the chain between forward and backward -- so the
     # encoder's backward is seeded with the gradient itself (bit-identical: the factor is exactly 1.0)
     direct = (not getattr(args, "no_mse", False) and not getattr(args, "ranking_task", False) and gas == 1 and loss_weight == 1.0
-              and embs.requires_grad and os.environ.get("CONVDR_KD_DIRECT_BACKWARD", "1") != "0")
+              and embs.requires_grad)
     if direct:
         loss1, seed = _mse_value_and_grad(embs, teacher_embs)
         embs.backward(seed)
