@@ -106,3 +106,53 @@ def trained_like_(model, seed=0, outlier_dims=(77, 588, 391), outlier_value=(-40
                 rows = diag_heads * (p.shape[0] // model.config.num_attention_heads)
                 p[:rows] = diag_scale * q[:rows]
     return model
+
+
+# ---- scratch-memory fills ---------------------------------------------------------------------------------------
+# tests/test_stale_memory_gpu.py: "same inputs, other garbage in the scratch memory -> identical bits out".
+FILLS = ("Z", "N", "R")        # zeros (the baseline), bytes 0xFF (NaN as bf16 / fp16 / fp32, -1 as an integer), seeded random bytes
+
+
+def fill_bytes(t, kind, seed=0):
+    """Overwrite every byte of the contiguous tensor `t` (any dtype, any device) with fill `kind`."""
+    import torch
+    assert t.is_contiguous()
+    b = t.reshape(-1).view(torch.uint8)
+    if kind == "Z":
+        b.zero_()
+    elif kind == "N":
+        b.fill_(0xFF)
+    elif kind == "R":
+        g = torch.Generator(device=b.device).manual_seed(seed)
+        b.copy_(torch.randint(0, 256, (b.numel(),), generator=g, dtype=torch.uint8, device=b.device))
+    else:
+        raise ValueError(kind)
+    return t
+
+
+def assert_fills_agree(runs, what=""):
+    """runs: {fill: (outputs, filled_ptrs, used_ptrs)} with outputs = {name: tensor}; "Z" must be there.
+    * every run used the buffers it filled (the host re-allocates a buffer that is too small: a fill of a buffer the
+      host then drops tests nothing),
+    * the Z outputs are finite,
+    * every output of every other fill is bit-identical to the Z run's (torch.equal: a NaN never compares equal)."""
+    import torch
+    assert "Z" in runs, "%s: no baseline run" % what
+    for f, (out, filled, used) in runs.items():
+        assert filled == used, "%s: fill %s went to a buffer the call did not use (%s vs %s)" % (what, f, filled, used)
+    ref = runs["Z"][0]
+    assert ref, "%s: no outputs" % what
+    for n, t in ref.items():
+        if t.dtype.is_floating_point:
+            assert bool(torch.isfinite(t).all()), "%s: %s is not finite under fill Z" % (what, n)
+    for f, (out, _, _) in runs.items():
+        if f == "Z":
+            continue
+        assert sorted(out) == sorted(ref), "%s: fill %s returned other outputs" % (what, f)
+        for n, t in ref.items():
+            o = out[n]
+            assert o.shape == t.shape and o.dtype == t.dtype, "%s: %s under fill %s: shape / dtype" % (what, n, f)
+            if not torch.equal(o, t):
+                bad = (o != t) | (o != o) if t.dtype.is_floating_point else (o != t)
+                raise AssertionError("%s: %s depends on the scratch memory: fill %s differs from fill Z in %d of %d elements"
+                                     % (what, n, f, int(bad.sum()), t.numel()))
