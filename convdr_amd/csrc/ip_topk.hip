@@ -1150,6 +1150,141 @@ extern "C" int convdr_topk_merge(const float* Da, const int64_t* Ia, int na, int
   return 0;
 }
 
+// ---- W-way merge of sorted per-query lists in one launch (the exchange step of the sharded search) ------------------
+// k_topk_merge taken from 2 lists to W.  One workgroup per query; the first m = min(n, n_out) scores of every list are
+// staged in LDS list after list (an entry past position n_out of its own list can never be output, and a count cut at
+// m >= n_out still pushes its element past the output).  Element j of list w goes to slot
+//   j + sum_{u < w} #{x in list u : x >= v} + sum_{u > w} #{x in list u : x > v}         (earlier lists win ties)
+// -- the stable descending sort of [list 0, ..., list W-1], i.e. the reference's `>=` merge chained over blocks 0..W-1 --
+// each count a binary search; the walk over u stops as soon as the slot has left the output, and elements below a
+// score that n_out others certainly reach are not searched for at all.  The lanes' searches diverge, so LDS bank
+// conflicts are the rule here (at most W * m * (W - 1) * log2 m dword reads per query: 39 k at 8 x 100).
+namespace convdr {
+struct MergeListsPlain {     // D / I + w * list_stride + q * ld
+  const float* D;
+  const int64_t* I;
+  int64_t list_stride, ld;
+  __device__ float score(int w, int q, int j) const { return D[w * list_stride + q * ld + j]; }
+  __device__ int64_t id(int w, int q, int j) const { return I[w * list_stride + q * ld + j]; }
+};
+struct MergeListsPacked {    // [nlists][nq][n] records of 3 dwords: score bits, offset low word, offset high word
+  const uint32_t* rec;
+  int64_t nq, n;
+  __device__ const uint32_t* at(int w, int q, int j) const { return rec + ((w * nq + q) * n + j) * 3; }
+  __device__ float score(int w, int q, int j) const { return __uint_as_float(at(w, q, j)[0]); }
+  __device__ int64_t id(int w, int q, int j) const {
+    const uint32_t* r = at(w, q, j);
+    return (int64_t)(((uint64_t)r[2] << 32) | (uint64_t)r[1]);
+  }
+};
+
+template <class Lists, int THREADS>
+__global__ void __launch_bounds__(THREADS) k_topk_merge_multi(Lists in, int nlists, int m, int n_out,
+                                                              float* __restrict__ Dout, int64_t* __restrict__ Iout,
+                                                              int64_t ldo) {
+  extern __shared__ float sm[];
+  const int q = blockIdx.x;
+  const int total = nlists * m;
+  Dout += q * ldo; Iout += q * ldo;
+  for (int e = threadIdx.x; e < total; e += THREADS) {
+    const int w = e / m;
+    sm[e] = in.score(w, q, e - w * m);
+  }
+  __syncthreads();
+  // Entry p = ceil(n_out / W) - 1 exists in every list (n_out <= W * n), and at least W * (p + 1) >= n_out entries are
+  // >= the smallest of those W scores: anything strictly below it cannot be output, whatever the tie rule.  With W
+  // like lists that leaves about n_out of the W * m elements to search for (all of them when one list is padding only).
+  const int p = (n_out + nlists - 1) / nlists - 1;
+  float floor_v = sm[p];
+  for (int u = 1; u < nlists; ++u) floor_v = fminf(floor_v, sm[u * m + p]);
+  for (int e = threadIdx.x; e < total; e += THREADS) {
+    const float v = sm[e];
+    if (v < floor_v) continue;
+    const int w = e / m, j = e - w * m;
+    int pos = j;
+    for (int u = 0; u < nlists && pos < n_out; ++u) {
+      if (u == w) continue;
+      const float* other = sm + u * m;
+      const bool earlier = u < w;
+      // first index of list u that does NOT precede v, looked for among the first `hi` entries only: a count of
+      // n_out - pos already puts the element past the output.  The last of them is probed first: an element that is
+      // out leaves after ONE read instead of a whole search (8 x 4096 lists, 100 queries: 133 -> 110 us).
+      int lo = 0, hi = m < n_out - pos ? m : n_out - pos;
+      const float last = other[hi - 1];
+      if (earlier ? (last >= v) : (last > v)) {
+        lo = hi;
+      } else {
+        --hi;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          const bool precedes = earlier ? (other[mid] >= v) : (other[mid] > v);
+          if (precedes) lo = mid + 1; else hi = mid;
+        }
+      }
+      pos += lo;
+    }
+    if (pos < n_out) {
+      Dout[pos] = v;
+      Iout[pos] = in.id(w, q, j);
+    }
+  }
+}
+
+constexpr int64_t TOPK_MERGE_MULTI_MAX = 32768;      // staged scores: 128 KB of the CU's 160 KB LDS
+
+template <class Lists, int THREADS>
+static int launch_topk_merge_multi(const Lists& in, int nlists, int m, int nq, int n_out, float* Dout, int64_t* Iout,
+                                   int64_t ldo, hipStream_t st) {
+  static DeviceOnce attr_done;
+  if (attr_done.first())
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_topk_merge_multi<Lists, THREADS>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(TOPK_MERGE_MULTI_MAX * 4)));
+  hipLaunchKernelGGL((k_topk_merge_multi<Lists, THREADS>), dim3(nq), dim3(THREADS), (size_t)nlists * m * 4, st, in, nlists, m,
+                     n_out, Dout, Iout, ldo);
+  CONVDR_CHECK_LAUNCH("k_topk_merge_multi");
+  return 0;
+}
+
+// 256 threads up to 4096 staged elements (k = 100 at W = 8: 800, three or four per thread); 1024 beyond (32 k elements)
+template <class Lists>
+static int topk_merge_multi(const Lists& in, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout, int64_t ldo,
+                            hipStream_t st) {
+  const int m = n < n_out ? n : n_out;
+  if ((int64_t)nlists * m <= 4096) return launch_topk_merge_multi<Lists, 256>(in, nlists, m, nq, n_out, Dout, Iout, ldo, st);
+  return launch_topk_merge_multi<Lists, 1024>(in, nlists, m, nq, n_out, Dout, Iout, ldo, st);
+}
+
+static bool topk_merge_multi_sizes_ok(int nlists, int n, int nq, int n_out) {
+  return nlists >= 1 && n >= 0 && n <= 4096 && nq >= 0 && n_out >= 0 && (int64_t)n_out <= (int64_t)nlists * n &&
+         (int64_t)nlists * (n < n_out ? n : n_out) <= TOPK_MERGE_MULTI_MAX;
+}
+}  // namespace convdr
+
+extern "C" int convdr_topk_merge_multi(const float* D, const int64_t* I, int nlists, int n, int64_t list_stride, int64_t ld,
+                                       int nq, int n_out, float* Dout, int64_t* Iout, int64_t ldo, convdr_stream_t stream) {
+  using namespace convdr;
+  CONVDR_REQUIRE(topk_merge_multi_sizes_ok(nlists, n, nq, n_out),
+                 "convdr_topk_merge_multi: bad sizes nlists=%d n=%d n_out=%d nq=%d (n <= 4096, nlists * min(n, n_out) <= %d, "
+                 "n_out <= nlists * n)", nlists, n, n_out, nq, (int)TOPK_MERGE_MULTI_MAX);
+  CONVDR_REQUIRE(ld >= n && ldo >= n_out && (nlists == 1 || nq == 0 || list_stride >= n),
+                 "convdr_topk_merge_multi: pitch smaller than the row (ld=%lld list_stride=%lld n=%d, ldo=%lld n_out=%d)",
+                 (long long)ld, (long long)list_stride, n, (long long)ldo, n_out);
+  if (nq == 0 || n_out == 0) return 0;
+  return topk_merge_multi(MergeListsPlain{D, I, list_stride, ld}, nlists, n, nq, n_out, Dout, Iout, ldo, (hipStream_t)stream);
+}
+
+extern "C" int convdr_topk_merge_packed(const void* lists, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout,
+                                        int64_t ldo, convdr_stream_t stream) {
+  using namespace convdr;
+  CONVDR_REQUIRE(topk_merge_multi_sizes_ok(nlists, n, nq, n_out),
+                 "convdr_topk_merge_packed: bad sizes nlists=%d n=%d n_out=%d nq=%d (n <= 4096, nlists * min(n, n_out) <= %d, "
+                 "n_out <= nlists * n)", nlists, n, n_out, nq, (int)TOPK_MERGE_MULTI_MAX);
+  CONVDR_REQUIRE(ldo >= n_out, "convdr_topk_merge_packed: pitch smaller than the row (ldo=%lld n_out=%d)", (long long)ldo, n_out);
+  if (nq == 0 || n_out == 0) return 0;
+  return topk_merge_multi(MergeListsPacked{(const uint32_t*)lists, (int64_t)nq, (int64_t)n}, nlists, n, nq, n_out, Dout, Iout,
+                          ldo, (hipStream_t)stream);
+}
+
 extern "C" int convdr_ip_column_mean(const float* p_f32, int64_t n, int d, float* scratch /* >= 1024 * d floats */,
                                      float* mean, convdr_stream_t stream) {
   CONVDR_REQUIRE(n > 0 && d > 0, "convdr_ip_column_mean: empty block");

@@ -2,9 +2,10 @@
 "gloo" in the CPU tests).  Only the steps that are real exchanges use a collective:
 
   corpus encode   no collective: rank r encodes records i % W == r and writes its own block pair (encode.py)
-  search          every rank searches its resident block with the replicated query matrix; the per-rank top-k lists
+  search          every rank searches its resident block -- or, with any number of block files on disk, its contiguous
+                  share of them (search_blocks_sharded) -- with the replicated query matrix; the per-rank top-k lists
                   (k scores + k record offsets per query: 9.6 MB at W = 8, Nq = 1k, k = 100) are all-gathered once and
-                  merged with the reference's tie rule "earlier block first" (run_convdr_inference.py:218);
+                  merged in one launch with the reference's tie rule "earlier block first" (run_convdr_inference.py:218);
                   queries encoded data-parallel are all-gathered first (3 MB at Nq = 1k)
   training        the reference uses single-process nn.DataParallel (run_convdr_train.py:77-78); here: one replica per
                   GPU, per-rank batches, ONE all-reduce of the flat fp32 gradient buffer per step (the backward already
@@ -30,33 +31,62 @@ def all_gather_rows(x, group=None, force=False):
     return torch.cat(parts, 0)
 
 
+_MERGE_MULTI_MAX_N = 4096          # convdr_topk_merge_multi / _packed: entries per list ...
+_MERGE_MULTI_MAX_STAGED = 32768    # ... and nlists * min(n, n_out), the scores one workgroup stages in LDS (128 KB)
+
+
+def _merge_multi_fits(W, n, n_out):
+    return 1 <= W and 0 <= n <= _MERGE_MULTI_MAX_N and W * min(n, n_out) <= _MERGE_MULTI_MAX_STAGED and 0 <= n_out <= W * n
+
+
 def merge_rank_topk(D_all, I_all, k):
     """D_all / I_all: [W, nq, k] per-rank results (each row sorted descending) -> global [nq, k].
     Ties keep the lower rank (= earlier block) first, then the earlier position: what chaining the reference's `>=`
-    two-way merge (run_convdr_inference.py:213-229) over blocks 0..W-1 gives.  On a GPU that chain is run literally with
-    the device merge kernel (convdr_topk_merge, k outputs per step: entries past rank k can never re-enter); CPU tensors
-    (the gloo tests) take a stable descending sort of the rank-ordered concatenation, the same permutation."""
+    two-way merge (run_convdr_inference.py:213-229) over blocks 0..W-1 gives.  On a GPU that is ONE launch of the W-way
+    merge kernel (convdr_topk_merge_multi: every element finds its own output slot) into one pair of output tensors; a
+    shape outside that kernel's contract (W * k > 32768, k > 4096) runs the chain literally with the two-way kernel
+    (`_merge_rank_topk_chain`).  CPU tensors (the gloo tests) take a stable descending sort of the rank-ordered
+    concatenation.  All three are the same permutation."""
     W, nq, kk = D_all.shape
     if D_all.is_cuda:
+        n_out = min(k, W * kk)
+        if W == 1 or not _merge_multi_fits(W, kk, n_out):
+            return _merge_rank_topk_chain(D_all, I_all, k)
         from . import _lib
         L = _lib.lib()
         D_all, I_all = D_all.contiguous(), I_all.contiguous()
-        Dm, Im = D_all[0], I_all[0]
+        Do = torch.empty((nq, n_out), dtype=torch.float32, device=D_all.device)
+        Io = torch.empty((nq, n_out), dtype=torch.int64, device=D_all.device)
         with torch.cuda.device(D_all.device):
-            for r in range(1, W):
-                na = Dm.shape[1]
-                no = min(k, na + kk)
-                Do = torch.empty((nq, no), dtype=torch.float32, device=D_all.device)
-                Io = torch.empty((nq, no), dtype=torch.int64, device=D_all.device)
-                _lib.check(L.convdr_topk_merge(_lib.ptr(Dm), _lib.ptr(Im), na, Dm.stride(0), _lib.ptr(D_all[r]), _lib.ptr(I_all[r]),
-                                               kk, D_all[r].stride(0), nq, no, _lib.ptr(Do), _lib.ptr(Io), Do.stride(0),
-                                               _lib.stream_ptr()), "convdr_topk_merge")
-                Dm, Im = Do, Io
-        return Dm[:, :k], Im[:, :k]
+            _lib.check(L.convdr_topk_merge_multi(_lib.ptr(D_all), _lib.ptr(I_all), W, kk, nq * kk, kk, nq, n_out, _lib.ptr(Do),
+                                                 _lib.ptr(Io), n_out, _lib.stream_ptr()), "convdr_topk_merge_multi")
+        return Do, Io
     d = D_all.permute(1, 0, 2).reshape(nq, W * kk)
     i = I_all.permute(1, 0, 2).reshape(nq, W * kk)
     order = torch.sort(d, dim=1, descending=True, stable=True).indices[:, :k]
     return torch.gather(d, 1, order), torch.gather(i, 1, order)
+
+
+def _merge_rank_topk_chain(D_all, I_all, k):
+    """merge_rank_topk on CUDA tensors as W - 1 dependent convdr_topk_merge launches (k outputs per step: entries past
+    rank k can never re-enter).  The route of shapes the one-launch kernel does not take, and the baseline of
+    tools/merge_ab.py."""
+    W, nq, kk = D_all.shape
+    from . import _lib
+    L = _lib.lib()
+    D_all, I_all = D_all.contiguous(), I_all.contiguous()
+    Dm, Im = D_all[0], I_all[0]
+    with torch.cuda.device(D_all.device):
+        for r in range(1, W):
+            na = Dm.shape[1]
+            no = min(k, na + kk)
+            Do = torch.empty((nq, no), dtype=torch.float32, device=D_all.device)
+            Io = torch.empty((nq, no), dtype=torch.int64, device=D_all.device)
+            _lib.check(L.convdr_topk_merge(_lib.ptr(Dm), _lib.ptr(Im), na, Dm.stride(0), _lib.ptr(D_all[r]), _lib.ptr(I_all[r]),
+                                           kk, D_all[r].stride(0), nq, no, _lib.ptr(Do), _lib.ptr(Io), Do.stride(0),
+                                           _lib.stream_ptr()), "convdr_topk_merge")
+            Dm, Im = Do, Io
+    return Dm[:, :k], Im[:, :k]
 
 
 def search_sharded(index, queries, k, embid, group=None):
@@ -102,7 +132,9 @@ def search_sharded_device(index, queries, k, embid, group=None, force=False, cer
 
 def exchange_topk(D, ids, k, group=None, force=False):
     """The exchange step of the sharded search on its own (bench.py times it apart from the local search): every rank's
-    certified (scores [nq, k] fp32, record offsets [nq, k] int64) -> ONE all-gather -> device merge -> global (D, offsets)."""
+    certified (scores [nq, k] fp32, record offsets [nq, k] int64) -> ONE all-gather -> device merge -> global (D, offsets).
+    On a GPU the gathered buffer goes to convdr_topk_merge_packed as it is (one launch, no unpacking); CPU tensors (gloo) and
+    shapes outside that kernel's contract are unpacked for merge_rank_topk."""
     W = _world(group)
     if W == 1 and not (force and dist.is_initialized()):
         return D, ids
@@ -118,9 +150,108 @@ def exchange_topk(D, ids, k, group=None, force=False):
         parts = [torch.empty_like(buf) for _ in range(W)]
         dist.all_gather(parts, buf, group=group)
         out = torch.stack(parts)
+    if out.is_cuda and _merge_multi_fits(W, k, k):
+        # the merge kernel reads the wire format itself: no unpacking copies
+        from . import _lib
+        Do = torch.empty((nq, k), dtype=torch.float32, device=D.device)
+        Io = torch.empty((nq, k), dtype=torch.int64, device=D.device)
+        with torch.cuda.device(D.device):
+            _lib.check(_lib.lib().convdr_topk_merge_packed(_lib.ptr(out), W, k, nq, k, _lib.ptr(Do), _lib.ptr(Io), k,
+                                                           _lib.stream_ptr()), "convdr_topk_merge_packed")
+        return Do, Io
     D_all = out[..., 0].contiguous().view(torch.float32)
     I_all = out[..., 1:].contiguous().view(torch.int64).view(W, nq, k)
     return merge_rank_topk(D_all, I_all, k)
+
+
+def plan_block_shards(nblocks, world):
+    """Which rank searches which block file: rank r owns the CONTIGUOUS range [r * B // W, (r + 1) * B // W) -- W lists of
+    ascending block ids, disjoint, covering 0..B-1, lengths differing by at most one, empty for some ranks when W > B.
+    Contiguous and not round-robin (r, r + W, ...) on purpose: the reference's tie rule is "earlier block first", and only
+    with contiguous ownership is "lower rank first" -- the rule of the cross-rank merge -- the same thing, so the merge
+    needs no block-id key (see search_blocks_sharded)."""
+    B, W = int(nblocks), int(world)
+    if B < 0 or W < 1:
+        raise ValueError("plan_block_shards: nblocks=%d world=%d" % (B, W))
+    return [list(range(r * B // W, (r + 1) * B // W)) for r in range(W)]
+
+
+def count_blocks(ann_data_dir, max_blocks=8):
+    """Number of block files under `ann_data_dir`, found the way the reference finds them (run_convdr_inference.py:
+    159-177): the first block id in 0..max_blocks-1 whose embedding or id file is missing ends the list."""
+    import os
+    B = 0
+    while B < max_blocks and all(os.path.isfile(os.path.join(ann_data_dir, "passage__%s_p__data_obj_%d.pb" % (kind, B)))
+                                 for kind in ("emb", "embid")):
+        B += 1
+    return B
+
+
+_FAISS_PAD_SCORE = -3.4028234663852886e38     # what IndexFlatIP.search returns beside id -1 when a block has < k rows
+
+
+def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, group=None, timings=None):
+    """search.search_one_by_one over ANY number of block files with ANY number of ranks: every rank searches the blocks
+    plan_block_shards gives it, the per-rank top-topN lists are exchanged once (exchange_topk) and merged.
+    Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy, identical on every rank and equal to
+    ``search_one_by_one(...)[:, :topN]`` of one process over all blocks.  Only these topN columns are defined: the
+    reference's columns topN..2 topN are the tail of its LAST two-way merge and mean nothing across ranks (EvalDevQuery
+    reads [:, :topN] only).
+
+      blocks     counted by every rank for itself, as the reference does (count_blocks); no collective.
+      ownership  contiguous and balanced: rank r owns blocks [r * B // W, (r + 1) * B // W).  The reference's merge lets the
+                 EARLIER BLOCK win ties (`>=`, run_convdr_inference.py:218) and the cross-rank merge lets the LOWER RANK win
+                 them; with contiguous ownership the two are one rule.  With round-robin ownership (r, r + W, ...) they
+                 are not: with exact duplicates in blocks (0, 3) and (1, 2, 4) of five, round-robin at W = 2, 3, 4 returns
+                 the tied ids in another order than the one-process walk (tests/test_block_shards_cpu.py keeps that
+                 counter-example).  The blocks of one encode run differ in size by at most one record (blocks.shard_indices),
+                 so both rules balance equally well.
+      local      the pipelined loop of search_one_by_one over the owned block ids (two blocks in flight, running two-way
+                 merge cut to topN); results stay on the device.  An index without search_begin takes the host path.
+      W > B      a rank without a block contributes a list of FAISS padding (-3.4028235e38, -1) and joins the collective.
+      exchange   fp32 scores (the host path's float64 scores are widened fp32 values: narrowing is exact) and int64
+                 offsets, one all-gather, one merge launch.  World size 1: no collective.
+    timings (optional dict): this rank's search_one_by_one stage times, "exchange_s" and "block_ids".
+    topN <= FlatIPIndex.MAX_K (4096): the large-k route of the index is not part of this flow."""
+    import time
+    import numpy as np
+    from . import search as S
+    topN = int(topN)
+    if topN < 1 or topN > 4096:
+        raise ValueError("search_blocks_sharded: topN = %d is outside 1..4096 (FlatIPIndex.MAX_K); search k > 4096 with "
+                         "search_one_by_one in one process" % topN)
+    W = _world(group)
+    if W == 1:
+        tm = {}
+        D, I = S.search_one_by_one(ann_data_dir, index, queries, topN, max_blocks=max_blocks, timings=tm)
+        if timings is not None:
+            timings.update(tm, exchange_s=0.0, block_ids=list(range(count_blocks(ann_data_dir, max_blocks))))
+        return D[:, :topN], I[:, :topN]
+    B = count_blocks(ann_data_dir, max_blocks)
+    if B == 0:
+        raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
+    mine = plan_block_shards(B, W)[dist.get_rank(group)]
+    on_device = hasattr(index, "search_begin")
+    dev = torch.device(getattr(index, "device", "cpu")) if on_device else torch.device("cpu")
+    nq = int(queries.shape[0])
+    tm = {"load_add_s": 0.0, "search_finish_merge_s": 0.0, "blocks": 0, "bytes": 0}
+    merged = S._search_block_list(ann_data_dir, index, queries, topN, mine, False, tm) if mine else None
+    if merged is None:
+        D = torch.full((nq, topN), _FAISS_PAD_SCORE, dtype=torch.float32, device=dev)
+        ids = torch.full((nq, topN), -1, dtype=torch.int64, device=dev)
+    elif on_device:
+        D, ids = merged[0][:, :topN].contiguous(), merged[1][:, :topN].contiguous()
+    else:
+        D = torch.from_numpy(np.ascontiguousarray(merged[0][:, :topN]).astype(np.float32))
+        ids = torch.from_numpy(np.ascontiguousarray(merged[1][:, :topN], dtype=np.int64))
+    t0 = time.perf_counter()
+    Dm, Im = exchange_topk(D, ids, topN, group=group)
+    Dm, Im = Dm.double().cpu().numpy(), Im.cpu().numpy()
+    tm["exchange_s"] = time.perf_counter() - t0
+    tm["block_ids"] = list(mine)
+    if timings is not None:
+        timings.update(tm)
+    return Dm, Im
 
 
 def train_sampler(dataset, shuffle=True, seed=0, drop_last=False, rank=None, world=None):

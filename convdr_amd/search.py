@@ -786,6 +786,20 @@ def search_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, max_blocks
     block: 44 GB for CAsT's 14.6 GB blocks, of 288 GB) -- pass an index that is not a FlatIPIndex-with-twin, or search block
     files one at a time with index.add(BlockView) / search / reset yourself, where that does not fit.
     timings (optional dict): filled with the wall seconds spent per stage."""
+    merged = _search_block_list(ann_data_dir, gpu_index, query_embedding, topN, range(max_blocks), True, timings)
+    if merged is None:
+        raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
+    if hasattr(gpu_index, "search_begin"):
+        return merged[0].double().cpu().numpy(), merged[1].cpu().numpy()
+    return merged
+
+
+def _search_block_list(ann_data_dir, gpu_index, query_embedding, topN, block_ids, stop_at_missing, timings=None):
+    """The loop of ``search_one_by_one`` over the block files `block_ids`, in that order.  stop_at_missing: the first
+    block whose embedding or id file cannot be read ends the walk (the reference's discovery, run_convdr_inference.py:
+    159-177); otherwise (parallel.search_blocks_sharded: the ids of blocks that were found) such a block is an error.
+    Returns the running merge as it stands -- device tensors (fp32, int64) on the device path, numpy (float64, int64) on
+    the host path -- or None when no block was searched."""
     import time
     from . import blocks
     on_device = hasattr(gpu_index, "search_begin")
@@ -809,20 +823,24 @@ def search_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, max_blocks
             cand = (D, found)
             merged = cand if merged is None else merge_topk_device(merged, cand, topN)
             idx.reset()
-        for block_id in range(max_blocks):
+        for pos, block_id in enumerate(block_ids):
             emb_path, id_path = paths(block_id)
             try:
                 view = blocks.BlockView(emb_path)
             except Exception:
-                break
+                if stop_at_missing:
+                    break
+                raise
             try:
                 try:
                     ids = load_block(id_path)
                 except Exception:
-                    break
-                idx = twins[block_id & 1]
+                    if stop_at_missing:
+                        break
+                    raise
+                idx = twins[pos & 1]
                 if idx is None:
-                    idx = twins[block_id & 1] = gpu_index.twin()
+                    idx = twins[pos & 1] = gpu_index.twin()
                 t0 = time.perf_counter()
                 idx.add(view)                # the host reads; the GPU meanwhile searches the previous block
                 t1 = time.perf_counter()
@@ -842,23 +860,21 @@ def search_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, max_blocks
             tm["search_finish_merge_s"] += time.perf_counter() - t1
         if timings is not None:
             timings.update(tm)
-        if merged is None:
-            raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
-        return merged[0].double().cpu().numpy(), merged[1].cpu().numpy()
-    for block_id in range(max_blocks):
+        return merged
+    for block_id in block_ids:
         emb_path, id_path = paths(block_id)
         try:
             passage_embedding = load_block(emb_path)
             passage_embedding2id = load_block(id_path)
         except Exception:
-            break
+            if stop_at_missing:
+                break
+            raise
         gpu_index.add(passage_embedding)
         D, I = gpu_index.search(query_embedding, topN)
         cand = (D.astype(np.float64), np.asarray(passage_embedding2id)[I])
         merged = cand if merged is None else merge_topk(merged, cand, topN)
         gpu_index.reset()
-    if merged is None:
-        raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
     return merged
 
 

@@ -126,6 +126,22 @@ const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, int64_t n, i
 int convdr_topk_merge(const float* Da, const int64_t* Ia, int na, int64_t lda, const float* Db, const int64_t* Ib, int nb,
                       int64_t ldb, int nq, int n_out, float* Dout, int64_t* Iout, int64_t ldo, convdr_stream_t stream);
 
+/* W-way merge in ONE launch: the exchange step of the sharded search (every rank's top-k list of every query, all-gathered).
+ * nlists lists of n entries per query, every row sorted by score descending; writes the first n_out entries of the
+ * complete merge.  On equal scores the entry of the EARLIER list comes first and each list keeps its own order: the
+ * permutation a stable descending sort of the concatenation [list 0, ..., list nlists - 1] produces, i.e. what
+ * chaining convdr_topk_merge over lists 0 .. nlists - 1 gives.  FAISS padding (-3.4028235e38, -1) sorts like any score;
+ * NaN scores are out of contract.  Nothing but the n_out entries of each output row is written.
+ *   1 <= nlists, 0 <= n <= 4096, nlists * min(n, n_out) <= 32768, 0 <= n_out <= nlists * n, nq >= 0;
+ *   nq == 0 or n_out == 0: returns 0 without a launch; nlists == 1: a copy of the first n_out entries.
+ * convdr_topk_merge_multi  list w of query q at D / I + w * list_stride + q * ld (elements; ld >= n), ldo >= n_out.
+ * convdr_topk_merge_packed `lists` is the all-gathered exchange buffer [nlists][nq][n] of 12-byte records (score bits,
+ *                          offset low word, offset high word), as the ranks put it on the wire. */
+int convdr_topk_merge_multi(const float* D, const int64_t* I, int nlists, int n, int64_t list_stride, int64_t ld, int nq,
+                            int n_out, float* Dout, int64_t* Iout, int64_t ldo, convdr_stream_t stream);
+int convdr_topk_merge_packed(const void* lists, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout, int64_t ldo,
+                             convdr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dual-encoder forward: replaces the HuggingFace RobertaModel / BertModel forward + pooling + head
  * behind  /root/reference/model/models.py:140-148 (RobertaDot_NLL_LN.query_emb / body_emb) and
@@ -394,7 +410,7 @@ int convdr_encoder_debug_layout(const convdr_encoder_config* cfg, int64_t rows, 
  * convdr_amd/parallel.py keeps using; a torch-free host gets the same three steps here:
  *   query all-gather            convdr_comm_allgather(comm, Q_local, Q_all, nq_local * d * 4, stream)
  *   per-rank top-k all-gather   convdr_comm_allgather(comm, packed (score, offset) lists, all lists, nq * k * 12, stream)
- *                               followed by W - 1 convdr_topk_merge calls
+ *                               followed by ONE convdr_topk_merge_packed call on the gathered buffer
  *   gradient all-reduce (sum)   convdr_comm_allreduce_f32(comm, arena slice, arena slice, count, stream) behind
  *                               convdr_backward_wait_layer; 1 / W rides on convdr_grad_norm_clip(pre_scale)
  * One communicator per process and device (one process per GPU).  librccl.so is looked up at the first call (the copy
