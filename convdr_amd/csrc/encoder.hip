@@ -3,6 +3,7 @@
 // :205-211 + :227-235 (HFBertEncoder / BiEncoder.query_emb/body_emb).
 #include "gemm_launch.hpp"
 #include "gemm_ln.hpp"
+#include "cls_fold.hpp"
 
 #include "../../include/convdr_hip.h"
 
@@ -58,6 +59,8 @@ static EncBufs enc_plan(const convdr_encoder_config* c, int64_t rows, int B, cha
 static int64_t g_fused_ln_max_k = 1 << 30;
 static int64_t g_hm_blocked = 1;    // blocked activation hand-offs; convdr_set_option("hm_blocked", 0) gives the row-major paths back
 static int64_t g_fused_ln_min_rows = 128 * 192;   // below this the 128-token tiles cannot fill the 256 CUs
+static int64_t g_cls_fold = 1;      // last layer without K / V (cls_fold.hpp); convdr_set_option("cls_fold", 0): project K, V + CLS_Q attention
+static int64_t g_cls_fold_min_rows = CLS_FOLD_MIN_ROWS;   // packed rows from which the fold is taken ("cls_fold_min_rows"; tests lower it)
 
 // Y = A W^T + bias + R, X = LayerNorm(Y): fused row-complete kernel for hidden size 768 and enough rows to fill the
 // chip, else GEMM (fp32 sums) + LayerNorm kernel.  `Yf` is the fp32 scratch of the unfused path.
@@ -124,10 +127,12 @@ static int check_config(const convdr_encoder_config* c) {
 }
 
 // One transformer layer on packed rows; buffers may be shared across layers (inference).
-// cls_only (last layer): only the CLS rows of the output are live (models.py:43), so after attention the CLS rows of
-// ctx and of the layer input are gathered into compact [B, H] buffers and the output projection, LayerNorm and FFN run
-// on B rows instead of `rows`; K and V still need every token, but Q only the CLS rows (a B-row GEMM) and the attention
-// runs its CLS_Q form: saves ~10/12 of the last layer's GEMM work and half of its attention traffic.
+// cls_only (last layer): only the CLS rows of the output are live (models.py:43), so the CLS rows of ctx and of the
+// layer input are gathered into compact [B, H] buffers and the output projection, LayerNorm and FFN run on B rows
+// instead of `rows`; Q needs only the CLS rows (a B-row GEMM), and K and V are not formed at all: Wk and Wv are folded
+// through the single query (cls_fold.hpp) and the attention is one pass over the layer input.  "cls_fold" = 0, fewer
+// than "cls_fold_min_rows" packed rows (launch-bound batches: the fold's three launches and its one workgroup per
+// sequence lose there) or too few to hold the fold's buffers: K and V of every token and the attention's CLS_Q form.
 // On return: p.X holds the layer output (LayerNorm2 applied); when cls_only, p.Y[0..B) holds the pre-LayerNorm2 sums of
 // the B CLS rows instead.
 int encoder_layer_forward(const convdr_encoder_config* c, const convdr_layer_weights* w, const EncBufs& p,
@@ -160,21 +165,44 @@ int encoder_layer_forward(const convdr_encoder_config* c, const convdr_layer_wei
     }
     CONVDR_CHECK_LAUNCH("k_attention_fwd");
   } else {
-    // K and V of every token, Q of the B CLS rows only (a third of the projection and the Q / ctx traffic of the
-    // attention saved); the CLS queries land at the head of the otherwise unused Q buffer
+    // Q of the B CLS rows only; the CLS queries land at the head of the otherwise unused Q buffer
     hipLaunchKernelGGL(k_gather_cls, dim3((B + 3) / 4), dim3(256), 0, st, cu, B, H, p.X, (const float*)nullptr, p.cls_x,
                        (float*)nullptr);
     CONVDR_CHECK_LAUNCH("k_gather_cls");
-    g.W = (const bf16_t*)w->wqkv + (size_t)H * H; g.bias = w->bqkv + H; g.N = 2 * H; g.third0 = 1;
-    if (int e = launch_gemm<EPI_QKV>(g, st, "gemm_qkv")) return e;
     GemmArgs gq{};
     gq.rows = B; gq.W = (const bf16_t*)w->wqkv; gq.X = p.cls_x; gq.N = H; gq.K = H; gq.bias = w->bqkv; gq.Cb = p.Q;
     if (int e = launch_gemm<EPI_BF16>(gq, st, "gemm_qkv")) return e;
-    AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.cls_ctx, nullptr, 0.125f, nullptr};
-    ProfScope prof("attention", st);
-    if (qk_blocked) hipLaunchKernelGGL((k_attention_fwd<true, false, true>), dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
-    else hipLaunchKernelGGL(k_attention_fwd<true>, dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
-    CONVDR_CHECK_LAUNCH("k_attention_fwd<cls>");
+    // Folded form (cls_fold.hpp): with one query per (sequence, head) Wk and Wv go through that query and K, V are never
+    // formed.  U and Z ([B, heads, H] fp32 each) take the places of K and V^T, which this form leaves unused; a batch whose
+    // packed rows are too few for that (on average under H / 32 rows per sequence, and B > 5) keeps the projection.
+    const size_t fold_bytes = (size_t)B * c->heads * H * sizeof(float);
+    const bool fold = g_cls_fold != 0 && rows >= g_cls_fold_min_rows && fold_bytes <= (size_t)(rows + 128) * H * 2 && fold_bytes <= (size_t)H * p.ldt * 2;
+    if (fold) {
+      float *U = (float*)p.K, *Z = (float*)p.Vt;
+      const dim3 fgrid((unsigned)((B + FOLD_ROWS - 1) / FOLD_ROWS), (unsigned)c->heads);
+      {
+        ProfScope prof("gemm_qkv", st);
+        hipLaunchKernelGGL(k_cls_key_fold, fgrid, dim3(256), 0, st, p.Q, (const bf16_t*)w->wqkv + (size_t)H * H, B, H, 0.125f, U);
+        CONVDR_CHECK_LAUNCH("k_cls_key_fold");
+      }
+      {
+        ProfScope prof("attention", st);
+        if (int e = launch_cls_pool(p.X, U, cu, lens, B, H, Z, st)) return e;
+      }
+      ProfScope prof("gemm_qkv", st);
+      hipLaunchKernelGGL(k_cls_value_fold, fgrid, dim3(256), 0, st, Z, (const bf16_t*)w->wqkv + (size_t)2 * H * H, w->bqkv + 2 * H, B, H,
+                         p.cls_ctx);
+      CONVDR_CHECK_LAUNCH("k_cls_value_fold");
+    } else {
+      // K and V of every token (a third of the projection and the Q / ctx traffic of the attention saved)
+      g.W = (const bf16_t*)w->wqkv + (size_t)H * H; g.bias = w->bqkv + H; g.N = 2 * H; g.third0 = 1;
+      if (int e = launch_gemm<EPI_QKV>(g, st, "gemm_qkv")) return e;
+      AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.cls_ctx, nullptr, 0.125f, nullptr};
+      ProfScope prof("attention", st);
+      if (qk_blocked) hipLaunchKernelGGL((k_attention_fwd<true, false, true>), dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
+      else hipLaunchKernelGGL(k_attention_fwd<true>, dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
+      CONVDR_CHECK_LAUNCH("k_attention_fwd<cls>");
+    }
     xin = p.cls_x; ctx = p.cls_ctx; x1 = p.cls_x1; n = B;
   }
   // attention output dense + residual + LayerNorm -> X1
@@ -315,6 +343,14 @@ extern "C" int convdr_set_option(const char* name, int64_t value) {
   }
   if (strcmp(name, "hm_blocked") == 0) {   // FFN1 -> FFN2 activation layout (EPI_GELU_BLK): 1 blocked, 0 row-major
     g_hm_blocked = value;
+    return 0;
+  }
+  if (strcmp(name, "cls_fold") == 0) {   // last layer, CLS pooling: 1 Wk / Wv folded through the CLS query (cls_fold.hpp), 0 K / V projection + CLS_Q attention
+    g_cls_fold = value;
+    return 0;
+  }
+  if (strcmp(name, "cls_fold_min_rows") == 0) {   // packed rows from which "cls_fold" = 1 applies (below, the launch-bound unfolded path is faster)
+    g_cls_fold_min_rows = value;
     return 0;
   }
   if (strcmp(name, "gemm_tile_policy") == 0) {   // 0 cost model, 1 / 2 / 3 force 256 x 256 / 256 x 128 / 128 x 128 (gemm_launch.hpp)

@@ -388,7 +388,11 @@ int convdr_adamw_step_packed(float* p, const float* g, float* m, float* v, int64
 /* Tuning / test knobs: "fused_ln_min_rows" = minimum packed rows for the fused GEMM + residual + LayerNorm kernel
  * (default 24576; tests lower it to exercise that kernel on small inputs); "fused_ln_max_k" = largest contraction
  * length it is used for; "hm_blocked" = 0 / 1: row-major / blocked layout of the FFN activation between FFN1 and the
- * fused FFN2 + LayerNorm kernel (default 1; a workspace-internal choice, results are identical); "attn_bwd_fused" = 1 / 0:
+ * fused FFN2 + LayerNorm kernel (default 1; a workspace-internal choice, results are identical); "cls_fold" = 1 / 0: the last
+ * layer of the inference forward with CLS pooling folds Wk and Wv through the CLS query and reads the layer input once (K and
+ * V are never formed) / projects K and V of every token and runs the CLS-query attention (default 1; rounding-level
+ * differences; "cls_fold_min_rows" = packed rows from which the first form is taken, default 16,384: below, the second is
+ * faster; batches averaging under hidden / 32 packed rows per sequence take the second form either way); "attn_bwd_fused" = 1 / 0:
  * training backward of the attention in one workgroup per (sequence, head) for sequences of at most 256 tokens / always the
  * dQ kernel + the dK, dV kernel (default 1); "gelu_gp" = 1 / 0: gelu' evaluated in the training forward's FFN1 epilogue / the
  * pre-activation saved and a separate pass in the backward; "ip_fused_finish" = 1 / 0: one / three launches behind a scan;
