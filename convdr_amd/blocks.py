@@ -245,6 +245,37 @@ class BlockView:
         self.close()
 
 
+def key_row_stats(ann_data_dir, max_blocks=8, key_map=None):
+    """(most rows any key owns, rows in all) over the block files under `ann_data_dir`, from the small id files alone
+    (``passage__embid_p__data_obj_{b}.pb``).  Blocks are found as the search finds them (search._search_block_list): ids
+    0 .. max_blocks - 1 in order, the first one whose embedding file is missing or whose id file cannot be read ends the
+    list.  key = key_map[record offset] (e.g. offset2pid) or the record offset itself."""
+    ids = []
+    for b in range(max_blocks):
+        if not os.path.isfile(os.path.join(ann_data_dir, "passage__emb_p__data_obj_%d.pb" % b)):
+            break
+        try:
+            with open(os.path.join(ann_data_dir, "passage__embid_p__data_obj_%d.pb" % b), "rb") as h:
+                ids.append(np.asarray(pickle.load(h), dtype=np.int64).reshape(-1))
+        except Exception:
+            break
+    if not ids:
+        raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
+    keys = np.concatenate(ids)
+    if key_map is not None:
+        km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else np.asarray(key_map)
+        keys = km.astype(np.int64, copy=False)[keys]
+    if not len(keys):
+        return 1, 0
+    return int(np.unique(keys, return_counts=True)[1].max()), int(len(keys))
+
+
+def max_rows_per_key(ann_data_dir, max_blocks=8, key_map=None):
+    """The most rows any key owns in the block files (see key_row_stats): 1 for a plain corpus, the largest live-chunk
+    count of a record for MaxP blocks.  The row depth of a distinct search is topN times this."""
+    return key_row_stats(ann_data_dir, max_blocks, key_map)[0]
+
+
 class DocEmbeddingLookup:
     """Passage embeddings of the frozen teacher by passage id, straight from the corpus blocks.
 

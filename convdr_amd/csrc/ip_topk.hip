@@ -1285,6 +1285,157 @@ extern "C" int convdr_topk_merge_packed(const void* lists, int nlists, int n, in
                           ldo, (hipStream_t)stream);
 }
 
+// ---- first occurrence per key of a ranked list: the document-level cut of a row-level result -----------------------
+// The reference's `seen_pid` walk (run_convdr_inference.py:58-69) for all queries at once, one workgroup per query.
+//   stage    keys (key_map[I] or I) of the n entries into LDS; entries with I < 0 or I >= key_map_len are dropped
+//   claim    an open-addressing table of 2n..4n slots holds, per distinct key, the SMALLEST position that carries it:
+//            an element takes an empty slot with a compare-and-swap of its own position, or -- when the slot's holder
+//            has its key -- lowers the slot with atomicMin, or moves on to the next slot.  Which slot a key ends up in
+//            depends on the arrival order; the minimum it holds does not.
+//   compact  an element is kept iff its key's slot names it.  Positions are walked in chunks of THREADS, in order:
+//            ballot + popcount inside a wave, the waves' totals through LDS, a running base across chunks.
+// Nothing is ordered by an atomic's arrival: two runs write the same bytes.
+namespace convdr {
+constexpr uint32_t DISTINCT_EMPTY = 0xffffffffu;
+constexpr uint32_t DISTINCT_PAD_SCORE_BITS = 0xff7fffffu;   // -3.4028235e38, the score FAISS pads with
+
+__device__ __forceinline__ uint32_t distinct_hash(int64_t key) {   // murmur3's 64-bit finaliser
+  uint64_t x = (uint64_t)key;
+  x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+  x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+  x ^= x >> 33;
+  return (uint32_t)x;
+}
+
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_topk_distinct(const float* __restrict__ D, const int64_t* __restrict__ I, int n,
+                                                           int64_t ld, const int64_t* __restrict__ key_map, int64_t key_map_len,
+                                                           int n_out, float* __restrict__ Dout, int64_t* __restrict__ Iout,
+                                                           int64_t* __restrict__ Kout, int64_t ldo, int32_t* __restrict__ counts,
+                                                           int hbits) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int WAVES = THREADS / 64;
+  __shared__ uint32_t wave_tot[WAVES];
+  __shared__ uint32_t sh_valid, sh_oob;
+  int64_t* key = (int64_t*)smem;                              // [n]
+  uint32_t* table = (uint32_t*)(smem + (size_t)n * 8);        // [1 << hbits]
+  const uint32_t hmask = (1u << hbits) - 1u;
+  const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  D += q * ld; I += q * ld; Dout += q * ldo; Iout += q * ldo;
+  if (Kout) Kout += q * ldo;
+  auto valid_id = [&](int64_t id) { return id >= 0 && (key_map == nullptr || id < key_map_len); };
+
+  for (uint32_t h = threadIdx.x; h <= hmask; h += THREADS) table[h] = DISTINCT_EMPTY;
+  if (threadIdx.x == 0) { sh_valid = 0; sh_oob = 0; }
+  for (int i = threadIdx.x; i < n; i += THREADS) {
+    const int64_t id = I[i];
+    key[i] = valid_id(id) ? (key_map ? key_map[id] : id) : 0;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += THREADS) {
+    const int64_t id = I[i];
+    if (!valid_id(id)) continue;
+    const int64_t k = key[i];
+    uint32_t h = distinct_hash(k) & hmask;
+    for (uint32_t step = 0; step <= hmask; ++step, h = (h + 1u) & hmask) {   // ends early: the table has more slots than keys
+      const uint32_t o = atomicCAS(&table[h], DISTINCT_EMPTY, (uint32_t)i);
+      if (o == DISTINCT_EMPTY) break;
+      if (key[o] == k) { atomicMin(&table[h], (uint32_t)i); break; }
+    }
+  }
+  __syncthreads();
+  uint32_t base = 0;                                          // kept entries before this chunk (the same in every thread)
+  uint32_t wave_valid = 0;                                    // non-dropped entries of this wave's lanes
+  bool oob = false;
+  for (int i0 = 0; i0 < n; i0 += THREADS) {
+    const int i = i0 + threadIdx.x;
+    bool kept = false, valid = false;
+    int64_t id = -1, k = 0;
+    if (i < n) {
+      id = I[i];
+      valid = valid_id(id);
+      oob = oob || (id >= 0 && !valid);
+      if (valid) {
+        k = key[i];
+        uint32_t h = distinct_hash(k) & hmask, o = DISTINCT_EMPTY;
+        for (uint32_t step = 0; step <= hmask; ++step, h = (h + 1u) & hmask) {   // the key is in the table, no empty slot before it
+          o = table[h];
+          if (o == DISTINCT_EMPTY || key[o] == k) break;
+        }
+        kept = o == (uint32_t)i;
+      }
+    }
+    const uint64_t ballot = __builtin_amdgcn_ballot_w64(kept);
+    wave_valid += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(valid));
+    if (lane == 0) wave_tot[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const uint32_t t = wave_tot[w];
+      before += w < wave ? t : 0u;
+      total += t;
+    }
+    const uint32_t pos = base + before + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (kept && pos < (uint32_t)n_out) {
+      ((uint32_t*)Dout)[pos] = ((const uint32_t*)D)[i];       // score bits unchanged
+      Iout[pos] = id;
+      if (Kout) Kout[pos] = k;
+    }
+    base += total;
+    __syncthreads();                                          // wave_tot is rewritten by the next chunk
+  }
+  for (uint32_t p = base + threadIdx.x; p < (uint32_t)n_out; p += THREADS) {
+    ((uint32_t*)Dout)[p] = DISTINCT_PAD_SCORE_BITS;
+    Iout[p] = -1;
+    if (Kout) Kout[p] = -1;
+  }
+  if (lane == 0) atomicAdd(&sh_valid, wave_valid);            // (a sum of integers: the order of arrival does not show)
+  if (oob) sh_oob = 1u;                                       // (every writer writes the same value)
+  __syncthreads();
+  if (counts && threadIdx.x == 0) {
+    counts[2 * q] = sh_oob ? -1 : (int32_t)base;
+    counts[2 * q + 1] = (int32_t)sh_valid;
+  }
+}
+
+constexpr int TOPK_DISTINCT_MAX_N = 4096;
+constexpr int TOPK_DISTINCT_MAX_LDS = TOPK_DISTINCT_MAX_N * 8 + 2 * TOPK_DISTINCT_MAX_N * 4;   // keys + table: 64 KB
+
+template <int THREADS>
+static int launch_topk_distinct(const float* D, const int64_t* I, int n, int64_t ld, int nq, const int64_t* key_map,
+                                int64_t key_map_len, int n_out, float* Dout, int64_t* Iout, int64_t* Kout, int64_t ldo,
+                                int32_t* counts, hipStream_t st) {
+  static DeviceOnce attr_done;
+  if (attr_done.first())
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_topk_distinct<THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         TOPK_DISTINCT_MAX_LDS));
+  int hbits = 6;                                              // at least 2n slots (load <= 1/2), at least 64
+  while ((1 << hbits) < 2 * n) ++hbits;
+  hipLaunchKernelGGL((k_topk_distinct<THREADS>), dim3(nq), dim3(THREADS), (size_t)n * 8 + ((size_t)4 << hbits), st, D, I, n, ld,
+                     key_map, key_map_len, n_out, Dout, Iout, Kout, ldo, counts, hbits);
+  CONVDR_CHECK_LAUNCH("k_topk_distinct");
+  return 0;
+}
+}  // namespace convdr
+
+extern "C" int convdr_topk_distinct(const float* D, const int64_t* I, int n, int64_t ld, int nq, const int64_t* key_map,
+                                    int64_t key_map_len, int n_out, float* Dout, int64_t* Iout, int64_t* Kout, int64_t ldo,
+                                    int32_t* counts, convdr_stream_t stream) {
+  using namespace convdr;
+  CONVDR_REQUIRE(n >= 0 && n <= TOPK_DISTINCT_MAX_N && n_out >= 0 && n_out <= TOPK_DISTINCT_MAX_N && nq >= 0 &&
+                     key_map_len >= 0 && (key_map != nullptr || key_map_len == 0),
+                 "convdr_topk_distinct: bad sizes n=%d n_out=%d nq=%d key_map_len=%lld (n, n_out <= %d; key_map_len = 0 "
+                 "without a key_map)", n, n_out, nq, (long long)key_map_len, TOPK_DISTINCT_MAX_N);
+  CONVDR_REQUIRE(ld >= n && ldo >= n_out, "convdr_topk_distinct: pitch smaller than the row (ld=%lld n=%d, ldo=%lld n_out=%d)",
+                 (long long)ld, n, (long long)ldo, n_out);
+  if (nq == 0 || n_out == 0) return 0;
+  // 256 threads up to 1024 entries (four chunks of the ordered compaction), 1024 beyond
+  if (n <= 1024)
+    return launch_topk_distinct<256>(D, I, n, ld, nq, key_map, key_map_len, n_out, Dout, Iout, Kout, ldo, counts, (hipStream_t)stream);
+  return launch_topk_distinct<1024>(D, I, n, ld, nq, key_map, key_map_len, n_out, Dout, Iout, Kout, ldo, counts, (hipStream_t)stream);
+}
+
 extern "C" int convdr_ip_column_mean(const float* p_f32, int64_t n, int d, float* scratch /* >= 1024 * d floats */,
                                      float* mean, convdr_stream_t stream) {
   CONVDR_REQUIRE(n > 0 && d > 0, "convdr_ip_column_mean: empty block");

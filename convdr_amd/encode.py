@@ -13,6 +13,10 @@ What changed for MI355X (results are identical, embeddings do not depend on batc
   * only the real tokens of each passage are computed (the reference pads every passage to
     --max_seq_length and computes the padding);
   * no per-batch device sync: ids go up and embeddings come back through pinned buffers asynchronously.
+
+A MaxP model (``base_len``: rdot_nll_multi_chunk) encodes documents as one row per live 512-token chunk with the record
+offset repeated (_encode_shard_chunks; the reference: gen_passage_embeddings.py:116-120); search.search_distinct_one_by_one
+ranks such a block by document.
 """
 import os
 
@@ -60,6 +64,10 @@ def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_infere
     idx = blocks.shard_indices(len(cache), world, rank)
     L = cache.seq_len if max_seq_length is None else min(cache.seq_len, int(max_seq_length))
     lens_all = np.minimum(cache.lengths(idx), L).astype(np.int32) if len(idx) else np.zeros(0, np.int32)
+    base_len = None if is_query_inference else getattr(model.module if hasattr(model, "module") else model, "base_len", None)
+    if base_len:
+        return _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, int(base_len), batch_size, progress, token_budget,
+                                    model)
     out = None
     on_gpu = dev.type == "cuda"       # (the encoder itself is GPU-only; a host "device" only occurs with a stand-in tower in
     pin = (lambda t: t.pin_memory()) if on_gpu else (lambda t: t)     #  the multi-process CPU tests of the shard / file logic)
@@ -92,6 +100,58 @@ def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_infere
     if out is None:
         return np.zeros((0, 768), np.float32), idx
     return out.numpy(), idx
+
+
+def _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, base_len, batch_size, progress, token_budget, model):
+    """encode_shard for a MaxP model (``base_len``: RobertaDot_CLF_ANN_NLL_MultiChunk, models.py:159-188): one ROW PER LIVE
+    CHUNK.  A record of l tokens yields its ceil(l / base_len) chunks, chunk j = tokens [j * base_len, min(l, (j + 1) *
+    base_len)), as rows in record-major order, and embedding2id repeats the record offset for each -- what the reference's
+    loop writes for a 3-D body_emb (gen_passage_embeddings.py:116-120), with two stated departures: chunks of pure padding
+    are not emitted (the reference emits the encoder's output on all-pad input for them), and the reference's row order
+    is chunk-major per batch, so depends on the batch size.  Neither shows in a search result.
+    Chunking is index work on the staged ids; the forward is the 2-D tower call over chunk rows, and batch_size /
+    token_budget count chunk rows.  -> (embedding float32 [rows, D], embedding2id int64 [rows])"""
+    if L % base_len:
+        raise ValueError("MaxP encode: sequence length %d is not a multiple of base_len %d (the reference's reshape, "
+                         "models.py:168-171, fails there too)" % (L, base_len))
+    n_chunks = np.maximum(1, (lens_all.astype(np.int64) + base_len - 1) // base_len)
+    rec = np.repeat(np.arange(len(idx), dtype=np.int64), n_chunks)             # chunk row -> record (position in the shard)
+    first = np.concatenate([[0], np.cumsum(n_chunks)])[:-1]
+    chunk = np.arange(len(rec), dtype=np.int64) - np.repeat(first, n_chunks)      # chunk row -> chunk number j
+    clens = np.minimum(lens_all[rec].astype(np.int64) - chunk * base_len, base_len).astype(np.int32)
+    embid = idx[rec]
+    ids3 = cache.ids[:, :L].reshape(len(cache), L // base_len, base_len) if len(rec) else None   # a view: [record, chunk, token]
+    out = None
+    on_gpu = dev.type == "cuda"
+    pin = (lambda t: t.pin_memory()) if on_gpu else (lambda t: t)
+    stage = [pin(torch.empty((batch_size, base_len), dtype=torch.int32)) for _ in range(2)]
+    events = [None, None]
+    for bi, (s, e) in enumerate(plan_batches(clens, batch_size, token_budget, align=8)):
+        lens = clens[s:e]
+        n, lmax = e - s, int(lens.max())
+        buf = stage[bi & 1]
+        if events[bi & 1] is not None:
+            events[bi & 1].synchronize()                  # its previous H2D copy has been consumed
+        buf.numpy()[:n, :lmax] = ids3[embid[s:e], chunk[s:e], :lmax]
+        ids = buf[:n, :lmax].to(dev, non_blocking=True) if on_gpu else buf[:n, :lmax].clone()
+        if on_gpu:
+            ev = torch.cuda.Event()
+            ev.record()
+            events[bi & 1] = ev
+        with torch.no_grad():
+            emb = tower_call(ids, lens)
+        if out is None:
+            out = pin(torch.empty((len(rec), emb.shape[1]), dtype=torch.float32))
+        out[s:e].copy_(emb, non_blocking=True)
+        if progress:
+            progress(n)
+    if on_gpu:
+        torch.cuda.synchronize(dev)
+        from .train import check_status
+        check_status(model)
+    if out is None:
+        return np.zeros((0, 768), np.float32), embid
+    return out.numpy(), embid
 
 
 def _embed_fn(model, is_query):

@@ -254,6 +254,43 @@ def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, grou
     return Dm, Im
 
 
+def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_key=None, key_map=None, max_blocks=8, group=None,
+                                   timings=None):
+    """search.search_distinct_one_by_one over any number of ranks: per query the topN best DISTINCT keys (documents) over all
+    block files, identical on every rank and equal to the one-process result.
+    search_blocks_sharded runs at ROW depth m = topN * rows_per_key (<= 4096); the rows of one key may sit in blocks of
+    different ranks, so nothing is de-duplicated before the exchange: it stays at depth m, i.e. rows_per_key times the bytes
+    of a topN exchange (unmeasured on more than one GPU).  The merged row lists come back on the host
+    on every rank -- search_blocks_sharded's contract -- and the distinct walk (search.distinct_topk, nq x m entries) runs
+    there, on every rank alike.  rows_per_key=None: counted from the id files by every rank for itself
+    (blocks.max_rows_per_key), no collective.  An understated rows_per_key raises ConvdrError on every rank.
+    Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy."""
+    import numpy as np
+    from . import _lib, blocks
+    from . import search as S
+    topN = int(topN)
+    if rows_per_key is None:
+        rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
+    rows_per_key = int(rows_per_key)
+    m = topN * rows_per_key
+    if topN < 1 or rows_per_key < 1 or m > 4096:
+        raise ValueError("search_blocks_sharded_distinct: topN * rows_per_key = %d * %d = %d is outside 1..4096 "
+                         "(FlatIPIndex.MAX_K)" % (topN, rows_per_key, m))
+    Dm, Im = search_blocks_sharded(ann_data_dir, index, queries, m, max_blocks=max_blocks, group=group, timings=timings)
+    km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else key_map
+    D, I, _, counts = S.distinct_topk(Dm[:, :m], Im[:, :m], topN, km)
+    if (counts[:, 0] < 0).any():
+        raise _lib.ConvdrError("search_blocks_sharded_distinct: a record offset lies outside key_map (%d entries)" % len(km))
+    open_ = np.nonzero((counts[:, 0] < topN) & (counts[:, 1] >= m))[0]
+    if len(open_):
+        most, total = blocks.key_row_stats(ann_data_dir, max_blocks, key_map)
+        if total > m:
+            raise _lib.ConvdrError("search_blocks_sharded_distinct: %d queries hold fewer than %d keys in their top %d rows: "
+                                   "rows_per_key = %d is understated (the id files give %d)"
+                                   % (len(open_), topN, m, rows_per_key, most))
+    return D, I
+
+
 def train_sampler(dataset, shuffle=True, seed=0, drop_last=False, rank=None, world=None):
     """The sampler of a one-process-per-GPU training run.  The reference draws ONE RandomSampler batch per step and lets
     nn.DataParallel scatter it over the visible GPUs (run_convdr_train.py:51-57,77-78); with a process per GPU each rank

@@ -6,6 +6,9 @@ Mirrors, name for name, what the reference does with FAISS:
                                ``.add`` :180, ``.search`` :182, ``.reset`` :202
   * ``search_one_by_one``   <-> run_convdr_inference.py:157-242 (same merge rule, same output shapes)
   * ``EvalDevQuery``        <-> run_convdr_inference.py:21-113  (same .trec / .jsonl text)
+  * ``distinct_topk`` / ``FlatIPIndex.search_distinct`` / ``search_distinct_one_by_one``: the first-occurrence-per-pid walk
+                               of EvalDevQuery (:58-69) moved in front of the cut to topN, certified exact -- document-level
+                               results for blocks whose rows repeat a key (MaxP chunk rows, duplicate pids)
 All scoring / selection runs in libconvdr_hip.so (csrc/ip_topk.hip).
 """
 import json
@@ -521,6 +524,63 @@ class FlatIPIndex:
             self.stats["exhaustive_queries"] = len(bad)
         return D, I
 
+    def search_distinct(self, q, k, keys, depth=None, strict=True):
+        """Exact top-k DISTINCT keys (documents) of a block whose rows carry keys with repeats (MaxP chunk rows, duplicate
+        pids): per query the k best keys, each with its best row, in the canonical order of ``search``.
+        keys: device int64 [ntotal], the key of every row (``embid``, or ``offset2pid[embid]``).
+        The certified row search runs at depth m (``depth``, default min(MAX_K, 2k, ntotal)) and convdr_topk_distinct keeps the
+        first row per key.  A query is CERTIFIED -- its result is what the walk over ALL rows gives -- iff it found k keys, or
+        the list ran out of rows (n_valid < m), or m is the whole block: the first k distinct keys of the full order lie
+        inside any prefix that already holds k of them.  Only the uncertified queries are searched
+        again, at min(2m, MAX_K, ntotal).  A query still uncertified at the limit raises ConvdrError (strict) or keeps its
+        short, padded row (its counts tell).
+        Returns device tensors (D fp32 [nq, k], I int64 [nq, k] rows, K int64 [nq, k] keys, counts int32 [nq, 2] =
+        (n_distinct, n_valid) of the pass that produced the row); slots past a query's last key hold (-3.4028235e38, -1, -1)."""
+        import torch
+        qt = torch.as_tensor(q)
+        k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
+        if k < 1 or k > self.MAX_K:
+            raise ValueError("search_distinct: k = %d is outside 1..%d" % (k, self.MAX_K))
+        if keys.dtype != torch.int64 or keys.dim() != 1 or keys.device != self.device:
+            raise ValueError("search_distinct: keys must be an int64 vector on %s" % (self.device,))
+        keys = keys.contiguous()
+        limit = min(self.MAX_K, nt)
+        m = int(depth) if depth else min(self.MAX_K, 2 * k, nt)
+        m = max(1, min(m, self.MAX_K))
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        K = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        counts = torch.zeros((nq, 2), dtype=torch.int32, device=self.device)
+        if nq == 0:
+            return D, I, K, counts
+        qt = (qt if qt.dtype == torch.float32 else qt.float()).to(self.device)
+        todo = None                                     # indices of the queries still open (None: all)
+        self.distinct_stats = {"depths": [], "searched": []}
+        while True:
+            qs = qt if todo is None else qt[todo].contiguous()
+            Dm, Im = self.search_tensors(qs, m)
+            Dd, Id, Kd, cd = distinct_topk_device(Dm, Im, k, keys)
+            self.distinct_stats["depths"].append(m)
+            self.distinct_stats["searched"].append(int(qs.shape[0]))
+            if todo is None:
+                D, I, K, counts = Dd, Id, Kd, cd
+            else:
+                D[todo], I[todo], K[todo], counts[todo] = Dd, Id, Kd, cd
+            c = cd.cpu().numpy()                        # the one host round trip of a pass: the certificate
+            if (c[:, 0] < 0).any():
+                raise _lib.ConvdrError("search_distinct: keys has %d entries, the block %d rows" % (keys.numel(), nt))
+            open_ = np.nonzero(~((c[:, 0] >= k) | (c[:, 1] < m) | (m >= nt)))[0]
+            if not len(open_):
+                return D, I, K, counts
+            if m >= limit:
+                if strict:
+                    raise _lib.ConvdrError("search_distinct: %d queries hold fewer than %d distinct keys in their top %d rows, the "
+                                           "deepest row search (FlatIPIndex.MAX_K = %d)" % (len(open_), k, m, self.MAX_K))
+                return D, I, K, counts
+            sub = torch.as_tensor(open_, device=self.device)
+            todo = sub if todo is None else todo[sub]
+            m = min(2 * m, limit)
+
     MAX_K = 4096         # convdr_ip_search: k <= cap / 2, cap <= 8192
 
     def _search_large_k(self, q, k, q_chunk=8):
@@ -770,6 +830,114 @@ def merge_topk_device(merged, cand, topN):
                                                 Db.stride(0), nq, na + nb, _lib.ptr(Do), _lib.ptr(Io), Do.stride(0),
                                                 _lib.stream_ptr()), "convdr_topk_merge")
     return Do, Io
+
+
+PAD_SCORE = -3.4028234663852886e38      # what IndexFlatIP.search returns beside id -1
+
+
+def distinct_topk(D, I, k, key_map=None):
+    """The reference's `seen_pid` walk (run_convdr_inference.py:58-69) over ranked lists, as array operations: the numpy
+    restatement of convdr_topk_distinct (include/convdr_hip.h) for the host path.  D / I: [nq, n] scores and ids, every row a
+    ranked list; key = key_map[I] (or I).  Entries with I < 0 are dropped; an entry is kept iff no earlier one has its key.
+    Returns (D [nq, k] in D's dtype, I int64 [nq, k], K int64 [nq, k], counts int32 [nq, 2] = (n_distinct, n_valid));
+    slots past a row's last key hold (-3.4028235e38, -1, -1); n_distinct = -1 for a row with an I >= len(key_map)."""
+    D, I = np.asarray(D), np.asarray(I, dtype=np.int64)
+    nq, k = I.shape[0], int(k)
+    km = None if key_map is None else np.asarray(key_map, dtype=np.int64)
+    Do = np.full((nq, k), PAD_SCORE, D.dtype)
+    Io = np.full((nq, k), -1, np.int64)
+    Ko = np.full((nq, k), -1, np.int64)
+    counts = np.zeros((nq, 2), np.int32)
+    for j in range(nq):
+        valid = I[j] >= 0
+        oob = False
+        if km is not None:
+            over = I[j] >= len(km)
+            oob = bool((valid & over).any())
+            valid &= ~over
+        pos = np.nonzero(valid)[0]
+        ids = I[j, pos]
+        keys = ids if km is None else km[ids]
+        _, first = np.unique(keys, return_index=True)       # first occurrence of every key ...
+        first.sort()                                        # ... in rank order
+        keep = first[:k]
+        Do[j, :len(keep)] = D[j, pos[keep]]
+        Io[j, :len(keep)] = ids[keep]
+        Ko[j, :len(keep)] = keys[keep]
+        counts[j] = (-1 if oob else len(first), len(pos))
+    return Do, Io, Ko, counts
+
+
+def distinct_topk_device(D, I, k, key_map=None):
+    """``distinct_topk`` on the device (convdr_topk_distinct, one launch, no sync): D fp32 / I int64 [nq, n <= 4096] torch
+    tensors with unit column stride, key_map None or a device int64 vector.  Returns device (D, I, K [nq, k], counts [nq, 2])."""
+    import torch
+    nq, n, k = int(D.shape[0]), int(D.shape[1]), int(k)
+    assert D.dtype == torch.float32 and I.dtype == torch.int64 and D.shape == I.shape
+    if n and nq and (D.stride(1) != 1 or I.stride(1) != 1 or D.stride(0) != I.stride(0)):
+        D, I = D.contiguous(), I.contiguous()
+    if key_map is not None:
+        assert key_map.dtype == torch.int64 and key_map.dim() == 1 and key_map.device == D.device
+        key_map = key_map.contiguous()
+    Do = torch.empty((nq, k), dtype=torch.float32, device=D.device)
+    Io = torch.empty((nq, k), dtype=torch.int64, device=D.device)
+    Ko = torch.empty((nq, k), dtype=torch.int64, device=D.device)
+    counts = torch.zeros((nq, 2), dtype=torch.int32, device=D.device)
+    with torch.cuda.device(D.device):
+        _lib.check(_lib.lib().convdr_topk_distinct(_lib.ptr(D), _lib.ptr(I), n, max(int(D.stride(0)), n), nq, _lib.ptr(key_map),
+                                                   0 if key_map is None else key_map.numel(), k, _lib.ptr(Do), _lib.ptr(Io),
+                                                   _lib.ptr(Ko), k, _lib.ptr(counts), _lib.stream_ptr()), "convdr_topk_distinct")
+    return Do, Io, Ko, counts
+
+
+def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, rows_per_key=None, key_map=None, max_blocks=8,
+                               timings=None):
+    """``search_one_by_one`` at DOCUMENT level: per query the topN best distinct keys over all block files, each with the
+    score and record offset of its best row -- what the reference gets from search_one_by_one + the `seen_pid` walk of
+    EvalDevQuery (run_convdr_inference.py:58-69) only while the top-topN ROWS still hold topN documents.
+    key: the record offset itself (key_map=None: MaxP blocks, where encode.py repeats the offset for every chunk row) or
+    key_map[offset] (e.g. offset2pid, for a corpus with duplicate pids; numpy or torch int64).
+    rows_per_key: the most rows any key owns (None: counted from the id files, blocks.max_rows_per_key).  The block walk
+    runs ONCE, at row depth m = topN * rows_per_key <= FlatIPIndex.MAX_K -- deep enough for every query when rows_per_key
+    is right -- the running merge is cut to m columns and ONE distinct step (device: convdr_topk_distinct) follows.  The
+    certificate is checked: a query with fewer than topN keys in m rows of a corpus that has more rows means rows_per_key
+    was understated -> ConvdrError; the walk is never silently repeated.
+    Returns (D float64 [nq, topN], record offsets int64 [nq, topN]), the shapes EvalDevQuery reads; a corpus with fewer
+    than topN keys leaves (-3.4028235e38, -1) in the tail.  Host path (an index without search_begin): every block needs
+    at least m rows, as the reference's own id lookup does."""
+    from . import blocks
+    topN = int(topN)
+    if rows_per_key is None:
+        rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
+    rows_per_key = int(rows_per_key)
+    m = topN * rows_per_key
+    if topN < 1 or rows_per_key < 1 or m > FlatIPIndex.MAX_K:
+        raise ValueError("search_distinct_one_by_one: topN * rows_per_key = %d * %d = %d is outside 1..%d (FlatIPIndex.MAX_K)"
+                         % (topN, rows_per_key, m, FlatIPIndex.MAX_K))
+    merged = _search_block_list(ann_data_dir, gpu_index, query_embedding, m, range(max_blocks), True, timings)
+    if merged is None:
+        raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
+    if hasattr(gpu_index, "search_begin"):
+        import torch
+        Dm, Im = merged[0][:, :m], merged[1][:, :m]
+        km = key_map
+        if km is not None:
+            km = (km if torch.is_tensor(km) else torch.from_numpy(np.asarray(km, dtype=np.int64))).to(Dm.device, torch.int64)
+        D, I, _, counts = distinct_topk_device(Dm, Im, topN, km)
+        D, I, counts = D.double().cpu().numpy(), I.cpu().numpy(), counts.cpu().numpy()
+    else:
+        km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else key_map
+        D, I, _, counts = distinct_topk(merged[0][:, :m], merged[1][:, :m], topN, km)
+    if (counts[:, 0] < 0).any():
+        raise _lib.ConvdrError("search_distinct_one_by_one: a record offset lies outside key_map (%d entries)" % len(key_map))
+    open_ = np.nonzero((counts[:, 0] < topN) & (counts[:, 1] >= m))[0]
+    if len(open_):
+        most, total = blocks.key_row_stats(ann_data_dir, max_blocks, key_map)
+        if total > m:
+            raise _lib.ConvdrError("search_distinct_one_by_one: %d queries hold fewer than %d keys in their top %d rows: "
+                                   "rows_per_key = %d is understated (the id files give %d)"
+                                   % (len(open_), topN, m, rows_per_key, most))
+    return D, I
 
 
 def search_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, max_blocks=8, timings=None):

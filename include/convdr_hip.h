@@ -142,6 +142,25 @@ int convdr_topk_merge_multi(const float* D, const int64_t* I, int nlists, int n,
 int convdr_topk_merge_packed(const void* lists, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout, int64_t ldo,
                              convdr_stream_t stream);
 
+/* Document-level cut of a row-level result: the first entry per key of every query's ranked list, i.e. the `seen_pid` walk of
+ *   /root/reference/drivers/run_convdr_inference.py:58-69
+ * on the device.  D / I [nq, n] (row pitch ld) is a ranked list per query.  Per query, in position order 0 .. n - 1:
+ *   - an entry with I < 0 (FAISS padding) is dropped wherever it stands;
+ *   - key = key_map ? key_map[I] : I   (key_map: device int64 [key_map_len], e.g. offset2pid; NULL, 0: the id is the key);
+ *   - an I >= key_map_len is never dereferenced: the entry is dropped and the query's n_distinct is reported as -1;
+ *   - an entry is kept iff no earlier non-dropped entry has the same 64-bit key.
+ * The first n_out kept entries go out in their original order: Dout = score bits unchanged, Iout = the entry's own I (the best
+ * row of its key), Kout (nullable) = the key; the remaining slots of the n_out get (-3.4028235e38, -1, -1).  Nothing beyond
+ * n_out entries per row is written (row pitch ldo).  counts (nullable, int32 [nq, 2]) = (n_distinct, n_valid): ALL kept
+ * entries, before the cut to n_out, and all non-dropped entries.  With them a caller certifies a document-level top-k taken
+ * from an exact row-level top-n: it is the exhaustive answer iff n_distinct >= k, or n_valid < n, or n is the whole corpus
+ * (DESIGN.md section 4).  Bitwise repeatable; no workspace, no host synchronisation.
+ *   0 <= n <= 4096, 0 <= n_out <= 4096, ld >= n, ldo >= n_out, nq >= 0; nq == 0 or n_out == 0: returns 0 without a launch
+ *   (counts is then not written). */
+int convdr_topk_distinct(const float* D, const int64_t* I, int n, int64_t ld, int nq, const int64_t* key_map, int64_t key_map_len,
+                         int n_out, float* Dout, int64_t* Iout, int64_t* Kout, int64_t ldo, int32_t* counts,
+                         convdr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dual-encoder forward: replaces the HuggingFace RobertaModel / BertModel forward + pooling + head
  * behind  /root/reference/model/models.py:140-148 (RobertaDot_NLL_LN.query_emb / body_emb) and
