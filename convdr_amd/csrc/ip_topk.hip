@@ -1098,6 +1098,9 @@ static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) {
 
 }  // namespace convdr
 
+// k > 4096: the same cut / re-score / select through global memory (convdr_ip_search_deep*)
+#include "ip_deep.hpp"
+
 using namespace convdr;
 
 // ---- two-way merge of sorted per-query lists (run_convdr_inference.py:213-229) -------------------------------------

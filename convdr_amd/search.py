@@ -459,18 +459,26 @@ class FlatIPIndex:
         qt = (self._pad_columns(qt) if self.d != self.d_in else qt.to(self.device)).contiguous()
         assert qt.dim() == 2 and qt.shape[1] == self.d
         k = int(k)
-        if k > self.MAX_K:
-            # the reference takes any --top_n (run_convdr_inference.py:316-319); the kernel pipeline's candidate lists end at
-            # 8192 entries, so larger k takes the chunked host-side route (exact, slow): see _search_large_k
+        if k > self.DEEP_MAX_K:
+            # the reference takes any --top_n (run_convdr_inference.py:316-319); the deep kernel pipeline's candidate lists end
+            # at 131,072 entries, so larger k takes the chunked host-side route (exact, slow): see _search_large_k
             return (qt, k, None, None, None, None, None)
         x3 = self.precision in ("bf16x3", "fp16x3") or (self.precision == "auto" and getattr(self, "_x3_first", False) and self.ntotal > 0)
+        if k > self.MAX_K:
+            # 4096 < k <= 65536: the same pipeline with the lists in global memory (convdr_ip_search_deep*)
+            cap = self._deep_cap(k)
+            first = self.search_deep_device(qt, k, cap=cap, x3=x3) if self.ntotal else (None,) * 4
+            return (qt, k, x3) + tuple(first) + (cap,)
         return (qt, k, x3) + tuple(self.search_device(qt, k, x3=x3))
 
     def search_finish(self, handle):
         import torch
+        if len(handle) == 8:
+            return self._search_finish_deep(*handle)
         qt, k, x3, D, I, status, tau_retry = handle
         if x3 is None:
-            self.stats = {"retried": 0, "rounds": 0, "x3_queries": 0, "x3_first": False, "rescaled": 0, "large_k": k}
+            self.stats = {"retried": 0, "rounds": 0, "x3_queries": 0, "x3_first": False, "rescaled": 0, "large_k": k,
+                          "deep": 0, "deep_cap": 0, "chunked_queries": int(qt.shape[0])}
             return self._search_large_k(qt, k)
         nq = int(qt.shape[0])
         rescaled = 0
@@ -582,6 +590,122 @@ class FlatIPIndex:
             m = min(2 * m, limit)
 
     MAX_K = 4096         # convdr_ip_search: k <= cap / 2, cap <= 8192
+    DEEP_MAX_K = 65536   # convdr_ip_search_deep: k <= cap / 2, cap <= 131072
+    DEEP_MIN_CAP, DEEP_MAX_CAP = 16384, 131072
+    DEEP_WS_BYTES = 4 << 30      # most workspace one deep call may ask for; search_deep_device splits the queries to stay under it
+
+    def _deep_cap(self, k):
+        """Candidate capacity of the first deep pass: the largest power of two <= 4k inside the kernel's range -- between 2k
+        (the kernel's k <= cap / 2) and 4k entries per query."""
+        cap = self.DEEP_MIN_CAP
+        while 2 * cap <= 4 * k and cap < self.DEEP_MAX_CAP:
+            cap *= 2
+        return cap
+
+    def search_deep_device(self, q, k, tau_in=None, cap=None, x3=False):
+        """``search_device`` for MAX_K < k <= DEEP_MAX_K: enqueues convdr_ip_search_deep[_f16]; device (D, I, status, tau_retry)
+        with the meanings of search_device; no sync.
+        Memory bound: the deep workspace is ~ nq * cap * 28 bytes (list id + scan score, band id + fp64 score, ordered fp64
+        score) plus the threshold sample's scores (sampled rows x padded queries x 4); 1,000 queries at cap = 131,072 would be
+        3.7 GB beside the resident corpus.  The queries are therefore split so that ONE call never asks for more than
+        DEEP_WS_BYTES = 4 GiB of workspace (the calls run back to back on the stream and share the buffer)."""
+        import torch
+        L = _lib.lib()
+        cap = int(cap or self._deep_cap(k))
+        if x3:
+            self._ensure_lo()
+        nq, n = int(q.shape[0]), self.ntotal
+        if n <= cap:
+            tau_in = None               # every row is a candidate: the list is complete whatever threshold a retry proposes
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        status = torch.empty(nq, dtype=torch.int32, device=self.device)
+        tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
+        step = nq
+        while step > 1 and L.convdr_ip_deep_workspace_bytes(step, n, self.d, k, cap) > self.DEEP_WS_BYTES:
+            step = (step + 1) // 2
+        need = L.convdr_ip_deep_workspace_bytes(step, n, self.d, k, cap)
+        if not need:
+            raise _lib.ConvdrError("convdr_ip_search_deep: sizes outside the contract (nq=%d n=%d d=%d k=%d cap=%d)"
+                                   % (nq, n, self.d, k, cap))
+        ws = self._workspace(need)
+        p32 = self._p32 if n else q     # never dereferenced when n == 0
+        p16 = self._pbf if n else q
+        plo = self._plo if (x3 and n) else None
+        with torch.cuda.device(self.device):
+            for a in range(0, nq, step):
+                b = min(nq, a + step)
+                tin = None if tau_in is None else tau_in[a:b]
+                args = (b - a, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo))
+                tail = (n, self.d, k, _lib.ptr(self._max_norm), _lib.ptr(tin), cap, self.rank_target, _lib.ptr(ws), ws.numel(),
+                        _lib.ptr(D[a:b]), _lib.ptr(I[a:b]), _lib.ptr(status[a:b]), _lib.ptr(tau_retry[a:b]), _lib.stream_ptr())
+                if self.kind == "f16":
+                    _lib.check(L.convdr_ip_search_deep_f16(_lib.ptr(q[a:b]), *args, float(self._scale), *tail),
+                               "convdr_ip_search_deep_f16")
+                else:
+                    _lib.check(L.convdr_ip_search_deep(_lib.ptr(q[a:b]), *args, *tail), "convdr_ip_search_deep")
+        return D, I, status, tau_retry
+
+    def _certify_deep(self, qt, k, D, I, status, tau_retry, x3, cap):
+        """``_certify`` with the deep bounds: single-pass retries with the threshold the kernel proposes, the capacity doubled
+        on OVERFLOW up to DEEP_MAX_CAP.  Returns the indices still uncertified."""
+        import torch
+        st = status.cpu().numpy()
+        bad = np.nonzero(st != 0)[0]
+        rounds = 0
+        while len(bad) and rounds < 6:
+            rounds += 1
+            self.stats["rounds"] += 1
+            idx = torch.as_tensor(bad, device=self.device)
+            tau = tau_retry[idx].contiguous()
+            if (st[bad] == STATUS_OVERFLOW).any():
+                if cap >= self.DEEP_MAX_CAP:
+                    break
+                cap *= 2
+                self.stats["deep_cap"] = max(self.stats["deep_cap"], cap)
+            Db, Ib, sb, tb = self.search_deep_device(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3)
+            D[idx], I[idx], tau_retry[idx] = Db, Ib, tb
+            sb = sb.cpu().numpy()
+            st[bad] = sb
+            bad = bad[sb != 0]
+        return bad
+
+    def _search_finish_deep(self, qt, k, x3, D, I, status, tau_retry, cap):
+        """The ladder of search_finish for MAX_K < k <= DEEP_MAX_K: fp16 (or pinned) first pass -> rebuild on RANGE -> retries
+        with tau_retry / a doubled list -> split scan -> whatever is still open goes to _search_large_k."""
+        import torch
+        nq = int(qt.shape[0])
+        self.stats = {"retried": 0, "rounds": 1, "x3_queries": nq if x3 else 0, "x3_first": bool(x3), "rescaled": 0, "large_k": k,
+                      "deep": nq, "deep_cap": cap, "chunked_queries": 0}
+        if D is None:                   # empty index: FAISS padding
+            return (torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device),
+                    torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
+        n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()
+        if self.kind == "f16" and n_range:
+            self._rebuild_scaled()
+            self.stats["rescaled"] = 1
+            D, I, status, tau_retry = self.search_deep_device(qt, k, cap=cap, x3=x3)
+            n_bad = int((status != 0).sum().item())
+        self.stats["retried"] = int(n_bad)
+        bad = self._certify_deep(qt, k, D, I, status, tau_retry, x3, cap) if n_bad else []
+        if len(bad) and self.precision == "auto" and not x3:
+            idx = torch.as_tensor(bad, device=self.device)
+            qs = qt[idx].contiguous()
+            self.stats["x3_queries"] = len(bad)
+            Db, Ib, sb, tb = self.search_deep_device(qs, k, cap=cap, x3=True)
+            self.stats["rounds"] += 1
+            bad2 = self._certify_deep(qs, k, Db, Ib, sb, tb, True, cap) if int((sb != 0).sum().item()) else []
+            D[idx], I[idx] = Db, Ib
+            bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
+        if self.precision == "auto":
+            self._x3_first = self.stats["x3_queries"] > nq // 2
+        if len(bad):
+            idx = torch.as_tensor(np.asarray(bad, dtype=np.int64), device=self.device)
+            Db, Ib = self._search_large_k(qt[idx].contiguous(), k)
+            D[idx], I[idx] = Db, Ib
+            self.stats["chunked_queries"] = len(bad)
+            self.stats["deep"] = nq - len(bad)
+        return D, I
 
     def _search_large_k(self, q, k, q_chunk=8):
         """Exact top-k for k > MAX_K (any --top_n, run_convdr_inference.py:316-319) by chunking on the host side of the
@@ -816,13 +940,29 @@ def merge_topk(merged, cand, topN):
     return np.take_along_axis(aD, order, 1), np.take_along_axis(aI, order, 1)
 
 
+MERGE_KERNEL_MAX = 4096      # convdr_topk_merge: na, nb <= 4096
+
+
+def merge_topk_sorted(Da, Ia, Db, Ib):
+    """``merge_topk`` as torch operations on whatever device the lists live on: the stable descending sort of [A, B] --
+    ties keep A (the earlier blocks) first, each list keeps its own order.  For lists longer than convdr_topk_merge
+    takes (topN > 4096, once per block file: not a hot path)."""
+    import torch
+    aD, aI = torch.cat([Da, Db], dim=1), torch.cat([Ia, Ib], dim=1)
+    order = torch.sort(aD, dim=1, descending=True, stable=True).indices
+    return torch.gather(aD, 1, order), torch.gather(aI, 1, order)
+
+
 def merge_topk_device(merged, cand, topN):
     """``merge_topk`` on the device: (D fp32 [nq, na], I int64 [nq, na]) torch tensors in and out, same permutation
-    (convdr_topk_merge: A before B on equal scores, each list in its own order)."""
+    (convdr_topk_merge: A before B on equal scores, each list in its own order; lists longer than MERGE_KERNEL_MAX take
+    merge_topk_sorted)."""
     import torch
     Da, Ia = merged[0][:, :topN], merged[1][:, :topN]
     Db, Ib = cand[0][:, :topN], cand[1][:, :topN]
     nq, na, nb = Da.shape[0], Da.shape[1], Db.shape[1]
+    if na > MERGE_KERNEL_MAX or nb > MERGE_KERNEL_MAX:
+        return merge_topk_sorted(Da, Ia, Db, Ib)
     Do = torch.empty((nq, na + nb), dtype=torch.float32, device=Da.device)
     Io = torch.empty((nq, na + nb), dtype=torch.int64, device=Da.device)
     with torch.cuda.device(Da.device):

@@ -112,6 +112,30 @@ int convdr_ip_search_f16(const float* q_f32, int nq, const float* p_f32, const v
                          void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
                          float* tau_retry, convdr_stream_t stream);
 
+/* Deep candidate lists: convdr_ip_search[_f16] for 4,096 < k <= 65,536 (any k >= 1 is accepted).  Same arguments, same
+ * outputs, same status words and tau_retry, same certificate; the differences:
+ *   cap          a power of two in [16384, 131072], 1 <= k <= cap / 2 (so k <= 65,536); n < 2^31, d % 64 == 0, d <= 4096.
+ *   n <= cap     every row is a candidate (no threshold pass), as in the shallow call.
+ *   threshold    n > cap: from the COMPLETE scan scores of a row sample (16 evenly spaced runs of whole 256-row tiles,
+ *                >= 32,768 and <= 262,144 rows, sized so that the target rank is ~512 inside the sample); aimed at rank
+ *                rank_target of the block (0 -> cap / 2, or k + (cap - k) / 2 where cap / 2 < 1.5 k).
+ *   finish       three launches through global memory, one workgroup per query: cut (list -> band), the canonical fp64
+ *                re-score (the shallow call's kernel), select (radix select + tiled bitonic ordering of the survivors).
+ * Workspace (convdr_ip_deep_workspace_bytes; every part 256-byte aligned, nq_pad = nq rounded up to the scan's query tile,
+ * 128 or 256): the 16-bit queries and their remainders 2 x [nq_pad, d] x 2, norms / thresholds / band sizes / packed counts
+ * 4 x [nq_pad] x 4, hit counters [nq_pad] x 128, the sample's scores [rows, nq_pad] x 4 (rows: the tallest sample k allows, reserved for every n), then per query and list
+ * slot 28 bytes: list id 4 + list scan score 4 + band id 4 + band fp64 score 8 + ordered fp64 score 8 (the ordered ids
+ * reuse the list ids) = nq * cap * 28.  Arguments are validated before anything touches a device. */
+size_t convdr_ip_deep_workspace_bytes(int nq, int64_t n, int d, int k, int cap);   /* 0 for sizes outside the contract */
+int convdr_ip_search_deep(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo, int64_t n,
+                          int d, int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target,
+                          void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
+                          float* tau_retry, convdr_stream_t stream);
+int convdr_ip_search_deep_f16(const float* q_f32, int nq, const float* p_f32, const void* p_f16, const void* p_f16_lo,
+                              float p_scale, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
+                              int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
+                              int32_t* status, float* tau_retry, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
