@@ -178,6 +178,12 @@ register("convdr_topk_merge_multi", C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int6
 register("convdr_topk_merge_packed", C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int64, _p])
 register("convdr_topk_distinct", C.c_int, [_p, _p, C.c_int, C.c_int64, C.c_int, _p, C.c_int64, C.c_int, _p, _p, _p, C.c_int64, _p,
                                            _p])
+register("convdr_topk_distinct_deep_workspace_bytes", C.c_size_t, [C.c_int, C.c_int])
+register("convdr_topk_distinct_deep", C.c_int, [_p, _p, C.c_int, C.c_int64, C.c_int, _p, C.c_int64, C.c_int, _p, _p, _p, C.c_int64,
+                                                _p, _p, C.c_size_t, _p])
+register("convdr_topk_merge_deep", C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _p, _p, C.c_int64,
+                                             _p])
+register("convdr_topk_merge_deep_packed", C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int64, _p])
 register("convdr_pack_transposed", C.c_int, [_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int64), _p, _p])
 register("convdr_pack_transposed_bf16", C.c_int, [_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

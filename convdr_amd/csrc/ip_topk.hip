@@ -1439,6 +1439,9 @@ extern "C" int convdr_topk_distinct(const float* D, const int64_t* I, int n, int
   return launch_topk_distinct<1024>(D, I, n, ld, nq, key_map, key_map_len, n_out, Dout, Iout, Kout, ldo, counts, (hipStream_t)stream);
 }
 
+// lists of up to 65,536 entries: the same two contracts through global memory (convdr_topk_distinct_deep, convdr_topk_merge_deep*)
+#include "topk_deep.hpp"
+
 extern "C" int convdr_ip_column_mean(const float* p_f32, int64_t n, int d, float* scratch /* >= 1024 * d floats */,
                                      float* mean, convdr_stream_t stream) {
   CONVDR_REQUIRE(n > 0 && d > 0, "convdr_ip_column_mean: empty block");

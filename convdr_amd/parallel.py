@@ -35,8 +35,15 @@ _MERGE_MULTI_MAX_N = 4096          # convdr_topk_merge_multi / _packed: entries 
 _MERGE_MULTI_MAX_STAGED = 32768    # ... and nlists * min(n, n_out), the scores one workgroup stages in LDS (128 KB)
 
 
+MERGE_DEEP_MAX_K, MERGE_DEEP_MAX_LISTS = 65536, 64    # convdr_topk_merge_deep / _packed: lists in global memory, no staging cap
+
+
 def _merge_multi_fits(W, n, n_out):
     return 1 <= W and 0 <= n <= _MERGE_MULTI_MAX_N and W * min(n, n_out) <= _MERGE_MULTI_MAX_STAGED and 0 <= n_out <= W * n
+
+
+def _merge_deep_fits(W, n):
+    return 1 <= W <= MERGE_DEEP_MAX_LISTS and 0 <= n <= MERGE_DEEP_MAX_K
 
 
 def merge_rank_topk(D_all, I_all, k):
@@ -44,22 +51,28 @@ def merge_rank_topk(D_all, I_all, k):
     Ties keep the lower rank (= earlier block) first, then the earlier position: what chaining the reference's `>=`
     two-way merge (run_convdr_inference.py:213-229) over blocks 0..W-1 gives.  On a GPU that is ONE launch of the W-way
     merge kernel (convdr_topk_merge_multi: every element finds its own output slot) into one pair of output tensors; a
-    shape outside that kernel's contract (W * k > 32768, k > 4096) runs the chain literally with the two-way kernel
-    (`_merge_rank_topk_chain`).  CPU tensors (the gloo tests) take a stable descending sort of the rank-ordered
+    shape with k <= 4096 outside that kernel's contract (W * k > 32768) runs the chain literally with the two-way kernel
+    (`_merge_rank_topk_chain`); lists longer than 4,096 (up to 65,536, W <= 64) take ONE launch of convdr_topk_merge_deep,
+    which leaves the lists in global memory.  CPU tensors (the gloo tests) take a stable descending sort of the rank-ordered
     concatenation.  All three are the same permutation."""
     W, nq, kk = D_all.shape
     if D_all.is_cuda:
         n_out = min(k, W * kk)
-        if W == 1 or not _merge_multi_fits(W, kk, n_out):
+        deep = kk > _MERGE_MULTI_MAX_N
+        if deep and not _merge_deep_fits(W, kk):
+            raise ValueError("merge_rank_topk: %d lists of %d entries are outside convdr_topk_merge_deep (<= %d lists of <= %d)"
+                             % (W, kk, MERGE_DEEP_MAX_LISTS, MERGE_DEEP_MAX_K))
+        if not deep and (W == 1 or not _merge_multi_fits(W, kk, n_out)):
             return _merge_rank_topk_chain(D_all, I_all, k)
         from . import _lib
         L = _lib.lib()
         D_all, I_all = D_all.contiguous(), I_all.contiguous()
         Do = torch.empty((nq, n_out), dtype=torch.float32, device=D_all.device)
         Io = torch.empty((nq, n_out), dtype=torch.int64, device=D_all.device)
+        name = "convdr_topk_merge_deep" if deep else "convdr_topk_merge_multi"
         with torch.cuda.device(D_all.device):
-            _lib.check(L.convdr_topk_merge_multi(_lib.ptr(D_all), _lib.ptr(I_all), W, kk, nq * kk, kk, nq, n_out, _lib.ptr(Do),
-                                                 _lib.ptr(Io), n_out, _lib.stream_ptr()), "convdr_topk_merge_multi")
+            _lib.check(getattr(L, name)(_lib.ptr(D_all), _lib.ptr(I_all), W, kk, nq * kk, kk, nq, n_out, _lib.ptr(Do),
+                                        _lib.ptr(Io), n_out, _lib.stream_ptr()), name)
         return Do, Io
     d = D_all.permute(1, 0, 2).reshape(nq, W * kk)
     i = I_all.permute(1, 0, 2).reshape(nq, W * kk)
@@ -134,7 +147,8 @@ def exchange_topk(D, ids, k, group=None, force=False):
     """The exchange step of the sharded search on its own (bench.py times it apart from the local search): every rank's
     certified (scores [nq, k] fp32, record offsets [nq, k] int64) -> ONE all-gather -> device merge -> global (D, offsets).
     On a GPU the gathered buffer goes to convdr_topk_merge_packed as it is (one launch, no unpacking); CPU tensors (gloo) and
-    shapes outside that kernel's contract are unpacked for merge_rank_topk."""
+    shapes outside that kernel's contract are unpacked for merge_rank_topk; k > 4,096 on a GPU: convdr_topk_merge_deep_packed,
+    on the gathered buffer as it is as well."""
     W = _world(group)
     if W == 1 and not (force and dist.is_initialized()):
         return D, ids
@@ -150,14 +164,16 @@ def exchange_topk(D, ids, k, group=None, force=False):
         parts = [torch.empty_like(buf) for _ in range(W)]
         dist.all_gather(parts, buf, group=group)
         out = torch.stack(parts)
-    if out.is_cuda and _merge_multi_fits(W, k, k):
+    deep = k > _MERGE_MULTI_MAX_N and _merge_deep_fits(W, k)
+    if out.is_cuda and (deep or _merge_multi_fits(W, k, k)):
         # the merge kernel reads the wire format itself: no unpacking copies
         from . import _lib
         Do = torch.empty((nq, k), dtype=torch.float32, device=D.device)
         Io = torch.empty((nq, k), dtype=torch.int64, device=D.device)
+        name = "convdr_topk_merge_deep_packed" if deep else "convdr_topk_merge_packed"
         with torch.cuda.device(D.device):
-            _lib.check(_lib.lib().convdr_topk_merge_packed(_lib.ptr(out), W, k, nq, k, _lib.ptr(Do), _lib.ptr(Io), k,
-                                                           _lib.stream_ptr()), "convdr_topk_merge_packed")
+            _lib.check(getattr(_lib.lib(), name)(_lib.ptr(out), W, k, nq, k, _lib.ptr(Do), _lib.ptr(Io), k, _lib.stream_ptr()),
+                       name)
         return Do, Io
     D_all = out[..., 0].contiguous().view(torch.float32)
     I_all = out[..., 1:].contiguous().view(torch.int64).view(W, nq, k)
@@ -190,7 +206,7 @@ def count_blocks(ann_data_dir, max_blocks=8):
 _FAISS_PAD_SCORE = -3.4028234663852886e38     # what IndexFlatIP.search returns beside id -1 when a block has < k rows
 
 
-def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, group=None, timings=None):
+def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, group=None, timings=None, max_depth=None):
     """search.search_one_by_one over ANY number of block files with ANY number of ranks: every rank searches the blocks
     plan_block_shards gives it, the per-rank top-topN lists are exchanged once (exchange_topk) and merged.
     Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy, identical on every rank and equal to
@@ -212,14 +228,20 @@ def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, grou
       exchange   fp32 scores (the host path's float64 scores are widened fp32 values: narrowing is exact) and int64
                  offsets, one all-gather, one merge launch.  World size 1: no collective.
     timings (optional dict): this rank's search_one_by_one stage times, "exchange_s" and "block_ids".
-    topN <= FlatIPIndex.MAX_K (4096): the large-k route of the index is not part of this flow."""
+    topN <= max_depth, by default FlatIPIndex.MAX_K (4096).  max_depth up to FlatIPIndex.DEEP_MAX_K (65536) opens the deep
+    route: deep block searches, merge_topk_sorted as the running merge, convdr_topk_merge_deep_packed after the exchange."""
     import time
     import numpy as np
     from . import search as S
     topN = int(topN)
-    if topN < 1 or topN > 4096:
-        raise ValueError("search_blocks_sharded: topN = %d is outside 1..4096 (FlatIPIndex.MAX_K); search k > 4096 with "
-                         "search_one_by_one in one process" % topN)
+    if max_depth is None:
+        if topN < 1 or topN > 4096:
+            raise ValueError("search_blocks_sharded: topN = %d is outside 1..4096 (FlatIPIndex.MAX_K); search k > 4096 with "
+                             "search_one_by_one in one process" % topN)
+    else:
+        max_depth = S._check_max_depth("search_blocks_sharded", max_depth)
+        if topN < 1 or topN > max_depth:
+            raise ValueError("search_blocks_sharded: topN = %d is outside 1..%d (max_depth)" % (topN, max_depth))
     W = _world(group)
     if W == 1:
         tm = {}
@@ -255,7 +277,7 @@ def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, grou
 
 
 def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_key=None, key_map=None, max_blocks=8, group=None,
-                                   timings=None):
+                                   timings=None, max_depth=None):
     """search.search_distinct_one_by_one over any number of ranks: per query the topN best DISTINCT keys (documents) over all
     block files, identical on every rank and equal to the one-process result.
     search_blocks_sharded runs at ROW depth m = topN * rows_per_key (<= 4096); the rows of one key may sit in blocks of
@@ -264,6 +286,8 @@ def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_
     on every rank -- search_blocks_sharded's contract -- and the distinct walk (search.distinct_topk, nq x m entries) runs
     there, on every rank alike.  rows_per_key=None: counted from the id files by every rank for itself
     (blocks.max_rows_per_key), no collective.  An understated rows_per_key raises ConvdrError on every rank.
+    max_depth (default FlatIPIndex.MAX_K = 4096, at most DEEP_MAX_K = 65536) bounds m and is passed on to
+    search_blocks_sharded: TREC depth 1,000 over documents of five chunks is m = 5,000.
     Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy."""
     import numpy as np
     from . import _lib, blocks
@@ -273,10 +297,12 @@ def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_
         rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
     rows_per_key = int(rows_per_key)
     m = topN * rows_per_key
-    if topN < 1 or rows_per_key < 1 or m > 4096:
-        raise ValueError("search_blocks_sharded_distinct: topN * rows_per_key = %d * %d = %d is outside 1..4096 "
-                         "(FlatIPIndex.MAX_K)" % (topN, rows_per_key, m))
-    Dm, Im = search_blocks_sharded(ann_data_dir, index, queries, m, max_blocks=max_blocks, group=group, timings=timings)
+    limit = 4096 if max_depth is None else S._check_max_depth("search_blocks_sharded_distinct", max_depth)
+    if topN < 1 or rows_per_key < 1 or m > limit:
+        raise ValueError("search_blocks_sharded_distinct: topN * rows_per_key = %d * %d = %d is outside 1..%d "
+                         "(%s)" % (topN, rows_per_key, m, limit, "FlatIPIndex.MAX_K" if max_depth is None else "max_depth"))
+    Dm, Im = search_blocks_sharded(ann_data_dir, index, queries, m, max_blocks=max_blocks, group=group, timings=timings,
+                                   max_depth=max_depth)
     km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else key_map
     D, I, _, counts = S.distinct_topk(Dm[:, :m], Im[:, :m], topN, km)
     if (counts[:, 0] < 0).any():

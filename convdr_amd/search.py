@@ -532,7 +532,7 @@ class FlatIPIndex:
             self.stats["exhaustive_queries"] = len(bad)
         return D, I
 
-    def search_distinct(self, q, k, keys, depth=None, strict=True):
+    def search_distinct(self, q, k, keys, depth=None, strict=True, max_depth=None):
         """Exact top-k DISTINCT keys (documents) of a block whose rows carry keys with repeats (MaxP chunk rows, duplicate
         pids): per query the k best keys, each with its best row, in the canonical order of ``search``.
         keys: device int64 [ntotal], the key of every row (``embid``, or ``offset2pid[embid]``).
@@ -542,19 +542,22 @@ class FlatIPIndex:
         inside any prefix that already holds k of them.  Only the uncertified queries are searched
         again, at min(2m, MAX_K, ntotal).  A query still uncertified at the limit raises ConvdrError (strict) or keeps its
         short, padded row (its counts tell).
+        max_depth (default MAX_K, at most DEEP_MAX_K) takes MAX_K's place in all of the above -- the bound of k, of ``depth``
+        and of the doubling: beyond 4,096 rows the row search is the deep one and the cut convdr_topk_distinct_deep.
         Returns device tensors (D fp32 [nq, k], I int64 [nq, k] rows, K int64 [nq, k] keys, counts int32 [nq, 2] =
         (n_distinct, n_valid) of the pass that produced the row); slots past a query's last key hold (-3.4028235e38, -1, -1)."""
         import torch
         qt = torch.as_tensor(q)
         k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
-        if k < 1 or k > self.MAX_K:
-            raise ValueError("search_distinct: k = %d is outside 1..%d" % (k, self.MAX_K))
+        max_depth = _check_max_depth("search_distinct", max_depth)
+        if k < 1 or k > max_depth:
+            raise ValueError("search_distinct: k = %d is outside 1..%d" % (k, max_depth))
         if keys.dtype != torch.int64 or keys.dim() != 1 or keys.device != self.device:
             raise ValueError("search_distinct: keys must be an int64 vector on %s" % (self.device,))
         keys = keys.contiguous()
-        limit = min(self.MAX_K, nt)
-        m = int(depth) if depth else min(self.MAX_K, 2 * k, nt)
-        m = max(1, min(m, self.MAX_K))
+        limit = min(max_depth, nt)
+        m = int(depth) if depth else min(max_depth, 2 * k, nt)
+        m = max(1, min(m, max_depth))
         D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         K = torch.empty((nq, k), dtype=torch.int64, device=self.device)
@@ -583,7 +586,9 @@ class FlatIPIndex:
             if m >= limit:
                 if strict:
                     raise _lib.ConvdrError("search_distinct: %d queries hold fewer than %d distinct keys in their top %d rows, the "
-                                           "deepest row search (FlatIPIndex.MAX_K = %d)" % (len(open_), k, m, self.MAX_K))
+                                           "deepest row search (%s = %d)"
+                                           % (len(open_), k, m, "FlatIPIndex.MAX_K" if max_depth == self.MAX_K else "max_depth",
+                                              max_depth))
                 return D, I, K, counts
             sub = torch.as_tensor(open_, device=self.device)
             todo = sub if todo is None else todo[sub]
@@ -1008,9 +1013,16 @@ def distinct_topk(D, I, k, key_map=None):
     return Do, Io, Ko, counts
 
 
+DISTINCT_KERNEL_MAX = 4096   # convdr_topk_distinct: n, n_out <= 4096 (keys and table in LDS)
+DISTINCT_DEEP_WS_BYTES = None   # most workspace one convdr_topk_distinct_deep call may ask for (None: FlatIPIndex.DEEP_WS_BYTES)
+
+
 def distinct_topk_device(D, I, k, key_map=None):
-    """``distinct_topk`` on the device (convdr_topk_distinct, one launch, no sync): D fp32 / I int64 [nq, n <= 4096] torch
-    tensors with unit column stride, key_map None or a device int64 vector.  Returns device (D, I, K [nq, k], counts [nq, 2])."""
+    """``distinct_topk`` on the device, no sync: D fp32 / I int64 [nq, n <= 65536] torch tensors with unit column stride,
+    key_map None or a device int64 vector.  Returns device (D, I, K [nq, k], counts [nq, 2]).
+    n, k <= 4096: convdr_topk_distinct, one launch.  Beyond: convdr_topk_distinct_deep, whose keys and table live in a
+    workspace allocated per call (n * 8 + at most 4n * 4 bytes per query: 1 MB at n = 65,536); the queries are split so that
+    one call never asks for more than FlatIPIndex.DEEP_WS_BYTES (the calls run back to back on the stream and share it)."""
     import torch
     nq, n, k = int(D.shape[0]), int(D.shape[1]), int(k)
     assert D.dtype == torch.float32 and I.dtype == torch.int64 and D.shape == I.shape
@@ -1023,15 +1035,43 @@ def distinct_topk_device(D, I, k, key_map=None):
     Io = torch.empty((nq, k), dtype=torch.int64, device=D.device)
     Ko = torch.empty((nq, k), dtype=torch.int64, device=D.device)
     counts = torch.zeros((nq, 2), dtype=torch.int32, device=D.device)
+    L = _lib.lib()
+    ld, kml = max(int(D.stride(0)), n), 0 if key_map is None else key_map.numel()
     with torch.cuda.device(D.device):
-        _lib.check(_lib.lib().convdr_topk_distinct(_lib.ptr(D), _lib.ptr(I), n, max(int(D.stride(0)), n), nq, _lib.ptr(key_map),
-                                                   0 if key_map is None else key_map.numel(), k, _lib.ptr(Do), _lib.ptr(Io),
-                                                   _lib.ptr(Ko), k, _lib.ptr(counts), _lib.stream_ptr()), "convdr_topk_distinct")
+        if n <= DISTINCT_KERNEL_MAX and k <= DISTINCT_KERNEL_MAX:
+            _lib.check(L.convdr_topk_distinct(_lib.ptr(D), _lib.ptr(I), n, ld, nq, _lib.ptr(key_map), kml, k, _lib.ptr(Do),
+                                              _lib.ptr(Io), _lib.ptr(Ko), k, _lib.ptr(counts), _lib.stream_ptr()),
+                       "convdr_topk_distinct")
+            return Do, Io, Ko, counts
+        budget = FlatIPIndex.DEEP_WS_BYTES if DISTINCT_DEEP_WS_BYTES is None else int(DISTINCT_DEEP_WS_BYTES)
+        step = max(nq, 1)
+        while step > 1 and L.convdr_topk_distinct_deep_workspace_bytes(step, n) > budget:
+            step = (step + 1) // 2
+        need = L.convdr_topk_distinct_deep_workspace_bytes(step, n)
+        if n > FlatIPIndex.DEEP_MAX_K or k > FlatIPIndex.DEEP_MAX_K or not need:
+            raise _lib.ConvdrError("convdr_topk_distinct_deep: sizes outside the contract (nq=%d n=%d n_out=%d)" % (nq, n, k))
+        ws = torch.empty(need, dtype=torch.uint8, device=D.device)
+        for a in range(0, nq, step):
+            b = min(nq, a + step)
+            _lib.check(L.convdr_topk_distinct_deep(_lib.ptr(D[a:b]), _lib.ptr(I[a:b]), n, ld, b - a, _lib.ptr(key_map), kml, k,
+                                                   _lib.ptr(Do[a:b]), _lib.ptr(Io[a:b]), _lib.ptr(Ko[a:b]), k,
+                                                   _lib.ptr(counts[a:b]), _lib.ptr(ws), need, _lib.stream_ptr()),
+                       "convdr_topk_distinct_deep")
     return Do, Io, Ko, counts
 
 
+def _check_max_depth(who, max_depth):
+    """The row depth a distinct / sharded search may reach: FlatIPIndex.MAX_K unless the caller asks for more."""
+    if max_depth is None:
+        return FlatIPIndex.MAX_K
+    md = int(max_depth)
+    if md < 1 or md > FlatIPIndex.DEEP_MAX_K:
+        raise ValueError("%s: max_depth = %d is outside 1..%d (FlatIPIndex.DEEP_MAX_K)" % (who, md, FlatIPIndex.DEEP_MAX_K))
+    return md
+
+
 def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, rows_per_key=None, key_map=None, max_blocks=8,
-                               timings=None):
+                               timings=None, max_depth=None):
     """``search_one_by_one`` at DOCUMENT level: per query the topN best distinct keys over all block files, each with the
     score and record offset of its best row -- what the reference gets from search_one_by_one + the `seen_pid` walk of
     EvalDevQuery (run_convdr_inference.py:58-69) only while the top-topN ROWS still hold topN documents.
@@ -1044,16 +1084,20 @@ def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, r
     was understated -> ConvdrError; the walk is never silently repeated.
     Returns (D float64 [nq, topN], record offsets int64 [nq, topN]), the shapes EvalDevQuery reads; a corpus with fewer
     than topN keys leaves (-3.4028235e38, -1) in the tail.  Host path (an index without search_begin): every block needs
-    at least m rows, as the reference's own id lookup does."""
+    at least m rows, as the reference's own id lookup does.
+    max_depth (default FlatIPIndex.MAX_K, at most DEEP_MAX_K): the bound of m.  Beyond 4,096 the block searches are the deep
+    ones, the running merge is merge_topk_sorted and the distinct step convdr_topk_distinct_deep."""
     from . import blocks
+    max_depth = _check_max_depth("search_distinct_one_by_one", max_depth)
     topN = int(topN)
     if rows_per_key is None:
         rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
     rows_per_key = int(rows_per_key)
     m = topN * rows_per_key
-    if topN < 1 or rows_per_key < 1 or m > FlatIPIndex.MAX_K:
-        raise ValueError("search_distinct_one_by_one: topN * rows_per_key = %d * %d = %d is outside 1..%d (FlatIPIndex.MAX_K)"
-                         % (topN, rows_per_key, m, FlatIPIndex.MAX_K))
+    if topN < 1 or rows_per_key < 1 or m > max_depth:
+        raise ValueError("search_distinct_one_by_one: topN * rows_per_key = %d * %d = %d is outside 1..%d (%s)"
+                         % (topN, rows_per_key, m, max_depth,
+                            "FlatIPIndex.MAX_K" if max_depth == FlatIPIndex.MAX_K else "max_depth"))
     merged = _search_block_list(ann_data_dir, gpu_index, query_embedding, m, range(max_blocks), True, timings)
     if merged is None:
         raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)

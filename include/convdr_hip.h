@@ -185,6 +185,37 @@ int convdr_topk_distinct(const float* D, const int64_t* I, int n, int64_t ld, in
                          int n_out, float* Dout, int64_t* Iout, int64_t* Kout, int64_t ldo, int32_t* counts,
                          convdr_stream_t stream);
 
+/* Deep lists: the two list kernels above for lists of up to 65,536 entries, what a row search beyond k = 4,096
+ * (convdr_ip_search_deep) hands on.  Same contracts, same bytes wherever the shallow entry accepts the shape; the lists stay
+ * in global memory.  Arguments are validated before anything touches a device.
+ *
+ * convdr_topk_distinct_deep   convdr_topk_distinct, word for word: padding ids dropped, key_map / key_map_len, n_distinct = -1
+ *   for an id >= key_map_len, an entry kept iff it is the first of its 64-bit key, score bits / I / K out with the
+ *   (-3.4028235e38, -1, -1) tail, counts = (n_distinct, n_valid), nothing past n_out written, bitwise repeatable, no host
+ *   synchronisation.  0 <= n <= 65536, 0 <= n_out <= 65536, ld >= n, ldo >= n_out, nq >= 0, Kout and counts nullable;
+ *   nq == 0 or n_out == 0: returns 0 without a launch (counts is then not written).  One 1,024-thread workgroup per query.
+ *   workspace (device, workspace_bytes >= convdr_topk_distinct_deep_workspace_bytes(nq, n)): the staged keys int64 [nq][n],
+ *   rounded up to 256 bytes, then the open-addressing tables uint32 [nq][2^hbits], 2^hbits the smallest power of two >= 2n
+ *   and >= 64 -- at most 512 KB + 512 KB per query.  The kernel initialises what it reads: no result depends on what the
+ *   workspace or the outputs held before.
+ * convdr_topk_distinct_deep_workspace_bytes   0 for sizes outside the contract (nq < 0, n < 0, n > 65536).
+ *
+ * convdr_topk_merge_deep / convdr_topk_merge_deep_packed   convdr_topk_merge_multi / convdr_topk_merge_packed with the same
+ *   arguments (plain pitches / the [nlists][nq][n] 12-byte records of the exchange, read in place) and the same permutation:
+ *   the stable descending sort of [list 0, ..., list nlists - 1], earlier lists first on equal scores, FAISS padding sorted
+ *   like a score, NaN out of contract.  Nothing but the n_out entries of each output row is written; no workspace.
+ *   1 <= nlists <= 64, 0 <= n <= 65536, 0 <= n_out <= nlists * n, nlists * min(n, n_out) < 2^31, nq >= 0, ld >= n,
+ *   ldo >= n_out, list_stride >= n where nlists > 1; nq == 0 or n_out == 0: returns 0 without a launch.  A query's
+ *   nlists * min(n, n_out) elements are cut into chunks of 1,024 over grid.y (at most 4,096 chunks), queries on grid.x. */
+size_t convdr_topk_distinct_deep_workspace_bytes(int nq, int n);
+int convdr_topk_distinct_deep(const float* D, const int64_t* I, int n, int64_t ld, int nq, const int64_t* key_map,
+                              int64_t key_map_len, int n_out, float* Dout, int64_t* Iout, int64_t* Kout, int64_t ldo,
+                              int32_t* counts, void* workspace, size_t workspace_bytes, convdr_stream_t stream);
+int convdr_topk_merge_deep(const float* D, const int64_t* I, int nlists, int n, int64_t list_stride, int64_t ld, int nq,
+                           int n_out, float* Dout, int64_t* Iout, int64_t ldo, convdr_stream_t stream);
+int convdr_topk_merge_deep_packed(const void* lists, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout,
+                                  int64_t ldo, convdr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dual-encoder forward: replaces the HuggingFace RobertaModel / BertModel forward + pooling + head
  * behind  /root/reference/model/models.py:140-148 (RobertaDot_NLL_LN.query_emb / body_emb) and
