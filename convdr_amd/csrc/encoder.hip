@@ -249,24 +249,13 @@ extern "C" int convdr_cast_f32_bf16(const float* x, void* y, int64_t n, convdr_s
   return 0;
 }
 
-extern "C" int convdr_encoder_forward(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
-                                      const void* input_ids, int ids_are_int32, const int64_t* attention_mask, int B, int L,
-                                      const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int max_len,
-                                      void* workspace, size_t workspace_bytes, float* out, convdr_stream_t stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int e = check_config(cfg)) return e;
-  CONVDR_REQUIRE(B > 0 && L > 0 && rows > 0 && rows % 8 == 0 && max_len > 0 && max_len <= L,
-                 "convdr_encoder_forward: bad sizes B=%d L=%d rows=%lld max_len=%d", B, L, (long long)rows, max_len);
-  const EncBufs p = enc_plan(cfg, rows, B, (char*)workspace);
-  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_encoder_forward: workspace too small (%zu < %zu)", workspace_bytes,
-                 p.total);
+namespace convdr {
+// Everything behind the packing kernel: tok_id / tok_pos of the workspace -> out.  Shared by the padded and the ragged entry,
+// which therefore issue the same launches for the same sequences, cu and B.
+static int encoder_forward_packed(const convdr_encoder_config* cfg, const convdr_encoder_weights* w, const EncBufs& p,
+                                  const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int B, int max_len,
+                                  float* out, hipStream_t st) {
   const int H = cfg->hidden;
-  // V^T columns past the last row are read (never used) by the last key tile: keep them finite
-  CONVDR_CHECK_HIP(hipMemset2DAsync(p.Vt + rows, p.ldt * 2, 0, (p.ldt - rows) * 2, H, st));
-  CONVDR_CHECK_HIP(hipMemsetAsync(p.status, 0, 256, st));
-  hipLaunchKernelGGL(k_seq_pack, dim3((B + 3) / 4), dim3(256), 0, st, input_ids, ids_are_int32, attention_mask, seq_lens, B, L, cu_seqlens,
-                     cfg->kind, cfg->pad_idx, cfg->max_pos, cfg->vocab, p.tok_id, p.tok_pos, p.status);
-  CONVDR_CHECK_LAUNCH("k_seq_pack");
   {
     ProfScope prof("embed_ln", st);
     hipLaunchKernelGGL(k_embed_ln, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, p.tok_id, p.tok_pos, rows, H,
@@ -301,6 +290,54 @@ extern "C" int convdr_encoder_forward(const convdr_encoder_config* cfg, const co
     CONVDR_CHECK_LAUNCH("k_layernorm(head)");
   }
   return 0;
+}
+}  // namespace convdr
+
+extern "C" int convdr_encoder_forward(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
+                                      const void* input_ids, int ids_are_int32, const int64_t* attention_mask, int B, int L,
+                                      const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int max_len,
+                                      void* workspace, size_t workspace_bytes, float* out, convdr_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = check_config(cfg)) return e;
+  CONVDR_REQUIRE(B > 0 && L > 0 && rows > 0 && rows % 8 == 0 && max_len > 0 && max_len <= L,
+                 "convdr_encoder_forward: bad sizes B=%d L=%d rows=%lld max_len=%d", B, L, (long long)rows, max_len);
+  const EncBufs p = enc_plan(cfg, rows, B, (char*)workspace);
+  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_encoder_forward: workspace too small (%zu < %zu)", workspace_bytes,
+                 p.total);
+  const int H = cfg->hidden;
+  // V^T columns past the last row are read (never used) by the last key tile: keep them finite
+  CONVDR_CHECK_HIP(hipMemset2DAsync(p.Vt + rows, p.ldt * 2, 0, (p.ldt - rows) * 2, H, st));
+  CONVDR_CHECK_HIP(hipMemsetAsync(p.status, 0, 256, st));
+  hipLaunchKernelGGL(k_seq_pack, dim3((B + 3) / 4), dim3(256), 0, st, input_ids, ids_are_int32, attention_mask, seq_lens, B, L, cu_seqlens,
+                     cfg->kind, cfg->pad_idx, cfg->max_pos, cfg->vocab, p.tok_id, p.tok_pos, p.status);
+  CONVDR_CHECK_LAUNCH("k_seq_pack");
+  return encoder_forward_packed(cfg, w, p, cu_seqlens, seq_lens, rows, B, max_len, out, st);
+}
+
+// The same forward for ragged input: a flat stream of the unmasked tokens plus offsets instead of a padded [B, L] matrix and
+// its mask (k_seq_pack_ragged); from the embedding kernel on it is the code above.
+extern "C" int convdr_encoder_forward_ragged(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
+                                             const int32_t* tokens, int64_t n_tokens, const int32_t* tok_offsets, int B,
+                                             const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int max_len,
+                                             void* workspace, size_t workspace_bytes, float* out, convdr_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = check_config(cfg)) return e;
+  CONVDR_REQUIRE(B > 0 && n_tokens >= B && n_tokens <= INT32_MAX && rows > 0 && rows % 8 == 0 && rows >= n_tokens && max_len > 0 &&
+                     max_len <= n_tokens,
+                 "convdr_encoder_forward_ragged: bad sizes B=%d n_tokens=%lld rows=%lld max_len=%d", B, (long long)n_tokens,
+                 (long long)rows, max_len);
+  CONVDR_REQUIRE(tokens != nullptr && tok_offsets != nullptr, "convdr_encoder_forward_ragged: null tokens / tok_offsets");
+  const EncBufs p = enc_plan(cfg, rows, B, (char*)workspace);
+  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_encoder_forward_ragged: workspace too small (%zu < %zu)", workspace_bytes,
+                 p.total);
+  const int H = cfg->hidden;
+  // V^T columns past the last row are read (never used) by the last key tile: keep them finite
+  CONVDR_CHECK_HIP(hipMemset2DAsync(p.Vt + rows, p.ldt * 2, 0, (p.ldt - rows) * 2, H, st));
+  CONVDR_CHECK_HIP(hipMemsetAsync(p.status, 0, 256, st));
+  hipLaunchKernelGGL(k_seq_pack_ragged, dim3((B + 3) / 4), dim3(256), 0, st, tokens, n_tokens, tok_offsets, seq_lens, B, cu_seqlens,
+                     cfg->kind, cfg->pad_idx, cfg->max_pos, cfg->vocab, p.tok_id, p.tok_pos, p.status);
+  CONVDR_CHECK_LAUNCH("k_seq_pack_ragged");
+  return encoder_forward_packed(cfg, w, p, cu_seqlens, seq_lens, rows, B, max_len, out, st);
 }
 
 // Debug / test aid: byte offsets of the activation buffers inside the workspace, in the order

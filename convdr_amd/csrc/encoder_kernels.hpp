@@ -84,6 +84,64 @@ static __global__ void __launch_bounds__(256) k_seq_pack(const void* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// pack, ragged input: one wave per sequence.  tokens[off[b] .. off[b+1]) are the UNMASKED tokens of sequence b, back to
+// back with no padding between sequences; they go to rows cu[b].., and tok_id / tok_pos / status get exactly what k_seq_pack
+// writes for the same sequences stored right-padded in a [B, L] matrix.
+// Why the flat stream is enough: the reference's RoBERTa position of token l is
+//   cumsum(ids[0..l] != pad_idx) * (ids[l] != pad_idx) + pad_idx   over the padded row,
+// which depends only on the ids at or before l; under a prefix (right-padding) mask every one of those is a kept token, so
+// the padding behind the sequence never enters a kept token's position.  (BERT: the index inside the sequence.)  A mask with
+// holes has masked ids BEFORE kept ones, is not representable as a stream, and stays with k_seq_pack.
+// Hardening: the offsets come from the caller.  A sequence is read only if 0 <= off[b] <= off[b+1] <= n_tokens,
+// off[b+1] - off[b] == lens[b] and 1 <= lens[b] <= cu[b+1] - cu[b]; otherwise it is flagged CONVDR_ENC_STATUS_BAD_LENS, nothing
+// of `tokens` is read for it and all its rows get id -1 / position 0.  So no read goes past tokens + n_tokens.
+// ---------------------------------------------------------------------------------------------
+static __global__ void __launch_bounds__(256) k_seq_pack_ragged(const int32_t* __restrict__ tokens, int64_t n_tokens,
+                                                         const int32_t* __restrict__ off, const int32_t* __restrict__ lens,
+                                                         int B, const int32_t* __restrict__ cu, int kind, int pad_idx,
+                                                         int max_pos, int vocab, int32_t* __restrict__ tok_id,
+                                                         int32_t* __restrict__ tok_pos, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int base = cu[b], end = cu[b + 1];
+  const int64_t o0 = off[b], o1 = off[b + 1];
+  const int len_b = lens[b];
+  const bool ok = o0 >= 0 && o0 <= o1 && o1 <= n_tokens && o1 - o0 == (int64_t)len_b && len_b >= 1 &&
+                  (int64_t)len_b <= (int64_t)end - (int64_t)base;
+  const int n = ok ? len_b : 0;
+  int kept = 0, nonpad = 0;
+  int flags = ok ? 0 : CONVDR_ENC_STATUS_BAD_LENS;
+  for (int l0 = 0; l0 < n; l0 += 64) {
+    const int l = l0 + lane;
+    const bool m = l < n;
+    int id = m ? tokens[o0 + l] : pad_idx;
+    const bool np = m && id != pad_idx;
+    const unsigned long long bm = __ballot(m), bnp = __ballot(np);
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    if (m) {
+      if (id < 0 || id >= vocab) { flags |= CONVDR_ENC_STATUS_BAD_TOKEN; id = 0; }   // clamped + flagged, as in k_seq_pack
+      const int row = base + kept + __popcll(bm & lt);
+      int p = kind == 0 ? (np ? nonpad + __popcll(bnp & (lt | (1ull << lane))) + pad_idx : pad_idx) : l;
+      p = p < max_pos ? p : max_pos - 1;
+      tok_id[row] = id;
+      tok_pos[row] = p;
+    }
+    kept += __popcll(bm);
+    nonpad += __popcll(bnp);
+  }
+  if (__ballot(flags != 0) != 0ull) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) flags |= __shfl_xor(flags, o, 64);
+    if (lane == 0) atomicOr(status, flags);
+  }
+  for (int r = base + kept + lane; r < end; r += 64) {
+    tok_id[r] = -1;
+    tok_pos[r] = 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // LayerNorm helpers: one wave per row, H <= 1024, H % 4 == 0; lane owns elements 256 j + 4 lane + c.
 // Biased variance, eps inside the sqrt (torch.nn.LayerNorm).
 // ---------------------------------------------------------------------------------------------

@@ -397,6 +397,48 @@ class EncoderTower(nn.Module):
             _status_post(self, self._ws)
         return out
 
+    def embed_ragged(self, tokens, seq_lens, head=None):
+        """The same embeddings from RAGGED input (convdr_encoder_forward_ragged): `tokens` is a CUDA int32 1-D tensor, the
+        unmasked tokens of all sequences back to back with no padding; `seq_lens` a host int array of their lengths.  What a
+        right-padded batch with a prefix mask holds -- so sequences that arrived in batches of different widths run in one
+        forward without re-padding -- and, for the same sequences, bit-identical to ``embed``.  No device -> host round trip."""
+        L_ = _lib.lib()
+        if tokens.device.type != "cuda":
+            raise _lib.ConvdrError("encoder inputs must be CUDA tensors (no CPU fallback)")
+        if tokens.dtype != torch.int32 or tokens.dim() != 1:
+            raise ValueError("embed_ragged needs a 1-D int32 token stream (got %s, %d-D)" % (tokens.dtype, tokens.dim()))
+        tokens = tokens.contiguous()
+        lens_host = np.ascontiguousarray(np.asarray(seq_lens, dtype=np.int32)).reshape(-1)
+        B, dev = len(lens_host), tokens.device
+        if B == 0 or lens_host.min() < 1:
+            raise ValueError("every sequence needs at least one unmasked token")
+        if int(lens_host.sum(dtype=np.int64)) != tokens.numel():
+            raise ValueError("seq_lens sum to %d, the token stream holds %d" % (int(lens_host.sum(dtype=np.int64)), tokens.numel()))
+        from ..train import _pinned_upload, _status_poll, _status_post
+        _status_poll(self)          # (a batch flagged by an earlier forward raises here at the latest)
+        self.check_positions(int(lens_host.max()))
+        # tok_offsets [B+1] | cu [B+1] | lens [B]: one upload
+        meta = np.zeros(3 * B + 2, np.int32)
+        np.cumsum(lens_host, out=meta[1:B + 1])
+        np.cumsum((lens_host + 7) // 8 * 8, out=meta[B + 2:2 * B + 2])
+        meta[2 * B + 2:] = lens_host
+        rows, max_len = int(meta[2 * B + 1]), int(lens_host.max())
+        meta_d = _pinned_upload(meta, dev)
+        off, cu, lens = meta_d[:B + 1], meta_d[B + 1:2 * B + 2], meta_d[2 * B + 2:]
+        with torch.cuda.device(dev):
+            c, w, _keep = self.packed(head)
+            self._ensure_kslice(c, w, _keep, rows, dev)
+            out = torch.empty((B, c.out_dim or c.hidden), dtype=torch.float32, device=dev)
+            need = L_.convdr_encoder_workspace_bytes(C.byref(c), rows, B)
+            if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+                self._ws = torch.empty(int(need * 1.25), dtype=torch.uint8, device=dev)
+            _lib.check(L_.convdr_encoder_forward_ragged(C.byref(c), C.byref(w), _lib.ptr(tokens), tokens.numel(), _lib.ptr(off), B,
+                                                        _lib.ptr(cu), _lib.ptr(lens), rows, max_len, _lib.ptr(self._ws),
+                                                        self._ws.numel(), _lib.ptr(out), _lib.stream_ptr()),
+                       "convdr_encoder_forward_ragged")
+            _status_post(self, self._ws)
+        return out
+
 
 # --------------------------------------------------------------------------------------------
 # checkpoint I/O shared by the model classes (HF directory layout: config.json + pytorch_model.bin)
@@ -539,6 +581,16 @@ class RobertaDot_NLL_LN(NLL, _PretrainedMixin, nn.Module):
     def body_emb(self, input_ids, attention_mask, seq_lens=None):
         return self.query_emb(input_ids, attention_mask, seq_lens)
 
+    def query_emb_ragged(self, tokens, seq_lens):
+        """query_emb for ragged input (extension, EncoderTower.embed_ragged): a flat CUDA int32 stream of the unmasked tokens
+        and the host lengths.  Inference only: there is no ragged training path."""
+        if bool(self.use_mean) != bool(getattr(self.roberta, "pool_mean", False)):
+            self.roberta.pool_mean = bool(self.use_mean)
+            self.roberta.invalidate_packed()
+        if _wants_autograd(self):
+            raise _lib.ConvdrError("query_emb_ragged has no training path: call it in eval() mode or under torch.no_grad()")
+        return self.roberta.embed_ragged(tokens, seq_lens, head=(self.embeddingHead, self.norm))
+
     def resize_token_embeddings(self, new_num_tokens):
         """run_convdr_train.py:474: grow the word-embedding table, new rows N(0, 0.02) like HF's _init_weights."""
         old = self.roberta.embeddings.word_embeddings
@@ -653,6 +705,13 @@ class BiEncoder(nn.Module):
 
     def body_emb(self, input_ids, attention_mask):
         return self.ctx_model(input_ids, attention_mask)[1]
+
+    def query_emb_ragged(self, tokens, seq_lens):
+        """query_emb for ragged input (extension, EncoderTower.embed_ragged); inference only.  The lengths come from the
+        host, so unlike ``query_emb`` this costs no device -> host round trip."""
+        if _wants_autograd(self.question_model):
+            raise _lib.ConvdrError("query_emb_ragged has no training path: call it in eval() mode or under torch.no_grad()")
+        return self.question_model.embed_ragged(tokens, seq_lens)
 
     def forward(self, query_ids, attention_mask_q, input_ids_a=None, attention_mask_a=None, input_ids_b=None,
                 attention_mask_b=None, is_query=True):

@@ -283,11 +283,30 @@ size_t convdr_encoder_workspace_bytes(const convdr_encoder_config* cfg, int64_t 
  * data/tokenizing.py:138-140).  Only mask == 1 tokens are computed ("packed rows"):
  * cu_seqlens (device int32 [B+1]) gives each sequence's first row, multiples of 8, cu[B] == rows;
  * seq_lens (device int32 [B]) = mask.sum(1) >= 1; mask[b, 0] must be 1 (the CLS position).  max_len = max(seq_lens).
+ * max_len sizes the attention grid and is a host value the library cannot check against the device array: it must be
+ * >= max(seq_lens) (a smaller one leaves the query rows past it without attention output; a larger one only costs idle
+ * workgroups).
  * out: device fp32 [B, out_dim or hidden]. */
 int convdr_encoder_forward(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
                            const void* input_ids, int ids_are_int32, const int64_t* attention_mask, int B, int L,
                            const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int max_len,
                            void* workspace, size_t workspace_bytes, float* out, convdr_stream_t stream);
+
+/* The same forward for RAGGED input: instead of a padded [B, L] matrix and its mask, `tokens` (device int32 [n_tokens])
+ * holds the unmasked tokens of all B sequences back to back with no padding, and tok_offsets (device int32 [B+1]) where
+ * each begins: sequence b is tokens[tok_offsets[b] .. tok_offsets[b+1]), tok_offsets[b+1] - tok_offsets[b] == seq_lens[b],
+ * tok_offsets[B] <= n_tokens.  This is what a right-padded ("prefix") mask keeps; a mask with holes is not representable
+ * and stays with convdr_encoder_forward.  So sequences that arrive in batches of different widths run in one forward
+ * without being re-padded to the widest.  cu_seqlens, seq_lens, rows, max_len (>= max(seq_lens), as above), workspace
+ * (convdr_encoder_workspace_bytes), the status word, convdr_encoder_debug_layout and `out` are those of
+ * convdr_encoder_forward, and for the same sequences, cu_seqlens and B the result is bit-identical to it.
+ * Requires B > 0, n_tokens >= B, rows % 8 == 0, rows >= n_tokens, 0 < max_len <= n_tokens.  A sequence whose offsets are
+ * not as stated (or do not fit its rows cu[b+1] - cu[b]) is not read: CONVDR_ENC_STATUS_BAD_LENS is set and its rows are
+ * computed as empty; no read ever goes past tokens + n_tokens. */
+int convdr_encoder_forward_ragged(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
+                                  const int32_t* tokens, int64_t n_tokens, const int32_t* tok_offsets, int B,
+                                  const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows, int max_len,
+                                  void* workspace, size_t workspace_bytes, float* out, convdr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training step of the student encoder: replaces, for /root/reference/drivers/run_convdr_train.py:109-191,
