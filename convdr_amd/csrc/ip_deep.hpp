@@ -304,7 +304,7 @@ static bool ip_deep_sizes_ok(int nq, int64_t n, int d, int k, int cap) {
 static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_half,
                           const void* p_half_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
                           int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                          float* tau_retry, hipStream_t st) {
+                          float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false) {
   CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search_deep: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
   CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search_deep: need d %% 64 == 0 and d <= 4096 (got %d)", d);
   CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search_deep: block too large (n=%lld >= 2^31)", (long long)n);
@@ -326,7 +326,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
   double* band_x = (double*)(ws + p.o_bx);
   double* sort_x = (double*)(ws + p.o_sx);
   uint32_t* band = (uint32_t*)(ws + p.o_m);
-  const bool x3 = p_half_lo != nullptr;
+  const bool x3 = p_half_lo != nullptr || two_pass;   // the query's remainder is an operand (ip_search: `split`)
 
   bf16_t* qlo = x3 ? (bf16_t*)(ws + p.o_qlo) : nullptr;
   const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
@@ -345,6 +345,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
     ScanArgs a{};
     a.P = (const bf16_t*)p_half; a.Qb = qb; a.Plo = (const bf16_t*)p_half_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad;
     a.d = d; a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = list_id; a.cand_s = list_s; a.cap = cap; a.T = T;
+    a.two_pass = two_pass ? 1 : 0;
     if (tau_in) {
       CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
     } else if (p.mode < 0) {
@@ -356,7 +357,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
         const int64_t rows = std::min<int64_t>((int64_t)p.segTiles * p.tr, n - row0);
         ScanArgs b = a;
         b.P = a.P + row0 * d;
-        if (x3) b.Plo = a.Plo + row0 * d;
+        if (a.Plo) b.Plo = a.Plo + row0 * d;
         b.n = rows;
         b.nPt = (int)ceil_div64(rows, p.tr);   // = segTiles: only the block's last tile is ragged
         b.pt_stride = 1;
@@ -381,7 +382,12 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
   if (n > 0) {
     // (bands are thousands of rows per query here: more waves per query than the shallow call's 64 when queries are few)
     ProfScope prof("ip_rescore_deep", st);
-    hipLaunchKernelGGL(k_ip_rescore, dim3(nq, nq < 64 ? 128 : 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, band_id, band_x);
+    if (rows_f16)   // the half store: its halves are the rows, the fp64 sum is multiplied by 1 / p_scale once (k_ip_rescore)
+      hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, nq < 64 ? 128 : 16), dim3(256), 0, st, q_f32, (const _Float16*)p_half, d,
+                         cap, band, band_id, band_x, 1.0 / (double)p_scale);
+    else
+      hipLaunchKernelGGL(k_ip_rescore<float>, dim3(nq, nq < 64 ? 128 : 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, band_id,
+                         band_x, 1.0);
     CONVDR_CHECK_LAUNCH("k_ip_rescore");
   }
   static DeviceOnce attr_done;

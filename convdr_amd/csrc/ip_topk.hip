@@ -44,6 +44,12 @@ constexpr int IP_SAMPLE_MAX = 262144;
 //                     |fl(q) fl(p) - q p| summed over d  <=  rel |q||p| + eta (1 + u) sqrt(d) (|q| + |p|) + d eta^2
 //                     (ip_eps_abs; ~1e-6 of |q||p| at these scales).  The scan then works entirely in scaled units:
 //                     thresholds, candidate scores and eps; the results come from the fp64 re-scoring of the originals.
+//   half store:      (the passages ARE halves, the resident copy 2^s v is exact: the passage operand has no error)
+//                     one pass:   only the query rounds: u + d * 2^-23, and eta sqrt(d) |p| -- every term is one of the
+//                                 fp16 scan's above, which is used unchanged (a superset, incl. flushed subnormal inputs)
+//                     two passes: P Qh + P Ql leaves out the query's second-rounding remainder, <= u^2 (1 + u) |q| |p|, and
+//                                 runs two accumulation chains, 2 d * 2^-23; Qh and Ql each carry eta.  Term by term below
+//                                 the split scan's 3 u^2 (1 + 2u) + 3 d 2^-23 and 2 eta (1 + u) sqrt(d): used unchanged
 constexpr int IP_KIND_BF16 = 0, IP_KIND_F16 = 1;
 static inline float ip_eps_coef(int d, bool x3, int kind = IP_KIND_BF16) {
   const double u = kind == IP_KIND_F16 ? 1.0 / 2048.0 : 1.0 / 256.0, acc = (double)d / 8388608.0;
@@ -166,6 +172,58 @@ __global__ void __launch_bounds__(256) k_rows_to_half(const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The half store: the passage IS its stored half v; the resident copy holds 2^s v (scale = 2^s, s >= 0), which is at once
+// the corpus (re-scored in fp64 and multiplied by 2^-s, see k_ip_rescore) and the un-centred fp16 scan operand.
+// src: rows of halves (kept bit for bit) or fp32 rows (rounded to nearest even once, here).  store = half * scale; the
+// rows' UNSCALED norm is folded into *max_norm.  flags |= 1: a value is not finite (after rounding); flags |= 2: the
+// scaled value left the half range or does not divide back to the half (scaling a half by 2^s, s >= 0, is exact,
+// subnormals included, unless it overflows -- this is the check of that).  `store` may be `src` (halves): the in-place
+// rescale by 2^(s_new - s_old) <= 1 with s_new >= 0, equally exact; a lane reads its 8 bytes before it writes them.
+// store == nullptr: norms and flag 1 only.  One wave per row, 8- / 16-byte loads and 8-byte stores, no LDS.
+// ------------------------------------------------------------------------------------------
+template <bool SRC_F32>
+__global__ void __launch_bounds__(256) k_store_rows_f16(const void* src, int64_t n, int d, float scale, float inv_scale,
+                                                        _Float16* store, float* __restrict__ max_norm,
+                                                        int32_t* __restrict__ flags) {
+  typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float wmax = 0.f;
+  int bad = 0;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < n; row += (int64_t)gridDim.x * 4) {
+    double ss = 0.0;
+    for (int e = lane * 4; e < d; e += 256) {
+      f16x4_t h;
+      if constexpr (SRC_F32) {
+        const float4 v = *(const float4*)((const float*)src + row * d + e);
+        h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};   // round to nearest even
+      } else {
+        const uint2 raw = *(const uint2*)((const _Float16*)src + row * d + e);
+        h = *(const f16x4_t*)&raw;
+      }
+      f16x4_t o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float f = (float)h[c];
+        o[c] = (_Float16)(f * scale);          // fp32 product of a half and a power of two: exact; then one conversion
+        // the sign comes from the source bits: a half of -0 stays -0 however the product above is contracted
+        // (a multiply selected as a fused multiply-add with a +0 addend returns +0 for it)
+        o[c] = __builtin_copysignf16(o[c], h[c]);
+        const float back = (float)o[c];
+        if (!(fabsf(f) <= 65504.f)) bad |= 1;
+        else if (!(fabsf(back) <= 65504.f) || back * inv_scale != f) bad |= 2;
+        ss += (double)f * (double)f;
+      }
+      if (store) *(uint2*)(store + row * d + e) = *(const uint2*)&o;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    wmax = fmaxf(wmax, (float)(sqrt(ss) * (1.0 + 1e-6)));   // (rounded up: a bound; NaN rows raise flag 1 instead)
+  }
+  if (max_norm && lane == 0 && wmax > 0.f) atomicMax((int*)max_norm, __float_as_int(wmax));  // non-negative floats order like ints
+  if (bad) atomicOr(flags, bad);
+}
+
 // column sums of fp32 rows: part[chunk][d]; grid (ceil(d / 256), chunks)
 __global__ void __launch_bounds__(256) k_colsum_f32(const float* __restrict__ X, int64_t n, int d, float* __restrict__ part) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -217,6 +275,7 @@ struct ScanArgs {
   int cap;
   float* T;          // FULL: [nPt*128, nq_pad]; TOP2: [nPt*8, nq_pad]
   int dbg_prelanded; // timing experiment (TRACE library only): a tile's first K chunks are not waited for (garbage results)
+  int two_pass;      // half store (fp16 only): S~ = P Qh + P Ql, the passage operand is exact and has no remainder copy
 };
 
 template <int MODE, class T>
@@ -320,7 +379,9 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 // tile order, query tile fastest); the first K chunk of the next tile streams into the idle operand stage while the
 // epilogue of this one runs, so neither the workgroup dispatch gap nor the cold HBM round trip for a fresh passage
 // tile is exposed (they were ~40 % of a 12-step tile).
-template <int MODE, class T, bool X3, bool F16>
+// PASSES: 1 = S~ = Ph Qh; 3 = the split scan Ph Qh + Ph Ql + Pl Qh; 2 = the half store's second rung P Qh + P Ql (the
+// stored halves ARE the passages: there is no Pl).
+template <int MODE, class T, int PASSES, bool F16>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t ntiles = (uint32_t)a.nPt * (uint32_t)a.nQt;
@@ -363,13 +424,15 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) tau_lane[nt] = tau_next[nt];
     int idle = gemm_nt_mainloop<T, F16>(src, a.d, smem, acc, w, buf, true);
-    if constexpr (X3) {  // S~ = Ph Qh + Ph Ql + Pl Qh: fp32-class scores from three bf16 passes into the same accumulators
+    if constexpr (PASSES >= 2) {  // S~ = Ph Qh + Ph Ql + Pl Qh: fp32-class scores from three bf16 passes into the same accumulators
       __syncthreads();
       const TileSrc<T> s2(a.P, a.d, a.n, a.Qlo, a.d, a.nq_pad, m0, n0, w);
       idle = gemm_nt_mainloop<T, F16>(s2, a.d, smem, acc, w, idle);
-      __syncthreads();
-      const TileSrc<T> s3(a.Plo, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
-      idle = gemm_nt_mainloop<T, F16>(s3, a.d, smem, acc, w, idle);
+      if constexpr (PASSES == 3) {
+        __syncthreads();
+        const TileSrc<T> s3(a.Plo, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
+        idle = gemm_nt_mainloop<T, F16>(s3, a.d, smem, acc, w, idle);
+      }
     }
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_lane[nt]));   // hipcc: the loads are retired HERE
@@ -762,27 +825,49 @@ __global__ void __launch_bounds__(1024) k_ip_cut(int64_t n, int k, int cap, cons
 // exact rescoring: canonical fp64 inner product (see oracle/search.py: lane l owns elements
 // 256 j + 4 l + c, accumulated in (j, c) order; then butterfly 32,16,8,4,2,1)
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_ip_rescore(const float* __restrict__ Q, const float* __restrict__ P, int d,
+// PT = the passage element type: float (the fp32 block) or _Float16 (the half store, which holds 2^s v for the stored
+// half v).  A lane's 4 halves are one 8-byte load and widen to double exactly; the lane / (j, c) / butterfly order is
+// the same.  Every product q (2^s v) is 2^s (q v) exactly, and every fp64 rounding of the fma chain and of the butterfly
+// commutes with a power-of-two factor (|q| < 2^128, |2^s v| < 2^16, and the smallest non-zero product, 2^-149 2^-24 =
+// 2^-173, is 849 binades above the fp64 subnormals: nothing overflows or loses bits to underflow), so the sum is 2^s times the
+// oracle's sum bit for bit, and ONE multiplication by 2^-s after the butterfly (`unscale`, exact) gives the oracle's value.
+struct f64x4 { double x, y, z, w; };
+template <class PT>
+__device__ __forceinline__ f64x4 ip_load4_f64(const PT* p) {
+  if constexpr (sizeof(PT) == 2) {
+    typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+    const uint2 raw = *(const uint2*)p;
+    const f16x4_t h = *(const f16x4_t*)&raw;
+    return {(double)h[0], (double)h[1], (double)h[2], (double)h[3]};
+  } else {
+    const float4 y = *(const float4*)p;
+    return {(double)y.x, (double)y.y, (double)y.z, (double)y.w};
+  }
+}
+
+template <class PT>
+__global__ void __launch_bounds__(256) k_ip_rescore(const float* __restrict__ Q, const PT* __restrict__ P, int d,
                                                     int cap, const uint32_t* __restrict__ m_in,
                                                     const uint32_t* __restrict__ cand_id,
-                                                    double* __restrict__ cand_x) {
+                                                    double* __restrict__ cand_x, double unscale) {
   const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t c = m_in[q];
   const float* qv = Q + (int64_t)q * d;
   for (uint32_t slot = blockIdx.y * 4 + wave; slot < c; slot += gridDim.y * 4) {
     const uint32_t id = cand_id[(int64_t)q * cap + slot];
-    const float* pv = P + (int64_t)id * d;
+    const PT* pv = P + (int64_t)id * d;
     double acc = 0.0;
     for (int e = lane * 4; e < d; e += 256) {
       const float4 x = *(const float4*)(qv + e);
-      const float4 y = *(const float4*)(pv + e);
-      acc = fma((double)x.x, (double)y.x, acc);
-      acc = fma((double)x.y, (double)y.y, acc);
-      acc = fma((double)x.z, (double)y.z, acc);
-      acc = fma((double)x.w, (double)y.w, acc);
+      const f64x4 y = ip_load4_f64<PT>(pv + e);
+      acc = fma((double)x.x, y.x, acc);
+      acc = fma((double)x.y, y.y, acc);
+      acc = fma((double)x.z, y.z, acc);
+      acc = fma((double)x.w, y.w, acc);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if constexpr (sizeof(PT) == 2) acc *= unscale;
     if (lane == 0) cand_x[(int64_t)q * cap + slot] = acc;
   }
 }
@@ -864,15 +949,16 @@ __global__ void __launch_bounds__(IP_SELECT_THREADS) k_ip_select(int k, int cap,
 // -> cap x 16 bytes (64 KB at the default cap of 4096: two workgroups per CU).  The per-query band size and packed candidate
 // count are still written (convdr_ip_debug_*).  convdr_set_option("ip_fused_finish", 0) gives the three launches back.
 // ------------------------------------------------------------------------------------------
+template <class PT>
 __global__ void __launch_bounds__(1024) k_ip_finish(int64_t n, int k, int cap, const uint32_t* __restrict__ counts,
                                                    uint32_t* __restrict__ counts_packed,
                                                    const uint32_t* __restrict__ cand_id, const float* __restrict__ cand_s,
                                                    const float* __restrict__ tau, const float* __restrict__ qnorm,
                                                    const float* __restrict__ p_max_norm, float eps_coef, float eps_abs,
                                                    float p_scale, float norm_limit, const float* __restrict__ Q,
-                                                   const float* __restrict__ P, int d, uint32_t* __restrict__ m_out,
+                                                   const PT* __restrict__ P, int d, uint32_t* __restrict__ m_out,
                                                    int32_t* __restrict__ status, float* __restrict__ tau_retry,
-                                                   float* __restrict__ D, int64_t* __restrict__ I) {
+                                                   float* __restrict__ D, int64_t* __restrict__ I, double unscale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ SelectScratch sc;
   __shared__ uint32_t sh_m, sh_g;
@@ -931,18 +1017,19 @@ __global__ void __launch_bounds__(1024) k_ip_finish(int64_t n, int k, int cap, c
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const float* qv = Q + (int64_t)q * d;
     for (int slot = wave; slot < m; slot += nw) {
-      const float* pv = P + (int64_t)bid[slot] * d;
+      const PT* pv = P + (int64_t)bid[slot] * d;
       double acc = 0.0;
       for (int e = lane * 4; e < d; e += 256) {
         const float4 x = *(const float4*)(qv + e);
-        const float4 y = *(const float4*)(pv + e);
-        acc = fma((double)x.x, (double)y.x, acc);
-        acc = fma((double)x.y, (double)y.y, acc);
-        acc = fma((double)x.z, (double)y.z, acc);
-        acc = fma((double)x.w, (double)y.w, acc);
+        const f64x4 y = ip_load4_f64<PT>(pv + e);
+        acc = fma((double)x.x, y.x, acc);
+        acc = fma((double)x.y, y.y, acc);
+        acc = fma((double)x.z, y.z, acc);
+        acc = fma((double)x.w, y.w, acc);
       }
 #pragma unroll
       for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+      if constexpr (sizeof(PT) == 2) acc *= unscale;   // (the half store: exact, see k_ip_rescore)
       if (lane == 0) sx[slot] = acc;     // (key[] is dead: every thread passed the barrier after the compaction)
     }
   }
@@ -1046,10 +1133,10 @@ static IpPlan ip_plan(int nq, int64_t n, int d, int k, int cap) {
   return p;
 }
 
-template <int MODE, class T, bool X3, bool F16>
+template <int MODE, class T, int PASSES, bool F16>
 static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
   const unsigned tiles = (unsigned)a.nPt * (unsigned)a.nQt;
-  if constexpr (MODE == IP_MODE_EMIT && !X3) {   // the two-stage loop
+  if constexpr (MODE == IP_MODE_EMIT && PASSES == 1) {   // the two-stage loop
     constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
     static DeviceOnce attr3;  // > 48 KB dynamic LDS needs the opt-in once per kernel and device
     if (attr3.first())
@@ -1065,7 +1152,7 @@ static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
   } else {
     static DeviceOnce attr_done;
     if (attr_done.first())
-      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, X3, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, PASSES, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            T::SMEM_BYTES));
     const unsigned slots = (unsigned)device_cu_count() * (T::SMEM_BYTES > 80 * 1024 ? 1u : 2u);
     const unsigned grid = std::min(tiles, slots);
@@ -1075,7 +1162,7 @@ static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
     static const bool no_emit = getenv("CONVDR_DBG_SCAN_NOEMIT") != nullptr;   // timing only: every threshold = +inf
     if (no_emit) b.nq = 0;
 #endif
-    hipLaunchKernelGGL((k_ip_scan<MODE, T, X3, F16>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
+    hipLaunchKernelGGL((k_ip_scan<MODE, T, PASSES, F16>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
     CONVDR_CHECK_LAUNCH("k_ip_scan");
   }
   return 0;
@@ -1083,7 +1170,11 @@ static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
 
 template <int MODE, class T, bool F16>
 static int launch_scan_t(const ScanArgs& a, hipStream_t st) {
-  return a.Plo ? launch_scan_x<MODE, T, true, F16>(a, st) : launch_scan_x<MODE, T, false, F16>(a, st);
+  if (a.two_pass) {
+    if constexpr (F16) return launch_scan_x<MODE, T, 2, F16>(a, st);
+    CONVDR_REQUIRE(false, "convdr_ip_search: the two-pass scan exists for fp16 only");
+  }
+  return a.Plo ? launch_scan_x<MODE, T, 3, F16>(a, st) : launch_scan_x<MODE, T, 1, F16>(a, st);
 }
 
 template <int MODE, bool F16>
@@ -1509,10 +1600,12 @@ extern "C" const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, i
   return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, k, cap).o_m);
 }
 
+// rows_f16: the half store -- p_f32 is not used, the re-score reads p_bf16 (halves of 2^s v, p_scale = 2^s) and
+// two_pass selects its second rung (no remainder copy: p_bf16_lo is NULL).
 static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_bf16,
                      const void* p_bf16_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
                      int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                     float* tau_retry, hipStream_t st) {
+                     float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false) {
   CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
   CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search: need d %% 64 == 0 and d <= 4096 (got %d)", d);
   CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search: block too large (n=%lld >= 2^31)", (long long)n);
@@ -1534,7 +1627,9 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
   uint32_t* band = (uint32_t*)(ws + p.o_m);
 
   // queries -> 16-bit operands (+ norms); the kernel also zeroes the padding rows and the candidate counters
-  bf16_t* qlo = p_bf16_lo ? (bf16_t*)(ws + p.o_qlo) : nullptr;
+  const bool split = p_bf16_lo != nullptr || two_pass;   // the query's remainder is an operand: the tighter error band
+  const double unscale = 1.0 / (double)p_scale;
+  bf16_t* qlo = split ? (bf16_t*)(ws + p.o_qlo) : nullptr;
   const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
   if (kind == IP_KIND_F16)
     hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
@@ -1550,6 +1645,7 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
     ScanArgs a{};
     a.P = (const bf16_t*)p_bf16; a.Qb = qb; a.Plo = (const bf16_t*)p_bf16_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad; a.d = d;
     a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = cand_id; a.cand_s = cand_s; a.cap = cap; a.T = T;
+    a.two_pass = two_pass ? 1 : 0;
     if (tau_in) {
       CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
     } else if (p.mode < 0) {
@@ -1592,15 +1688,21 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
     CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_cut, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
     CONVDR_CHECK_HIP(
         hipFuncSetAttribute((const void*)k_ip_select, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 12));
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
   }
+  const float eps_coef = ip_eps_coef(d, split, kind), eps_abs = ip_eps_abs(d, split, kind);
   if (g_ip_fused_finish && n > 0) {
     ProfScope prof("ip_finish", st);
-    hipLaunchKernelGGL(k_ip_finish, dim3(nq), dim3(1024), (size_t)cap * 16, st, n, k, cap, counts,
-                       (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm,
-                       ip_eps_coef(d, p_bf16_lo != nullptr, kind), ip_eps_abs(d, p_bf16_lo != nullptr, kind),
-                       kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, q_f32, p_f32, d,
-                       band, status, tau_retry, D, I);
+    if (rows_f16)
+      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n, k, cap, counts,
+                         (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs, p_scale,
+                         IP_F16_NORM_LIMIT, q_f32, (const _Float16*)p_bf16, d, band, status, tau_retry, D, I, unscale);
+    else
+      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n, k, cap, counts,
+                         (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs,
+                         kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, q_f32, p_f32, d,
+                         band, status, tau_retry, D, I, 1.0);
     CONVDR_CHECK_LAUNCH("k_ip_finish");
     return 0;
   }
@@ -1608,14 +1710,18 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
   ProfScope prof("ip_cut", st);
   hipLaunchKernelGGL(k_ip_cut, dim3(nq), dim3(1024), (size_t)cap * 8, st, n, k, cap, counts,
                      (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm,
-                     p_max_norm, ip_eps_coef(d, p_bf16_lo != nullptr, kind), ip_eps_abs(d, p_bf16_lo != nullptr, kind),
+                     p_max_norm, eps_coef, eps_abs,
                      kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, band, status,
                      tau_retry);
   CONVDR_CHECK_LAUNCH("k_ip_cut");
   }
   if (n > 0) {
     ProfScope prof("ip_rescore", st);
-    hipLaunchKernelGGL(k_ip_rescore, dim3(nq, 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, cand_id, cand_x);
+    if (rows_f16)
+      hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, 16), dim3(256), 0, st, q_f32, (const _Float16*)p_bf16, d, cap, band,
+                         cand_id, cand_x, unscale);
+    else
+      hipLaunchKernelGGL(k_ip_rescore<float>, dim3(nq, 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, cand_id, cand_x, 1.0);
     CONVDR_CHECK_LAUNCH("k_ip_rescore");
   }
   ProfScope prof("ip_select", st);
@@ -1641,4 +1747,51 @@ extern "C" int convdr_ip_search_f16(const float* q_f32, int nq, const float* p_f
                  (double)p_scale);
   return ip_search(IP_KIND_F16, p_scale, q_f32, nq, p_f32, p_f16, p_f16_lo, n, d, k, p_max_norm, tau_in, cap, rank_target,
                    workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream);
+}
+
+// ---- the half store ------------------------------------------------------------------------------------------------
+static bool ip_pow2_scale_ok(float s) {   // a finite power of two
+  int ex = 0;
+  return s > 0.f && s < INFINITY && frexpf(s, &ex) == 0.5f;
+}
+
+extern "C" int convdr_ip_store_rows_f16(const void* src, int src_is_f32, int64_t n, int d, float scale, void* store,
+                                        float* max_norm, int32_t* flags, convdr_stream_t stream) {
+  CONVDR_REQUIRE(n >= 0 && d > 0 && d % 64 == 0, "convdr_ip_store_rows_f16: need d %% 64 == 0 (got n=%lld d=%d)", (long long)n, d);
+  CONVDR_REQUIRE(ip_pow2_scale_ok(scale), "convdr_ip_store_rows_f16: scale must be a power of two (got %g)", (double)scale);
+  CONVDR_REQUIRE(scale >= 1.f || (!src_is_f32 && src == store && src != nullptr),
+                 "convdr_ip_store_rows_f16: scale must be >= 1 (got %g); only the in-place rescale of a half store takes a "
+                 "factor below 1", (double)scale);
+  CONVDR_REQUIRE(flags != nullptr || n == 0, "convdr_ip_store_rows_f16: flags is NULL");
+  if (n == 0) return 0;
+  const int64_t blocks = ceil_div64(n, 4);
+  const unsigned grid = (unsigned)(blocks < 8192 ? blocks : 8192);
+  if (src_is_f32)
+    hipLaunchKernelGGL(k_store_rows_f16<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, n, d, scale, 1.f / scale,
+                       (_Float16*)store, max_norm, flags);
+  else
+    hipLaunchKernelGGL(k_store_rows_f16<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, n, d, scale, 1.f / scale,
+                       (_Float16*)store, max_norm, flags);
+  CONVDR_CHECK_LAUNCH("k_store_rows_f16");
+  return 0;
+}
+
+extern "C" int convdr_ip_search_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n, int d,
+                                    int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
+                                    size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                                    convdr_stream_t stream) {
+  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && p_scale >= 1.f,
+                 "convdr_ip_search_h16: p_scale must be a power of two >= 1 (got %g)", (double)p_scale);
+  return ip_search(IP_KIND_F16, p_scale, q_f32, nq, nullptr, store_f16, nullptr, n, d, k, p_max_norm, tau_in, cap, rank_target,
+                   workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, true, two_pass != 0);
+}
+
+extern "C" int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n,
+                                         int d, int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target,
+                                         void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
+                                         float* tau_retry, convdr_stream_t stream) {
+  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && p_scale >= 1.f,
+                 "convdr_ip_search_deep_h16: p_scale must be a power of two >= 1 (got %g)", (double)p_scale);
+  return ip_search_deep(IP_KIND_F16, p_scale, q_f32, nq, nullptr, store_f16, nullptr, n, d, k, p_max_norm, tau_in, cap,
+                        rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, true, two_pass != 0);
 }

@@ -55,10 +55,21 @@ def plan_batches(lens, batch_size, token_budget=None, align=1):
     return out
 
 
+def _out_dtype(out_dtype):
+    """(numpy dtype, torch dtype) of the embeddings a shard returns: float32, or float16 for half blocks"""
+    dt = np.dtype(np.float32 if out_dtype is None else out_dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError("encode: out_dtype must be float32 or float16 (got %s)" % dt)
+    return dt, (torch.float16 if dt == np.float16 else torch.float32)
+
+
 def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_inference=False, max_seq_length=None,
-                 progress=None, token_budget=None):
+                 progress=None, token_budget=None, out_dtype=np.float32):
     """-> (embedding float32 [n, D] numpy, embedding2id int64 [n]) for this rank's records, in record order.
-    token_budget: see plan_batches (batch_size then only caps the record count and sizes the staging buffers)."""
+    token_budget: see plan_batches (batch_size then only caps the record count and sizes the staging buffers).
+    out_dtype=np.float16: the embeddings are rounded to nearest even on the device (``.half()``) and come back through a
+    pinned half buffer -- the rows of a half block, which FlatIPIndex(storage="fp16") keeps bit for bit."""
+    np_dt, t_dt = _out_dtype(out_dtype)
     tower_call = _embed_fn(model, is_query_inference)
     dev = next(model.parameters()).device
     idx = blocks.shard_indices(len(cache), world, rank)
@@ -67,7 +78,7 @@ def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_infere
     base_len = None if is_query_inference else getattr(model.module if hasattr(model, "module") else model, "base_len", None)
     if base_len:
         return _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, int(base_len), batch_size, progress, token_budget,
-                                    model)
+                                    model, np_dt, t_dt)
     out = None
     on_gpu = dev.type == "cuda"       # (the encoder itself is GPU-only; a host "device" only occurs with a stand-in tower in
     pin = (lambda t: t.pin_memory()) if on_gpu else (lambda t: t)     #  the multi-process CPU tests of the shard / file logic)
@@ -89,8 +100,8 @@ def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_infere
         with torch.no_grad():
             emb = tower_call(ids, lens)
         if out is None:
-            out = pin(torch.empty((len(idx), emb.shape[1]), dtype=torch.float32))
-        out[s:s + n].copy_(emb, non_blocking=True)
+            out = pin(torch.empty((len(idx), emb.shape[1]), dtype=t_dt))
+        out[s:s + n].copy_(emb if emb.dtype == t_dt else emb.to(t_dt), non_blocking=True)
         if progress:
             progress(n)
     if on_gpu:
@@ -98,11 +109,12 @@ def encode_shard(model, cache, rank=0, world=1, batch_size=1024, is_query_infere
         from .train import check_status
         check_status(model)  # token ids outside the embedding table: IndexError like the reference's lookup (models.py:141)
     if out is None:
-        return np.zeros((0, 768), np.float32), idx
+        return np.zeros((0, 768), np_dt), idx
     return out.numpy(), idx
 
 
-def _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, base_len, batch_size, progress, token_budget, model):
+def _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, base_len, batch_size, progress, token_budget, model,
+                         np_dt=np.dtype(np.float32), t_dt=torch.float32):
     """encode_shard for a MaxP model (``base_len``: RobertaDot_CLF_ANN_NLL_MultiChunk, models.py:159-188): one ROW PER LIVE
     CHUNK.  A record of l tokens yields its ceil(l / base_len) chunks, chunk j = tokens [j * base_len, min(l, (j + 1) *
     base_len)), as rows in record-major order, and embedding2id repeats the record offset for each -- what the reference's
@@ -141,8 +153,8 @@ def _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, base_len, bat
         with torch.no_grad():
             emb = tower_call(ids, lens)
         if out is None:
-            out = pin(torch.empty((len(rec), emb.shape[1]), dtype=torch.float32))
-        out[s:e].copy_(emb, non_blocking=True)
+            out = pin(torch.empty((len(rec), emb.shape[1]), dtype=t_dt))
+        out[s:e].copy_(emb if emb.dtype == t_dt else emb.to(t_dt), non_blocking=True)
         if progress:
             progress(n)
     if on_gpu:
@@ -150,7 +162,7 @@ def _encode_shard_chunks(tower_call, dev, cache, idx, lens_all, L, base_len, bat
         from .train import check_status
         check_status(model)
     if out is None:
-        return np.zeros((0, 768), np.float32), embid
+        return np.zeros((0, 768), np_dt), embid
     return out.numpy(), embid
 
 
@@ -166,9 +178,13 @@ def _embed_fn(model, is_query):
     return lambda ids, lens: tower.embed(ids, None, head=head, seq_lens=lens)
 
 
-def StreamInferenceDoc(args, model, cache, prefix="passage_", is_query_inference=False, batch_size=None):
+def StreamInferenceDoc(args, model, cache, prefix="passage_", is_query_inference=False, batch_size=None, out_dtype=None):
     """Encode this rank's shard and write its two block files; same file names / contents as the reference
-    (`merge=False` path, gen_passage_embeddings.py:156-167)."""
+    (`merge=False` path, gen_passage_embeddings.py:156-167).
+    out_dtype (default: ``args.emb_dtype``, else float32): np.float16 writes a float16 embedding block -- half the bytes on
+    disk and over PCIe, the input of FlatIPIndex(storage="fp16"); the id file does not change."""
+    if out_dtype is None:
+        out_dtype = getattr(args, "emb_dtype", None) or np.float32
     dist = _dist()
     rank = dist.get_rank() if dist else int(getattr(args, "rank", 0) or 0)
     world = dist.get_world_size() if dist else int(getattr(args, "world_size", 1) or 1)
@@ -177,7 +193,7 @@ def StreamInferenceDoc(args, model, cache, prefix="passage_", is_query_inference
     if dist:
         dist.barrier()
     emb, embid = encode_shard(model, cache, rank, world, batch_size or getattr(args, "per_gpu_eval_batch_size", 64),
-                              is_query_inference, getattr(args, "max_seq_length", None))
+                              is_query_inference, getattr(args, "max_seq_length", None), out_dtype=out_dtype)
     blocks.dump_block(os.path.join(args.output_dir, "%s_emb_p__data_obj_%d.pb" % (prefix, rank)), emb)
     blocks.dump_block(os.path.join(args.output_dir, "%s_embid_p__data_obj_%d.pb" % (prefix, rank)), embid)
     if dist:

@@ -27,7 +27,10 @@ def _torch():
 
 STATUS_OK, STATUS_OVERFLOW, STATUS_TOO_FEW, STATUS_UNCERTAIN, STATUS_RANGE = 0, 1, 2, 3, 4
 
-_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16"}
+_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16"}
+_SPLIT = ("bf16x3", "fp16x3", "fp16x2")          # precisions that pin the second rung
+_HALF_PRECISIONS = ("auto", "fp16", "fp16x2")    # the rungs of a half store (storage="fp16")
+HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM_LIMIT
 
 
 class FlatIPIndex:
@@ -44,13 +47,31 @@ class FlatIPIndex:
     component).
     reserve(n): allocate the resident block for n passages up front; add() then fills it in place.  Without it every
     add() after the first re-allocates (FAISS semantics need one contiguous block): fine for the reference's one add per
-    reset, not for building a 117 GB corpus from slices."""
+    reset, not for building a 117 GB corpus from slices.
+    storage: "fp32" (default) is the index described above.  "fp16" is the HALF STORE: the passage is kept once, in 16 bits,
+    and that copy is both the corpus and the scan operand (include/convdr_hip.h, "Half-precision passage store") -- a third
+    of the bytes, no fp32 block, no remainder copy, no centre.  The corpus is then DEFINED as the stored halves (float16
+    rows are kept bit for bit, fp32 rows are rounded to nearest even once, at add) and ``search`` returns the exact,
+    certified top-k of those halves widened to fp32.  Its precisions are "auto" (single pass, then the two-pass rung
+    P Qh + P Ql, then the exhaustive rung; `stats["x2_queries"]`), "fp16" and "fp16x2"; add() refuses (ConvdrError, index
+    unchanged) rows with a value that is not finite as a half or with a norm above 60,000."""
 
-    def __init__(self, d, device=None, cap=4096, rank_target=0, precision="auto", center=True, prepin=True):
+    def __init__(self, d, device=None, cap=4096, rank_target=0, precision="auto", center=None, prepin=True, storage="fp32"):
+        if storage not in ("fp32", "fp16"):
+            raise ValueError("FlatIPIndex: storage must be 'fp32' or 'fp16' (got %r)" % (storage,))
+        if storage == "fp16":
+            if precision not in _HALF_PRECISIONS:
+                raise ValueError("FlatIPIndex(storage='fp16'): precision must be one of %s (got %r)" % (_HALF_PRECISIONS, precision))
+            if center:
+                raise ValueError("FlatIPIndex(storage='fp16'): the half store is not centred (center=True)")
+            center = False
+        elif center is None:
+            center = True
         import torch
         if not torch.cuda.is_available():
             raise _lib.ConvdrError("FlatIPIndex needs a GPU (no CPU fallback)")
-        assert precision in _KINDS, precision
+        assert precision in _KINDS and (storage == "fp16" or precision != "fp16x2"), precision
+        self.storage, self._half = storage, storage == "fp16"
         _lib.lib()
         # the scan contracts in 64-wide K steps: other widths get zero columns, which add exact zeros to every score
         self.d_in = int(d)
@@ -95,7 +116,7 @@ class FlatIPIndex:
         """An empty index with this one's parameters (search_one_by_one keeps two blocks in flight: one being searched, one
         being loaded)."""
         t = FlatIPIndex(self.d_in, device=self.device, cap=self.cap, rank_target=self.rank_target, precision=self.precision,
-                        center=self.center, prepin=False)
+                        center=None if self._half else self.center, prepin=False, storage=self.storage)
         t.host_chunk_bytes, t.host_copy_threads, t.host_stage_buffers = self.host_chunk_bytes, self.host_copy_threads, self.host_stage_buffers
         return t
 
@@ -117,6 +138,23 @@ class FlatIPIndex:
     def _plo(self):
         return None if self._slo is None else self._slo[:self._n]
 
+    @property
+    def _rows(self):
+        """The rows the canonical re-score reads: the fp32 block, or the half store itself."""
+        return self._pbf if self._half else self._p32
+
+    @property
+    def store(self):
+        """storage="fp16": the resident halves [ntotal, d] = 2^s x the stored passages (s: ``_scale``)."""
+        return self._pbf if self._half else None
+
+    def _row_pair(self, sel):
+        """(re-score rows, scan copy) of a slice or an index vector of the resident rows, contiguous"""
+        if self._half:
+            r = self._pbf[sel].contiguous()
+            return r, r
+        return self._p32[sel].contiguous(), self._pbf[sel].contiguous()
+
     def reset(self):
         """faiss ``index.reset()``: forget the passages.  A reservation made with reserve() survives (its memory is reused
         by the next block); ``release()`` drops it."""
@@ -127,6 +165,11 @@ class FlatIPIndex:
         self._centre = None
         self._scale = 1.0                       # power of two applied to the fp16 scan copy (1 for bf16)
         self._max_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self._half:
+            # max norm and the flag word of convdr_ip_store_rows_f16 side by side: ONE host read at the end of an add()
+            self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self._max_norm, self._flags = self._mf[:1], self._mf[1:2].view(torch.int32)
+            self._uflags = self._mf[2:].view(torch.int32)       # update_rows has a flag word of its own: update_flags()
         self._ws = None
         self._x3_first = False
         if not hasattr(self, "_copy_stream"):
@@ -141,6 +184,15 @@ class FlatIPIndex:
         `lo`, default: only if the precision pins it).  Existing rows are kept."""
         import torch
         n = int(n)
+        if self._half:
+            if self._s16 is None or self._s16.shape[0] < n:
+                with torch.cuda.device(self.device):
+                    t = torch.empty((n, self.d), dtype=torch.float16, device=self.device)
+                    if self._s16 is not None and self._n:
+                        t[:self._n].copy_(self._s16[:self._n])
+                    self._s16 = t
+            self._reserved = True
+            return
         want_lo = (self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)
         if self._s32 is not None and self._s32.shape[0] >= n and (self._slo is not None or not want_lo):
             self._reserved = True
@@ -185,6 +237,16 @@ class FlatIPIndex:
         """CONVDR_IP_RANGE: rows added after the scale was fixed are more than 7x longer than the first block's longest.
         Re-derive the scale from the block's max norm and rebuild the fp16 copies from the resident fp32 rows."""
         import torch
+        if self._half:
+            # the half store is rescaled IN PLACE by 2^(s_new - s_old) <= 1, s_new >= 0: exact (convdr_ip_store_rows_f16)
+            new = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
+            with torch.cuda.device(self.device):
+                if self._n and new != self._scale:
+                    self._store_rows(self._pbf, self._pbf, new / self._scale, fold_norm=False)
+                    if int(self._flags.item()):
+                        raise _lib.ConvdrError("half store: the in-place rescale %g -> %g was not exact" % (self._scale, new))
+            self._scale = new
+            return
         with torch.cuda.device(self.device):
             self._scale = float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item())))
             if self._n:
@@ -209,6 +271,8 @@ class FlatIPIndex:
         host copy of the 14.6 GB block) and a pageable copy (run_convdr_inference.py:164-180)."""
         import torch
         chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
+        if self._half:
+            return self._add_half(x, chunk_bytes)
         if self.d != self.d_in:
             x = self._pad_columns(x.array if hasattr(x, "array") else x)
         if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView: positioned reads from the file
@@ -250,6 +314,140 @@ class FlatIPIndex:
                 dst32.copy_(t)
             self._prepare_into(dst32, dst16, dstlo)
         self._n += m
+
+    # -- the half store (storage="fp16") ----------------------------------------
+    def _store_rows(self, src, dst, scale, fold_norm=True, flags=None):
+        """convdr_ip_store_rows_f16: dst = half(src) * scale (dst None: norms and the non-finite flag only)"""
+        import torch
+        _lib.check(_lib.lib().convdr_ip_store_rows_f16(_lib.ptr(src), int(src.dtype == torch.float32), src.shape[0], self.d,
+                                                       float(scale), _lib.ptr(dst), _lib.ptr(self._max_norm) if fold_norm else None,
+                                                       _lib.ptr(self._flags if flags is None else flags), _lib.stream_ptr()),
+                   "convdr_ip_store_rows_f16")
+
+    def update_flags(self):
+        """Flag word of the update_rows calls so far (one host read): bit 0 = a new row held a value that is not finite as
+        a half, bit 1 = a scaled value overflowed (the rows outgrew the scale by more than CONVDR_IP_RANGE catches)."""
+        return int(self._uflags.item())
+
+    def _half_first_scale(self, src):
+        """An empty half store takes its scale from the first rows' largest norm (one pass, one host read), never below 1."""
+        self._store_rows(src, None, 1.0)
+        self._scale = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
+
+    def _half_grow(self, m):
+        need = self._n + m
+        if self._s16 is None or self._s16.shape[0] < need:
+            keep = getattr(self, "_reserved", False)
+            self.reserve(need)
+            self._reserved = keep
+        return self._s16[self._n:need]
+
+    def _add_half(self, x, chunk_bytes):
+        """add() of a half store.  `write(dst)` below puts the new rows into dst = store[n, n + m) (rounded, scaled, norms
+        and flags folded); the flag word and the max norm are read ONCE, at the end, and decide: keep, refuse (the index is
+        left exactly as it was), or -- a scaled value overflowed: the new rows are too long for the scale -- lower the scale,
+        rescale the resident rows in place and write the new rows once more (the only case with a second read)."""
+        import torch
+        if self.d != self.d_in:
+            x = self._pad_columns(x.array if hasattr(x, "array") else x)
+        reader = None
+        if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView
+            reader, x = x.read_rows_into, x.array
+        if isinstance(x, torch.Tensor) and x.device.type == "cpu" and not x.is_pinned() and x.dtype == torch.float16:
+            x = x.numpy()
+        if isinstance(x, np.ndarray) and x.dtype == np.float16 and x.ndim == 2 and x.nbytes > chunk_bytes // 2:
+            assert x.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, x.shape)
+            m, arr = int(x.shape[0]), x
+            write = lambda dst, first: self._half_stream(arr, dst, chunk_bytes, reader, first)
+        else:
+            from_host = not (isinstance(x, torch.Tensor) and x.is_cuda)
+            if isinstance(x, np.ndarray) and not x.flags.writeable:
+                x = np.array(x, order="C")              # (see add(): a read-only mapping is never aliased)
+            t = torch.as_tensor(x)
+            if t.dtype not in (torch.float16, torch.float32):
+                t = t.float()
+            t = t.to(self.device, non_blocking=not from_host or t.is_pinned()).contiguous()
+            assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
+            m = int(t.shape[0])
+
+            def write(dst, first):
+                if first:
+                    self._half_first_scale(t)
+                self._store_rows(t, dst, self._scale)
+        if m == 0:
+            return
+        n0, scale0 = self._n, self._scale
+        with torch.cuda.device(self.device):
+            mn0 = self._max_norm.clone()
+            dst = self._half_grow(m)
+            for attempt in (0, 1):
+                write(dst, n0 == 0 and attempt == 0)
+                got = self._mf[:2].cpu()                                    # the one host read of this add()
+                mn, fl = float(got[0]), int(got.view(torch.int32)[1])
+                self._flags.zero_()
+                if (fl & 1) or not mn <= HALF_NORM_LIMIT:
+                    self._scale = scale0
+                    self._max_norm.copy_(mn0)
+                    raise _lib.ConvdrError("FlatIPIndex(storage='fp16').add: %s; the index is unchanged (%d rows)"
+                                           % ("a value is not finite as a half" if fl & 1 else
+                                              "a row's norm %g exceeds %g" % (mn, HALF_NORM_LIMIT), n0))
+                if not (fl & 2):
+                    break
+                if attempt:
+                    raise _lib.ConvdrError("half store: scaled values overflow at scale %g, max norm %g" % (self._scale, mn))
+                self._rebuild_scaled()          # the scale that fits the new max norm; rows [0, n0) rescaled in place
+            self._n = n0 + m
+
+    def _half_stream(self, arr, p16, chunk_bytes, reader, first):
+        """_add_host_streamed for float16 rows: the same pinned staging buffers viewed as halves (twice the rows per chunk),
+        the copy stream writes straight into the store and convdr_ip_store_rows_f16 scales each chunk in place."""
+        import time
+        import torch
+        n, d = arr.shape
+        rows32 = max(1, int(chunk_bytes) // (4 * d))
+        rows_per = 2 * rows32
+        nbuf = max(2, int(self.host_stage_buffers))
+        t0 = time.perf_counter()
+        main = torch.cuda.current_stream()
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        stage32, freed = _staging(self.device, min(rows32, (n + 1) // 2), d, nbuf)
+        stage = [b.view(torch.float16).view(-1, d) for b in stage32]
+        cs = self._copy_stream
+        cs.wait_stream(main)
+        avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        threads = max(1, min(int(self.host_copy_threads), avail))
+        pool = _copy_pool(threads * (nbuf - 1), self.device)
+        chunks = [(s, min(n, s + rows_per)) for s in range(0, n, rows_per)]
+
+        def fill(ci):
+            s, e = chunks[ci]
+            bi = ci % nbuf
+            if freed[bi] is not None:           # (see _add_host_streamed: the events live with the buffers)
+                freed[bi].synchronize()
+            dst = stage[bi].numpy()[:e - s]
+            if reader is not None:
+                return reader(dst, s, e, pool=pool, parts=threads, wait=False)
+            step = (e - s + threads - 1) // threads
+            return [pool.submit(np.copyto, dst[a:a + step], arr[s + a:min(e, s + a + step)]) for a in range(0, e - s, step)]
+        inflight = {ci: fill(ci) for ci in range(min(nbuf - 1, len(chunks)))}
+        for ci, (s, e) in enumerate(chunks):
+            for f in inflight.pop(ci):
+                f.result()
+            bi = ci % nbuf
+            with torch.cuda.stream(cs):
+                p16[s:e].copy_(stage[bi][:e - s], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(cs)
+            freed[bi] = ev
+            main.wait_event(ev)
+            if ci + nbuf - 1 < len(chunks):
+                inflight[ci + nbuf - 1] = fill(ci + nbuf - 1)
+            if first and ci == 0:
+                self._half_first_scale(p16[s:e])
+            self._store_rows(p16[s:e], p16[s:e], self._scale)
+        self.stats["add_host_s"] = time.perf_counter() - t0
+        self.stats["add_host_bytes"] = n * d * 2
 
     def _pad_columns(self, x):
         import torch
@@ -331,7 +529,7 @@ class FlatIPIndex:
     def _ensure_lo(self):
         """Remainder copy for the split scan, built on first use."""
         import torch
-        if self._slo is None and self._s32 is not None:
+        if not self._half and self._slo is None and self._s32 is not None:
             with torch.cuda.device(self.device):
                 self._slo = torch.empty((self._s32.shape[0], self.d), dtype=self._half_dtype, device=self.device)
                 if self._n:
@@ -343,6 +541,13 @@ class FlatIPIndex:
         import torch
         m = int(emb.shape[0])
         assert emb.dtype == torch.float32 and emb.is_contiguous() and row0 + m <= self.ntotal
+        if self._half:
+            # the new rows are rounded to half and scaled; a row the store cannot hold is an error AFTER the write (the caller
+            # owns the rows it overwrites), a scale the rows outgrow is CONVDR_IP_RANGE at the next search, as for add()
+            src = emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))
+            with torch.cuda.device(self.device):
+                self._store_rows(src.contiguous(), self._pbf[row0:row0 + m], self._scale, flags=self._uflags)
+            return
         dst32, dstbf = self._p32[row0:row0 + m], self._pbf[row0:row0 + m]
         dstlo = None if self._slo is None else self._plo[row0:row0 + m]
         dst32[:, :self.d_in].copy_(emb)      # (zero columns of a padded width stay zero)
@@ -355,9 +560,14 @@ class FlatIPIndex:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry):
+    def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False):
         L = _lib.lib()
-        if self.kind == "f16":
+        if self._half:
+            _lib.check(L.convdr_ip_search_h16(_lib.ptr(q), nq, _lib.ptr(p16), float(self._scale), int(bool(split)), n, self.d, k,
+                                              _lib.ptr(self._max_norm), _lib.ptr(tau_in), cap, rank_target, _lib.ptr(ws),
+                                              ws.numel(), _lib.ptr(D), _lib.ptr(I), _lib.ptr(status), _lib.ptr(tau_retry),
+                                              _lib.stream_ptr()), "convdr_ip_search_h16")
+        elif self.kind == "f16":
             _lib.check(L.convdr_ip_search_f16(_lib.ptr(q), nq, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo), float(self._scale), n,
                                               self.d, k, _lib.ptr(self._max_norm), _lib.ptr(tau_in), cap, rank_target,
                                               _lib.ptr(ws), ws.numel(), _lib.ptr(D), _lib.ptr(I), _lib.ptr(status),
@@ -382,7 +592,7 @@ class FlatIPIndex:
         while cap < 2 * k and cap < 8192:      # the candidate list holds at least 2k entries (csrc/ip_topk.hip: k <= cap / 2)
             cap *= 2
         if x3 is None:
-            x3 = self.precision in ("bf16x3", "fp16x3")
+            x3 = self.precision in _SPLIT
         if x3:
             self._ensure_lo()
         nq, n = int(q.shape[0]), self.ntotal
@@ -392,11 +602,11 @@ class FlatIPIndex:
         tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
         need = L.convdr_ip_workspace_bytes(nq, n, self.d, k, cap)
         ws = self._workspace(need)
-        p32 = self._p32 if n else q  # never dereferenced when n == 0
+        p32 = self._rows if n else q  # never dereferenced when n == 0
         pbf = self._pbf if n else q
         plo = self._plo if (x3 and n) else None
         with torch.cuda.device(self.device):
-            self._search_call(q, nq, p32, pbf, plo, n, k, tau_in, cap, self.rank_target, ws, D, I, status, tau_retry)
+            self._search_call(q, nq, p32, pbf, plo, n, k, tau_in, cap, self.rank_target, ws, D, I, status, tau_retry, split=x3)
         return D, I, status, tau_retry
 
     def last_counts(self, nq, k, cap=None):
@@ -463,7 +673,7 @@ class FlatIPIndex:
             # the reference takes any --top_n (run_convdr_inference.py:316-319); the deep kernel pipeline's candidate lists end
             # at 131,072 entries, so larger k takes the chunked host-side route (exact, slow): see _search_large_k
             return (qt, k, None, None, None, None, None)
-        x3 = self.precision in ("bf16x3", "fp16x3") or (self.precision == "auto" and getattr(self, "_x3_first", False) and self.ntotal > 0)
+        x3 = self.precision in _SPLIT or (self.precision == "auto" and getattr(self, "_x3_first", False) and self.ntotal > 0)
         if k > self.MAX_K:
             # 4096 < k <= 65536: the same pipeline with the lists in global memory (convdr_ip_search_deep*)
             cap = self._deep_cap(k)
@@ -479,6 +689,7 @@ class FlatIPIndex:
         if x3 is None:
             self.stats = {"retried": 0, "rounds": 0, "x3_queries": 0, "x3_first": False, "rescaled": 0, "large_k": k,
                           "deep": 0, "deep_cap": 0, "chunked_queries": int(qt.shape[0])}
+            self.stats[self._split_key] = 0
             return self._search_large_k(qt, k)
         nq = int(qt.shape[0])
         rescaled = 0
@@ -488,8 +699,9 @@ class FlatIPIndex:
             rescaled = 1
             D, I, status, tau_retry = self.search_device(qt, k, x3=x3)
             n_bad = int((status != 0).sum().item())
-        self.stats = {"retried": int(n_bad), "rounds": 1, "x3_queries": nq if x3 else 0, "x3_first": bool(x3),
-                      "rescaled": rescaled}
+        split_key = self._split_key
+        self.stats = {"retried": int(n_bad), "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": rescaled}
+        self.stats[split_key] = nq if x3 else 0
         bad = []
         if self.stats["retried"]:
             if self.precision == "auto" and not x3:
@@ -513,14 +725,14 @@ class FlatIPIndex:
             # second rung: split scan for the queries the single-pass error band cannot separate
             idx = torch.as_tensor(bad, device=self.device)
             qs = qt[idx].contiguous()
-            self.stats["x3_queries"] = len(bad)
+            self.stats[split_key] = len(bad)
             Db, Ib, sb, tb = self.search_device(qs, k, x3=True)
             self.stats["rounds"] += 1
             bad2 = self._certify(qs, k, Db, Ib, sb, tb, True) if int((sb != 0).sum().item()) else []
             D[idx], I[idx] = Db, Ib
             bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
         if self.precision == "auto":
-            self._x3_first = self.stats["x3_queries"] > nq // 2
+            self._x3_first = self.stats[split_key] > nq // 2
         if len(bad):
             # last rung: more than 8192 passages inside the error band of the k-th score even with the split scan
             # (blocks whose norms spread over orders of magnitude: eps scales with the LARGEST norm).  Every slice of
@@ -594,6 +806,11 @@ class FlatIPIndex:
             todo = sub if todo is None else todo[sub]
             m = min(2 * m, limit)
 
+    @property
+    def _split_key(self):
+        """stats key that counts the queries of the second rung: the three-pass split scan, or the half store's two passes"""
+        return "x2_queries" if self._half else "x3_queries"
+
     MAX_K = 4096         # convdr_ip_search: k <= cap / 2, cap <= 8192
     DEEP_MAX_K = 65536   # convdr_ip_search_deep: k <= cap / 2, cap <= 131072
     DEEP_MIN_CAP, DEEP_MAX_CAP = 16384, 131072
@@ -634,7 +851,7 @@ class FlatIPIndex:
             raise _lib.ConvdrError("convdr_ip_search_deep: sizes outside the contract (nq=%d n=%d d=%d k=%d cap=%d)"
                                    % (nq, n, self.d, k, cap))
         ws = self._workspace(need)
-        p32 = self._p32 if n else q     # never dereferenced when n == 0
+        p32 = self._rows if n else q    # never dereferenced when n == 0
         p16 = self._pbf if n else q
         plo = self._plo if (x3 and n) else None
         with torch.cuda.device(self.device):
@@ -644,7 +861,10 @@ class FlatIPIndex:
                 args = (b - a, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo))
                 tail = (n, self.d, k, _lib.ptr(self._max_norm), _lib.ptr(tin), cap, self.rank_target, _lib.ptr(ws), ws.numel(),
                         _lib.ptr(D[a:b]), _lib.ptr(I[a:b]), _lib.ptr(status[a:b]), _lib.ptr(tau_retry[a:b]), _lib.stream_ptr())
-                if self.kind == "f16":
+                if self._half:
+                    _lib.check(L.convdr_ip_search_deep_h16(_lib.ptr(q[a:b]), b - a, _lib.ptr(p16), float(self._scale),
+                                                           int(bool(x3)), *tail), "convdr_ip_search_deep_h16")
+                elif self.kind == "f16":
                     _lib.check(L.convdr_ip_search_deep_f16(_lib.ptr(q[a:b]), *args, float(self._scale), *tail),
                                "convdr_ip_search_deep_f16")
                 else:
@@ -680,8 +900,10 @@ class FlatIPIndex:
         with tau_retry / a doubled list -> split scan -> whatever is still open goes to _search_large_k."""
         import torch
         nq = int(qt.shape[0])
-        self.stats = {"retried": 0, "rounds": 1, "x3_queries": nq if x3 else 0, "x3_first": bool(x3), "rescaled": 0, "large_k": k,
+        split_key = self._split_key
+        self.stats = {"retried": 0, "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": 0, "large_k": k,
                       "deep": nq, "deep_cap": cap, "chunked_queries": 0}
+        self.stats[split_key] = nq if x3 else 0
         if D is None:                   # empty index: FAISS padding
             return (torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device),
                     torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
@@ -696,14 +918,14 @@ class FlatIPIndex:
         if len(bad) and self.precision == "auto" and not x3:
             idx = torch.as_tensor(bad, device=self.device)
             qs = qt[idx].contiguous()
-            self.stats["x3_queries"] = len(bad)
+            self.stats[split_key] = len(bad)
             Db, Ib, sb, tb = self.search_deep_device(qs, k, cap=cap, x3=True)
             self.stats["rounds"] += 1
             bad2 = self._certify_deep(qs, k, Db, Ib, sb, tb, True, cap) if int((sb != 0).sum().item()) else []
             D[idx], I[idx] = Db, Ib
             bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
         if self.precision == "auto":
-            self._x3_first = self.stats["x3_queries"] > nq // 2
+            self._x3_first = self.stats[split_key] > nq // 2
         if len(bad):
             idx = torch.as_tensor(np.asarray(bad, dtype=np.int64), device=self.device)
             Db, Ib = self._search_large_k(qt[idx].contiguous(), k)
@@ -745,7 +967,7 @@ class FlatIPIndex:
                 Ds, Is = [], []
                 for s0 in range(0, n, step):
                     m = min(n, s0 + step) - s0
-                    D, I = exact(self._p32[s0:s0 + m], self._pbf[s0:s0 + m], m, m, qq)
+                    D, I = exact(self._rows[s0:s0 + m], self._pbf[s0:s0 + m], m, m, qq)
                     Ds.append(D)
                     Is.append(I + s0)
                 Dall, Iall = torch.cat(Ds, 1), torch.cat(Is, 1)
@@ -767,7 +989,7 @@ class FlatIPIndex:
                             raise _lib.ConvdrError("FlatIPIndex.search: %d passages share one fp32 score around rank %d; "
                                                    "k > %d cannot order a tie group that large" % (ln, b, self.MAX_K))
                         rows = torch.sort(i[b:b + ln]).values
-                        Dj, Ij = exact(self._p32[rows].contiguous(), self._pbf[rows].contiguous(), ln, ln, qq[j:j + 1].contiguous())
+                        Dj, Ij = exact(*self._row_pair(rows), ln, ln, qq[j:j + 1].contiguous())
                         d[b:b + ln], i[b:b + ln] = Dj[0], rows[Ij[0]]
                     Dout[j0 + j, :kk], Iout[j0 + j, :kk] = d[:kk], i[:kk]
         return Dout, Iout
@@ -797,7 +1019,7 @@ class FlatIPIndex:
         with torch.cuda.device(self.device):
             for s0 in range(0, n, step):
                 e0 = min(n, s0 + step)
-                D, I = exact(self._p32[s0:e0], self._pbf[s0:e0], e0 - s0, kk, q)
+                D, I = exact(self._rows[s0:e0], self._pbf[s0:e0], e0 - s0, kk, q)
                 I = torch.where(I >= 0, I + s0, I)
                 merged = (D, I) if merged is None else tuple(t[:, :kk].contiguous() for t in merge_topk_device(merged, (D, I), kk))
             # The merges compare the fp32-rounded scores; the result's order is defined on the canonical fp64 scores (two
@@ -813,7 +1035,7 @@ class FlatIPIndex:
                     Dout[j] = -3.4028234663852886e38
                     Iout[j] = -1
                     continue
-                Dj, Ij = exact(self._p32[rows].contiguous(), self._pbf[rows].contiguous(), m, k, q[j:j + 1].contiguous())
+                Dj, Ij = exact(*self._row_pair(rows), m, k, q[j:j + 1].contiguous())
                 Dout[j] = Dj[0]
                 Iout[j] = torch.where(Ij[0] >= 0, rows[Ij[0].clamp_min(0)], Ij[0])
         return Dout, Iout

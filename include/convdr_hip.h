@@ -136,6 +136,44 @@ int convdr_ip_search_deep_f16(const float* q_f32, int nq, const float* p_f32, co
                               int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
                               int32_t* status, float* tau_retry, convdr_stream_t stream);
 
+/* Half-precision passage store: the passage is stored ONCE, in 16 bits, and that copy is both the corpus and the scan
+ * operand (1,536 bytes per passage at d = 768 instead of 3,072 fp32 + 1,536 scan copy, + 1,536 for the split rung).
+ *   corpus    THE STORED HALVES.  Built from float16 rows (kept bit for bit) or from fp32 rows rounded to nearest even once
+ *             (numpy.astype(float16), torch.half()); from then on the corpus is those halves widened exactly to fp32.
+ *   result    what the fp32 entries return for that widened corpus, bit for bit: canonical fp64 summation order, ranking by
+ *             (score desc, index asc), D = the fp64 score rounded to fp32, padding -FLT_MAX / -1.
+ *   scaling   the resident copy is 2^s v for the stored half v, s >= 0 (p_scale = 2^s >= 1; convdr_ip_f16_scale of the
+ *             first rows' largest norm, clamped to >= 1).  Scaling a half up by a power of two is exact, subnormals included,
+ *             unless it overflows, so the copy is literally an un-centred fp16 scan copy and scan, thresholds (scaled
+ *             units) and certificate are those of convdr_ip_search_f16 with this p_scale.  The re-score sums
+ *             q . (2^s v) in fp64 and multiplies once by 2^-s: every fp64 step scales exactly, the value is the oracle's.
+ *   no centre the store is what it is: eps carries max|p|, not max|p - centre|.
+ *
+ * convdr_ip_store_rows_f16: src = n rows of halves (src_is_f32 = 0) or of fp32 (rounded here); store[i] = half * scale;
+ * the rows' UNSCALED norms are folded into *max_norm (nullable).  *flags (device int32, the caller zeroes it) is OR-ed with
+ *   1  a value is not finite (after rounding to half)
+ *   2  a scaled value overflowed, or store / scale != half
+ * store == NULL: norms and flag 1 only.  store == src (halves): the in-place rescale after CONVDR_IP_RANGE by the factor
+ * scale = 2^(s_new - s_old) <= 1 with s_new >= 0 -- the only form that takes a scale below 1.  d % 64 == 0, scale a power
+ * of two; arguments are validated before anything touches a device. */
+int convdr_ip_store_rows_f16(const void* src, int src_is_f32, int64_t n, int d, float scale, void* store, float* max_norm,
+                             int32_t* flags, convdr_stream_t stream);
+/* convdr_ip_search_f16 over a half store (workspace: convdr_ip_workspace_bytes).  two_pass = 0: the single-pass fp16 scan
+ * with today's fp16 eps (it bounds a superset of the errors: the passage operand carries none).  two_pass = 1: the second
+ * rung S~ = P Qh + P Ql -- two MFMA passes, no remainder copy -- with the split scan's eps (3 u^2 (1 + 2u) + 3 d 2^-23,
+ * u = 2^-11; every term of the two-pass error is majorised by the corresponding term of the three-pass bound).
+ * p_scale: a power of two >= 1, the scale the store was built with.  Status words, tau_retry and convdr_ip_debug_* as for
+ * convdr_ip_search_f16; both settings of the option ip_fused_finish work. */
+int convdr_ip_search_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n, int d,
+                         int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
+                         size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream);
+/* The same with deep candidate lists: the contract of convdr_ip_search_deep_f16 (workspace: convdr_ip_deep_workspace_bytes,
+ * cap a power of two in [16384, 131072], k <= cap / 2, n < 2^31). */
+int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n, int d,
+                              int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
+                              size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                              convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
