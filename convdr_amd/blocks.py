@@ -227,7 +227,7 @@ class BlockView:
         step = (total // parts + 4095) // 4096 * 4096
         futs = [pool.submit(rd, a, min(total, a + step)) for a in range(0, total, step)]
         if not wait:
-            return futs          # (the caller joins them: several chunks' reads in flight, FlatIPIndex._add_host_streamed)
+            return futs          # (the caller joins them: several chunks' reads in flight, FlatIPIndex._stream_rows)
         for f in futs:
             f.result()
         return []

@@ -203,9 +203,6 @@ def count_blocks(ann_data_dir, max_blocks=8):
     return B
 
 
-_FAISS_PAD_SCORE = -3.4028234663852886e38     # what IndexFlatIP.search returns beside id -1 when a block has < k rows
-
-
 def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, group=None, timings=None, max_depth=None):
     """search.search_one_by_one over ANY number of block files with ANY number of ranks: every rank searches the blocks
     plan_block_shards gives it, the per-rank top-topN lists are exchanged once (exchange_topk) and merged.
@@ -259,7 +256,7 @@ def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, grou
     tm = {"load_add_s": 0.0, "search_finish_merge_s": 0.0, "blocks": 0, "bytes": 0}
     merged = S._search_block_list(ann_data_dir, index, queries, topN, mine, False, tm) if mine else None
     if merged is None:
-        D = torch.full((nq, topN), _FAISS_PAD_SCORE, dtype=torch.float32, device=dev)
+        D = torch.full((nq, topN), S.PAD_SCORE, dtype=torch.float32, device=dev)
         ids = torch.full((nq, topN), -1, dtype=torch.int64, device=dev)
     elif on_device:
         D, ids = merged[0][:, :topN].contiguous(), merged[1][:, :topN].contiguous()
@@ -289,31 +286,20 @@ def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_
     max_depth (default FlatIPIndex.MAX_K = 4096, at most DEEP_MAX_K = 65536) bounds m and is passed on to
     search_blocks_sharded: TREC depth 1,000 over documents of five chunks is m = 5,000.
     Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy."""
-    import numpy as np
-    from . import _lib, blocks
+    from . import blocks
     from . import search as S
     topN = int(topN)
     if rows_per_key is None:
         rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
     rows_per_key = int(rows_per_key)
-    m = topN * rows_per_key
     limit = 4096 if max_depth is None else S._check_max_depth("search_blocks_sharded_distinct", max_depth)
-    if topN < 1 or rows_per_key < 1 or m > limit:
-        raise ValueError("search_blocks_sharded_distinct: topN * rows_per_key = %d * %d = %d is outside 1..%d "
-                         "(%s)" % (topN, rows_per_key, m, limit, "FlatIPIndex.MAX_K" if max_depth is None else "max_depth"))
+    m = S._distinct_row_depth("search_blocks_sharded_distinct", topN, rows_per_key, limit,
+                              "FlatIPIndex.MAX_K" if max_depth is None else "max_depth")
     Dm, Im = search_blocks_sharded(ann_data_dir, index, queries, m, max_blocks=max_blocks, group=group, timings=timings,
                                    max_depth=max_depth)
     km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else key_map
     D, I, _, counts = S.distinct_topk(Dm[:, :m], Im[:, :m], topN, km)
-    if (counts[:, 0] < 0).any():
-        raise _lib.ConvdrError("search_blocks_sharded_distinct: a record offset lies outside key_map (%d entries)" % len(km))
-    open_ = np.nonzero((counts[:, 0] < topN) & (counts[:, 1] >= m))[0]
-    if len(open_):
-        most, total = blocks.key_row_stats(ann_data_dir, max_blocks, key_map)
-        if total > m:
-            raise _lib.ConvdrError("search_blocks_sharded_distinct: %d queries hold fewer than %d keys in their top %d rows: "
-                                   "rows_per_key = %d is understated (the id files give %d)"
-                                   % (len(open_), topN, m, rows_per_key, most))
+    S._check_distinct_certificate("search_blocks_sharded_distinct", counts, topN, m, rows_per_key, ann_data_dir, max_blocks, key_map)
     return D, I
 
 

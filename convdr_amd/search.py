@@ -11,6 +11,7 @@ Mirrors, name for name, what the reference does with FAISS:
                                results for blocks whose rows repeat a key (MaxP chunk rows, duplicate pids)
 All scoring / selection runs in libconvdr_hip.so (csrc/ip_topk.hip).
 """
+import collections
 import json
 import os
 import pickle
@@ -26,11 +27,18 @@ def _torch():
 
 
 STATUS_OK, STATUS_OVERFLOW, STATUS_TOO_FEW, STATUS_UNCERTAIN, STATUS_RANGE = 0, 1, 2, 3, 4
+PAD_SCORE = -3.4028234663852886e38      # what IndexFlatIP.search returns beside id -1
 
 _KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16"}
 _SPLIT = ("bf16x3", "fp16x3", "fp16x2")          # precisions that pin the second rung
 _HALF_PRECISIONS = ("auto", "fp16", "fp16x2")    # the rungs of a half store (storage="fp16")
 HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM_LIMIT
+
+
+_Depth = collections.namedtuple("_Depth", "enqueue max_cap shortcut last_rung last_stat deep_stats")
+# what search_begin hands to search_finish: depth None = k > DEEP_MAX_K (nothing enqueued), first = (D, I, status, tau_retry) of
+# the enqueued first pass or None (deep search of an empty index)
+_Pending = collections.namedtuple("_Pending", "qt k depth x3 cap first")
 
 
 class FlatIPIndex:
@@ -183,30 +191,20 @@ class FlatIPIndex:
         """Backing storage for n passages (fp32 block + 16-bit scan copy, + the remainder copy of the split scan when
         `lo`, default: only if the precision pins it).  Existing rows are kept."""
         import torch
-        n = int(n)
-        if self._half:
-            if self._s16 is None or self._s16.shape[0] < n:
-                with torch.cuda.device(self.device):
-                    t = torch.empty((n, self.d), dtype=torch.float16, device=self.device)
-                    if self._s16 is not None and self._n:
-                        t[:self._n].copy_(self._s16[:self._n])
-                    self._s16 = t
-            self._reserved = True
-            return
-        want_lo = (self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)
-        if self._s32 is not None and self._s32.shape[0] >= n and (self._slo is not None or not want_lo):
-            self._reserved = True
-            return
+        held = {"_s16": self._half_dtype}          # the buffers this index holds: a half store keeps its 16-bit rows and nothing else
+        if not self._half:
+            held["_s32"] = torch.float32
+            if self._slo is not None or ((self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)):
+                held["_slo"] = self._half_dtype
+        rows = max(int(n), 0 if self._s16 is None else self._s16.shape[0])      # (all of them keep one row count)
         with torch.cuda.device(self.device):
-            def grow(old, dtype):
-                t = torch.empty((n, self.d), dtype=dtype, device=self.device)
-                if old is not None and self._n:
-                    t[:self._n].copy_(old[:self._n])
-                return t
-            self._s32 = grow(self._s32, torch.float32)
-            self._s16 = grow(self._s16, self._half_dtype)
-            if want_lo or self._slo is not None:
-                self._slo = grow(self._slo, self._half_dtype)
+            for name, dtype in held.items():
+                old = getattr(self, name)
+                if old is None or old.shape[0] < rows:
+                    t = torch.empty((rows, self.d), dtype=dtype, device=self.device)
+                    if old is not None and self._n:
+                        t[:self._n].copy_(old[:self._n])
+                    setattr(self, name, t)
         self._reserved = True
 
     def _prepare_into(self, src32, dst16, dstlo):
@@ -252,15 +250,47 @@ class FlatIPIndex:
             if self._n:
                 self._prepare_into(self._p32, self._pbf, self._plo)
 
-    def _grow_for(self, m, want_lo):
-        """rows [n, n + m) of the backing storage, growing it when needed (exact fit unless reserved larger)"""
+    def _grow_for(self, m, want_lo=False):
+        """rows [n, n + m) of the backing storage (fp32 block, scan copy, remainder copy; None for a buffer the index does not
+        hold), growing it when needed (exact fit unless reserved larger)"""
         need = self._n + m
-        if self._s32 is None or self._s32.shape[0] < need or (want_lo and self._slo is None):
+        if self._s16 is None or self._s16.shape[0] < need or (want_lo and self._slo is None):
             keep = getattr(self, "_reserved", False)
-            self.reserve(need, lo=want_lo or self._slo is not None)
+            self.reserve(need, lo=want_lo)
             self._reserved = keep
-        a, b = self._n, need
-        return self._s32[a:b], self._s16[a:b], (self._slo[a:b] if self._slo is not None else None)
+        return tuple(None if t is None else t[self._n:need] for t in (self._s32, self._s16, self._slo))
+
+    def _source(self, x, chunk_bytes, np_dtype, keep):
+        """What add() was given, normalised.  (host array, reader) when it is to be streamed: a `np_dtype` [n, d] array of more
+        than chunk_bytes // 2 that is a numpy array, a pageable CPU tensor (of keep[0], np_dtype's torch name) or the payload
+        of a blocks.BlockView (reader: its positioned reads from the file).  Otherwise (contiguous device tensor [n, d], None);
+        dtypes outside `keep` become fp32."""
+        import torch
+        if self.d != self.d_in:
+            x = self._pad_columns(x.array if hasattr(x, "array") else x)
+        reader = None
+        if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView
+            reader, x = x.read_rows_into, x.array
+        arr = x
+        if isinstance(x, torch.Tensor) and x.device.type == "cpu" and not x.is_pinned() and x.dtype == keep[0]:
+            arr = x.numpy()
+        if isinstance(arr, np.ndarray) and arr.dtype == np_dtype and arr.ndim == 2 and arr.nbytes > chunk_bytes // 2:
+            assert arr.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, arr.shape)
+            return arr, reader
+        from_host = not (isinstance(x, torch.Tensor) and x.is_cuda)
+        if isinstance(x, np.ndarray) and not x.flags.writeable:
+            # a read-only array (the mmap of a small block file): torch.as_tensor would alias it without knowing it must
+            # never write (a UserWarning today, undefined behaviour the day someone does) -- small by construction (large
+            # host blocks are streamed), so it is copied first
+            x = np.array(x, order="C")
+        t = torch.as_tensor(x)
+        if t.dtype not in keep:
+            t = t.float()
+        # (a host source that is not pinned -- e.g. the mmap of a small block file, which search_one_by_one closes right
+        #  after add() returns -- is copied synchronously: nothing may still be reading it when add() is back)
+        t = t.to(self.device, non_blocking=not from_host or t.is_pinned()).contiguous()
+        assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
+        return t, None
 
     def add(self, x, chunk_bytes=None):
         """x: numpy / torch [n, d] float32 (host or device).  Appends to the index.
@@ -269,50 +299,42 @@ class FlatIPIndex:
         centring / rounding / norm pass of chunk i (convdr_ip_prepare_block*), and the host fills one staging buffer
         (page faults on the mmap = the disk read) while the others are in flight.  The reference does pickle.load (a full
         host copy of the 14.6 GB block) and a pageable copy (run_convdr_inference.py:164-180)."""
+        import time
         import torch
         chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
         if self._half:
             return self._add_half(x, chunk_bytes)
-        if self.d != self.d_in:
-            x = self._pad_columns(x.array if hasattr(x, "array") else x)
-        if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView: positioned reads from the file
-            arr = x.array
-            if arr.dtype == np.float32 and arr.ndim == 2 and arr.nbytes > chunk_bytes // 2:
-                return self._add_host_streamed(arr, chunk_bytes, reader=x.read_rows_into)
-            x = arr
-        if isinstance(x, np.ndarray) or (isinstance(x, torch.Tensor) and x.device.type == "cpu" and not x.is_pinned()):
-            arr = x if isinstance(x, np.ndarray) else x.numpy()
-            if arr.dtype == np.float32 and arr.ndim == 2 and arr.shape[0] * arr.shape[1] * 4 > chunk_bytes // 2:
-                return self._add_host_streamed(arr, chunk_bytes)
-        from_host = not (isinstance(x, torch.Tensor) and x.is_cuda)
-        if isinstance(x, np.ndarray) and not x.flags.writeable:
-            # a read-only array (the mmap of a small block file): torch.as_tensor would alias it without knowing it must
-            # never write (a UserWarning today, undefined behaviour the day someone does) -- small by construction (large
-            # host blocks took the streamed path above), so it is copied first
-            x = np.array(x, dtype=np.float32, order="C")
-        t = torch.as_tensor(x)
-        if t.dtype != torch.float32:
-            t = t.float()
-        # (a host source that is not pinned -- e.g. the mmap of a small block file, which search_one_by_one closes right
-        #  after add() returns -- is copied synchronously: nothing may still be reading it when add() is back)
-        t = t.to(self.device, non_blocking=not from_host or t.is_pinned()).contiguous()
-        assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
+        t, reader = self._source(x, chunk_bytes, np.float32, (torch.float32,))
         m = int(t.shape[0])
         if m == 0:
             return
         want_lo = self.precision in ("bf16x3", "fp16x3") or self._slo is not None
         with torch.cuda.device(self.device):
-            if self._n == 0:
-                self._first_rows(t)
-            if self._s32 is None and not want_lo:
-                # first block of an unreserved index: adopt the caller's device tensor instead of copying it
-                self._s32 = t
-                self._s16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
-                dst32, dst16, dstlo = self._s32, self._s16, None
+            if isinstance(t, np.ndarray):
+                t0 = time.perf_counter()
+                p32, p16, plo = self._grow_for(m, want_lo)
+                first = self._n == 0
+
+                def prepare(ci, s, e):
+                    if first and ci == 0:
+                        # centre = column mean of the first chunk (>= 40 k passages): any centre keeps the search exact -- it
+                        # shifts every score of a query by the same constant -- it only has to be close to the mean to shrink
+                        # the rounding-error band; likewise the fp16 scale comes from the first chunk's norms
+                        self._first_rows(p32[s:e])
+                    self._prepare_into(p32[s:e], p16[s:e], plo[s:e] if plo is not None else None)
+                self._stream_rows(t, p32, reader, chunk_bytes, prepare, t0)
             else:
-                dst32, dst16, dstlo = self._grow_for(m, want_lo)
-                dst32.copy_(t)
-            self._prepare_into(dst32, dst16, dstlo)
+                if self._n == 0:
+                    self._first_rows(t)
+                if self._s32 is None and not want_lo:
+                    # first block of an unreserved index: adopt the caller's device tensor instead of copying it
+                    self._s32 = t
+                    self._s16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
+                    dst32, dst16, dstlo = self._s32, self._s16, None
+                else:
+                    dst32, dst16, dstlo = self._grow_for(m, want_lo)
+                    dst32.copy_(t)
+                self._prepare_into(dst32, dst16, dstlo)
         self._n += m
 
     # -- the half store (storage="fp16") ----------------------------------------
@@ -334,52 +356,32 @@ class FlatIPIndex:
         self._store_rows(src, None, 1.0)
         self._scale = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
 
-    def _half_grow(self, m):
-        need = self._n + m
-        if self._s16 is None or self._s16.shape[0] < need:
-            keep = getattr(self, "_reserved", False)
-            self.reserve(need)
-            self._reserved = keep
-        return self._s16[self._n:need]
-
     def _add_half(self, x, chunk_bytes):
         """add() of a half store.  `write(dst)` below puts the new rows into dst = store[n, n + m) (rounded, scaled, norms
         and flags folded); the flag word and the max norm are read ONCE, at the end, and decide: keep, refuse (the index is
         left exactly as it was), or -- a scaled value overflowed: the new rows are too long for the scale -- lower the scale,
         rescale the resident rows in place and write the new rows once more (the only case with a second read)."""
         import torch
-        if self.d != self.d_in:
-            x = self._pad_columns(x.array if hasattr(x, "array") else x)
-        reader = None
-        if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView
-            reader, x = x.read_rows_into, x.array
-        if isinstance(x, torch.Tensor) and x.device.type == "cpu" and not x.is_pinned() and x.dtype == torch.float16:
-            x = x.numpy()
-        if isinstance(x, np.ndarray) and x.dtype == np.float16 and x.ndim == 2 and x.nbytes > chunk_bytes // 2:
-            assert x.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, x.shape)
-            m, arr = int(x.shape[0]), x
-            write = lambda dst, first: self._half_stream(arr, dst, chunk_bytes, reader, first)
-        else:
-            from_host = not (isinstance(x, torch.Tensor) and x.is_cuda)
-            if isinstance(x, np.ndarray) and not x.flags.writeable:
-                x = np.array(x, order="C")              # (see add(): a read-only mapping is never aliased)
-            t = torch.as_tensor(x)
-            if t.dtype not in (torch.float16, torch.float32):
-                t = t.float()
-            t = t.to(self.device, non_blocking=not from_host or t.is_pinned()).contiguous()
-            assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
-            m = int(t.shape[0])
+        t, reader = self._source(x, chunk_bytes, np.float16, (torch.float16, torch.float32))
+        m = int(t.shape[0])
 
-            def write(dst, first):
+        def write(dst, first):
+            if not isinstance(t, np.ndarray):
                 if first:
                     self._half_first_scale(t)
-                self._store_rows(t, dst, self._scale)
+                return self._store_rows(t, dst, self._scale)
+
+            def scale_in_place(ci, s, e):       # the copy stream wrote the halves straight into the store
+                if first and ci == 0:
+                    self._half_first_scale(dst[s:e])
+                self._store_rows(dst[s:e], dst[s:e], self._scale)
+            self._stream_rows(t, dst, reader, chunk_bytes, scale_in_place)
         if m == 0:
             return
         n0, scale0 = self._n, self._scale
         with torch.cuda.device(self.device):
             mn0 = self._max_norm.clone()
-            dst = self._half_grow(m)
+            dst = self._grow_for(m)[1]
             for attempt in (0, 1):
                 write(dst, n0 == 0 and attempt == 0)
                 got = self._mf[:2].cpu()                                    # the one host read of this add()
@@ -398,56 +400,64 @@ class FlatIPIndex:
                 self._rebuild_scaled()          # the scale that fits the new max norm; rows [0, n0) rescaled in place
             self._n = n0 + m
 
-    def _half_stream(self, arr, p16, chunk_bytes, reader, first):
-        """_add_host_streamed for float16 rows: the same pinned staging buffers viewed as halves (twice the rows per chunk),
-        the copy stream writes straight into the store and convdr_ip_store_rows_f16 scales each chunk in place."""
+    def _stream_rows(self, arr, dst, reader, chunk_bytes, each, t0=None):
+        """Host rows `arr` -> device rows `dst` (same shape and element type) through the pinned staging buffers -- viewed as
+        dst's element type, so a buffer holds twice the rows of halves -- with the H2D copies on the copy stream; each(ci, s, e)
+        is called on the main stream's side once chunk ci = rows [s, e) is ordered before it (its copy enqueued and waited
+        for by the main stream).  reader: a BlockView's positioned reads instead of slices of `arr`.  t0: when the add()
+        began to enqueue, for `stats["add_host_s"]` (default: now)."""
         import time
         import torch
         n, d = arr.shape
-        rows32 = max(1, int(chunk_bytes) // (4 * d))
-        rows_per = 2 * rows32
+        t0 = time.perf_counter() if t0 is None else t0
+        per32 = max(1, int(chunk_bytes) // (4 * d))     # the pinned bytes per buffer, as fp32 rows
+        rows_per = per32 * 4 // dst.element_size()
         nbuf = max(2, int(self.host_stage_buffers))
-        t0 = time.perf_counter()
         main = torch.cuda.current_stream()
         if getattr(self, "_copy_stream", None) is None:
             self._copy_stream = torch.cuda.Stream(device=self.device)
-        stage32, freed = _staging(self.device, min(rows32, (n + 1) // 2), d, nbuf)
-        stage = [b.view(torch.float16).view(-1, d) for b in stage32]
+        stage, freed = _staging(self.device, min(per32, (n * dst.element_size() + 3) // 4), d, nbuf)
+        stage = [b.view(dst.dtype).view(-1, d) for b in stage]
         cs = self._copy_stream
-        cs.wait_stream(main)
+        cs.wait_stream(main)                    # (allocation order / the copy of the old rows in _grow_for)
         avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
         threads = max(1, min(int(self.host_copy_threads), avail))
         pool = _copy_pool(threads * (nbuf - 1), self.device)
         chunks = [(s, min(n, s + rows_per)) for s in range(0, n, rows_per)]
 
         def fill(ci):
+            """start filling staging buffer ci % nbuf with chunk ci: `threads` positioned reads / memcpy slices"""
             s, e = chunks[ci]
             bi = ci % nbuf
-            if freed[bi] is not None:           # (see _add_host_streamed: the events live with the buffers)
+            # staging buffer bi may be refilled once its previous H2D copy has completed.  The events live with the
+            # buffers (module-level, shared by every index of the process): the last copies of one add() are still in
+            # flight when the next add() starts filling (1 run in ~500 put rows of a second block into the first
+            # before they did, tests/test_ip_search_gpu.py::test_back_to_back_streamed_adds_keep_their_rows)
+            if freed[bi] is not None:
                 freed[bi].synchronize()
-            dst = stage[bi].numpy()[:e - s]
+            buf = stage[bi].numpy()[:e - s]
             if reader is not None:
-                return reader(dst, s, e, pool=pool, parts=threads, wait=False)
+                return reader(buf, s, e, pool=pool, parts=threads, wait=False)
             step = (e - s + threads - 1) // threads
-            return [pool.submit(np.copyto, dst[a:a + step], arr[s + a:min(e, s + a + step)]) for a in range(0, e - s, step)]
+            return [pool.submit(np.copyto, buf[a:a + step], arr[s + a:min(e, s + a + step)]) for a in range(0, e - s, step)]
         inflight = {ci: fill(ci) for ci in range(min(nbuf - 1, len(chunks)))}
         for ci, (s, e) in enumerate(chunks):
             for f in inflight.pop(ci):
                 f.result()
             bi = ci % nbuf
             with torch.cuda.stream(cs):
-                p16[s:e].copy_(stage[bi][:e - s], non_blocking=True)
+                dst[s:e].copy_(stage[bi][:e - s], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(cs)
             freed[bi] = ev
             main.wait_event(ev)
             if ci + nbuf - 1 < len(chunks):
+                # nbuf - 1 chunks are being read while this one crosses PCIe (the copy stream never waits for the host;
+                # with two buffers -- round 2 -- the reads of chunk i + 1 only started after chunk i had been enqueued)
                 inflight[ci + nbuf - 1] = fill(ci + nbuf - 1)
-            if first and ci == 0:
-                self._half_first_scale(p16[s:e])
-            self._store_rows(p16[s:e], p16[s:e], self._scale)
-        self.stats["add_host_s"] = time.perf_counter() - t0
-        self.stats["add_host_bytes"] = n * d * 2
+            each(ci, s, e)
+        self.stats["add_host_s"] = time.perf_counter() - t0     # host time to enqueue (the last chunks are still in flight)
+        self.stats["add_host_bytes"] = n * d * dst.element_size()
 
     def _pad_columns(self, x):
         import torch
@@ -462,69 +472,6 @@ class FlatIPIndex:
         scratch = torch.empty(1024 * self.d, dtype=torch.float32, device=self.device)
         _lib.check(_lib.lib().convdr_ip_column_mean(_lib.ptr(t), t.shape[0], self.d, _lib.ptr(scratch),
                                                    _lib.ptr(self._centre), _lib.stream_ptr()), "convdr_ip_column_mean")
-
-    def _add_host_streamed(self, arr, chunk_bytes, reader=None):
-        import time
-        import torch
-        n, d = arr.shape
-        assert d == self.d, "expected [n, %d], got %s" % (self.d, arr.shape)
-        rows_per = max(1, int(chunk_bytes) // (4 * d))
-        want_lo = self.precision in ("bf16x3", "fp16x3") or self._slo is not None
-        nbuf = max(2, int(self.host_stage_buffers))
-        t0 = time.perf_counter()
-        with torch.cuda.device(self.device):
-            main = torch.cuda.current_stream()
-            if getattr(self, "_copy_stream", None) is None:
-                self._copy_stream = torch.cuda.Stream(device=self.device)
-            stage, freed = _staging(self.device, min(rows_per, n), d, nbuf)
-            cs = self._copy_stream
-            p32, p16, plo = self._grow_for(n, want_lo)
-            cs.wait_stream(main)                    # (allocation order / the copy of the old rows in _grow_for)
-            avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-            threads = max(1, min(int(self.host_copy_threads), avail))
-            pool = _copy_pool(threads * (nbuf - 1), self.device)
-            chunks = [(s, min(n, s + rows_per)) for s in range(0, n, rows_per)]
-
-            def fill(ci):
-                """start filling staging buffer ci % nbuf with chunk ci: `threads` positioned reads / memcpy slices"""
-                s, e = chunks[ci]
-                bi = ci % nbuf
-                # staging buffer bi may be refilled once its previous H2D copy has completed.  The events live with the
-                # buffers (module-level, shared by every index of the process): the last copies of one add() are still in
-                # flight when the next add() starts filling (1 run in ~500 put rows of a second block into the first
-                # before they did, tests/test_ip_search_gpu.py::test_back_to_back_streamed_adds_keep_their_rows)
-                if freed[bi] is not None:
-                    freed[bi].synchronize()
-                dst = stage[bi].numpy()[:e - s]
-                if reader is not None:
-                    return reader(dst, s, e, pool=pool, parts=threads, wait=False)
-                step = (e - s + threads - 1) // threads
-                return [pool.submit(np.copyto, dst[a:a + step], arr[s + a:min(e, s + a + step)]) for a in range(0, e - s, step)]
-            first = self._n == 0
-            inflight = {ci: fill(ci) for ci in range(min(nbuf - 1, len(chunks)))}
-            for ci, (s, e) in enumerate(chunks):
-                for f in inflight.pop(ci):
-                    f.result()
-                bi = ci % nbuf
-                with torch.cuda.stream(cs):
-                    p32[s:e].copy_(stage[bi][:e - s], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(cs)
-                freed[bi] = ev
-                main.wait_event(ev)
-                if ci + nbuf - 1 < len(chunks):
-                    # nbuf - 1 chunks are being read while this one crosses PCIe (the copy stream never waits for the host;
-                    # with two buffers -- round 2 -- the reads of chunk i + 1 only started after chunk i had been enqueued)
-                    inflight[ci + nbuf - 1] = fill(ci + nbuf - 1)
-                if first and ci == 0:
-                    # centre = column mean of the first chunk (>= 40 k passages): any centre keeps the search exact -- it
-                    # shifts every score of a query by the same constant -- it only has to be close to the mean to shrink
-                    # the rounding-error band; likewise the fp16 scale comes from the first chunk's norms
-                    self._first_rows(p32[s:e])
-                self._prepare_into(p32[s:e], p16[s:e], plo[s:e] if plo is not None else None)
-            self._n += n
-        self.stats["add_host_s"] = time.perf_counter() - t0     # host time to enqueue (the last chunks are still in flight)
-        self.stats["add_host_bytes"] = n * d * 4
 
     def _ensure_lo(self):
         """Remainder copy for the split scan, built on first use."""
@@ -560,23 +507,60 @@ class FlatIPIndex:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False):
-        L = _lib.lib()
+    def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
+                     deep=False):
+        """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth."""
+        ptr = _lib.ptr
         if self._half:
-            _lib.check(L.convdr_ip_search_h16(_lib.ptr(q), nq, _lib.ptr(p16), float(self._scale), int(bool(split)), n, self.d, k,
-                                              _lib.ptr(self._max_norm), _lib.ptr(tau_in), cap, rank_target, _lib.ptr(ws),
-                                              ws.numel(), _lib.ptr(D), _lib.ptr(I), _lib.ptr(status), _lib.ptr(tau_retry),
-                                              _lib.stream_ptr()), "convdr_ip_search_h16")
+            name, rows = "_h16", (ptr(p16), float(self._scale), int(bool(split)))
         elif self.kind == "f16":
-            _lib.check(L.convdr_ip_search_f16(_lib.ptr(q), nq, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo), float(self._scale), n,
-                                              self.d, k, _lib.ptr(self._max_norm), _lib.ptr(tau_in), cap, rank_target,
-                                              _lib.ptr(ws), ws.numel(), _lib.ptr(D), _lib.ptr(I), _lib.ptr(status),
-                                              _lib.ptr(tau_retry), _lib.stream_ptr()), "convdr_ip_search_f16")
+            name, rows = "_f16", (ptr(p32), ptr(p16), ptr(plo), float(self._scale))
         else:
-            _lib.check(L.convdr_ip_search(_lib.ptr(q), nq, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo), n, self.d, k,
-                                          _lib.ptr(self._max_norm), _lib.ptr(tau_in), cap, rank_target,
-                                          _lib.ptr(ws), ws.numel(), _lib.ptr(D), _lib.ptr(I), _lib.ptr(status),
-                                          _lib.ptr(tau_retry), _lib.stream_ptr()), "convdr_ip_search")
+            name, rows = "", (ptr(p32), ptr(p16), ptr(plo))
+        name = "convdr_ip_search" + ("_deep" if deep else "") + name
+        _lib.check(getattr(_lib.lib(), name)(ptr(q), nq, *rows, n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target,
+                                             ptr(ws), ws.numel(), ptr(D), ptr(I), ptr(status), ptr(tau_retry),
+                                             _lib.stream_ptr()), name)
+
+    def _enqueue(self, q, k, tau_in, cap, x3, deep=False, rows=None, rank_target=None):
+        """One enqueue of the kernel pipeline, shallow or deep, over the resident block or over `rows` = (re-score rows, scan
+        copy) of an exhaustive slice: allocates (D, I, status, tau_retry), sizes the workspace and calls the entry.  No sync.
+        Memory bound of the deep pipeline: its workspace is ~ nq * cap * 28 bytes (list id + scan score, band id + fp64 score,
+        ordered fp64 score) plus the threshold sample's scores (sampled rows x padded queries x 4); 1,000 queries at
+        cap = 131,072 would be 3.7 GB beside the resident corpus.  The queries are therefore split so that ONE call never asks
+        for more than DEEP_WS_BYTES = 4 GiB of workspace (the calls run back to back on the stream and share the buffer)."""
+        import torch
+        L = _lib.lib()
+        if x3:
+            self._ensure_lo()
+        p32, p16 = (self._rows, self._pbf) if rows is None else rows
+        nq, n = int(q.shape[0]), self.ntotal if rows is None else int(p16.shape[0])
+        if n == 0:
+            p32 = p16 = q               # never dereferenced when n == 0
+        plo = self._plo if (x3 and n) else None
+        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        status = torch.empty(nq, dtype=torch.int32, device=self.device)
+        tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
+        ws_bytes = L.convdr_ip_deep_workspace_bytes if deep else L.convdr_ip_workspace_bytes
+        step = nq
+        while deep and step > 1 and ws_bytes(step, n, self.d, k, cap) > self.DEEP_WS_BYTES:
+            step = (step + 1) // 2
+        need = ws_bytes(step, n, self.d, k, cap)
+        if deep and not need:
+            raise _lib.ConvdrError("convdr_ip_search_deep: sizes outside the contract (nq=%d n=%d d=%d k=%d cap=%d)"
+                                   % (nq, n, self.d, k, cap))
+        ws = self._workspace(need)
+        rank_target = self.rank_target if rank_target is None else rank_target
+        with torch.cuda.device(self.device):
+            if step >= nq:
+                self._search_call(q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, x3, deep)
+            else:
+                for a in range(0, nq, step):
+                    b = min(nq, a + step)
+                    self._search_call(q[a:b], b - a, p32, p16, plo, n, k, None if tau_in is None else tau_in[a:b], cap, rank_target,
+                                      ws, D[a:b], I[a:b], status[a:b], tau_retry[a:b], x3, deep)
+        return D, I, status, tau_retry
 
     def search_device(self, q, k, tau_in=None, cap=None, x3=None):
         """One enqueue of the kernel pipeline; q is a device fp32 [nq, d] tensor.
@@ -586,28 +570,10 @@ class FlatIPIndex:
         astronomically long query) overflow -- D / I of such a query are NOT usable, and no retry with another threshold
         helps: call ``_rebuild_scaled()`` (search_tensors / search_finish do) and search again.  Callers that take one
         uncertified pass (search_sharded_device(certify=False), the C ABI) must treat any non-zero status as "no result"."""
-        import torch
-        L = _lib.lib()
         cap = cap or self.cap
         while cap < 2 * k and cap < 8192:      # the candidate list holds at least 2k entries (csrc/ip_topk.hip: k <= cap / 2)
             cap *= 2
-        if x3 is None:
-            x3 = self.precision in _SPLIT
-        if x3:
-            self._ensure_lo()
-        nq, n = int(q.shape[0]), self.ntotal
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        status = torch.empty(nq, dtype=torch.int32, device=self.device)
-        tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
-        need = L.convdr_ip_workspace_bytes(nq, n, self.d, k, cap)
-        ws = self._workspace(need)
-        p32 = self._rows if n else q  # never dereferenced when n == 0
-        pbf = self._pbf if n else q
-        plo = self._plo if (x3 and n) else None
-        with torch.cuda.device(self.device):
-            self._search_call(q, nq, p32, pbf, plo, n, k, tau_in, cap, self.rank_target, ws, D, I, status, tau_retry, split=x3)
-        return D, I, status, tau_retry
+        return self._enqueue(q, k, tau_in, cap, self.precision in _SPLIT if x3 is None else x3)
 
     def last_counts(self, nq, k, cap=None):
         """(emitted, band) int32 tensors [nq] of the last search_device call (instrumentation)."""
@@ -619,12 +585,11 @@ class FlatIPIndex:
             out.append(self._ws[off:off + 4 * nq].view(_torch().int32))
         return tuple(out)
 
-    def _certify(self, qt, k, D, I, status, tau_retry, x3):
+    def _certify(self, depth, qt, k, D, I, status, tau_retry, x3, cap):
         """Host loop around the kernel's certificate: re-run the queries that are not OK with the threshold the kernel
-        proposes (and a larger candidate capacity when needed).  Returns the indices still uncertified."""
+        proposes, the candidate capacity doubled on OVERFLOW up to the depth's limit.  Returns the indices still uncertified."""
         import torch
         st = status.cpu().numpy()
-        cap = self.cap
         bad = np.nonzero(st != 0)[0]
         rounds = 0
         while len(bad) and rounds < 6:
@@ -633,10 +598,12 @@ class FlatIPIndex:
             idx = torch.as_tensor(bad, device=self.device)
             tau = tau_retry[idx].contiguous()
             if (st[bad] == STATUS_OVERFLOW).any():
-                if cap >= 8192:
+                if cap >= depth.max_cap:
                     break
                 cap *= 2
-            Db, Ib, sb, tb = self.search_device(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3)
+                if depth.deep_stats:
+                    self.stats["deep_cap"] = max(self.stats["deep_cap"], cap)
+            Db, Ib, sb, tb = getattr(self, depth.enqueue)(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3)
             D[idx], I[idx], tau_retry[idx] = Db, Ib, tb
             sb = sb.cpu().numpy()
             st[bad] = sb
@@ -672,76 +639,83 @@ class FlatIPIndex:
         if k > self.DEEP_MAX_K:
             # the reference takes any --top_n (run_convdr_inference.py:316-319); the deep kernel pipeline's candidate lists end
             # at 131,072 entries, so larger k takes the chunked host-side route (exact, slow): see _search_large_k
-            return (qt, k, None, None, None, None, None)
+            return _Pending(qt, k, None, None, None, None)
         x3 = self.precision in _SPLIT or (self.precision == "auto" and getattr(self, "_x3_first", False) and self.ntotal > 0)
-        if k > self.MAX_K:
-            # 4096 < k <= 65536: the same pipeline with the lists in global memory (convdr_ip_search_deep*)
-            cap = self._deep_cap(k)
-            first = self.search_deep_device(qt, k, cap=cap, x3=x3) if self.ntotal else (None,) * 4
-            return (qt, k, x3) + tuple(first) + (cap,)
-        return (qt, k, x3) + tuple(self.search_device(qt, k, x3=x3))
+        # 4096 < k <= 65536: the same pipeline with the lists in global memory (convdr_ip_search_deep*)
+        depth, cap = (self._DEEP, self._deep_cap(k)) if k > self.MAX_K else (self._SHALLOW, self.cap)
+        if depth is self._DEEP and not self.ntotal:
+            return _Pending(qt, k, depth, x3, cap, None)        # (the shallow kernels pad an empty index's result themselves)
+        return _Pending(qt, k, depth, x3, cap, getattr(self, depth.enqueue)(qt, k, cap=cap, x3=x3))
 
     def search_finish(self, handle):
+        """The ladder, at either depth: fp16 (or pinned) first pass -> rebuild on RANGE -> retries with tau_retry / a doubled
+        list -> split scan -> whatever is still open takes the depth's last rung."""
         import torch
-        if len(handle) == 8:
-            return self._search_finish_deep(*handle)
-        qt, k, x3, D, I, status, tau_retry = handle
-        if x3 is None:
-            self.stats = {"retried": 0, "rounds": 0, "x3_queries": 0, "x3_first": False, "rescaled": 0, "large_k": k,
-                          "deep": 0, "deep_cap": 0, "chunked_queries": int(qt.shape[0])}
-            self.stats[self._split_key] = 0
-            return self._search_large_k(qt, k)
+        qt, k, depth, x3, cap, first = handle
         nq = int(qt.shape[0])
-        rescaled = 0
+        split_key = self._split_key
+        self.stats = {"retried": 0, "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": 0}
+        self.stats[split_key] = nq if x3 else 0
+        if depth is None:
+            self.stats.update(rounds=0, large_k=k, deep=0, deep_cap=0, chunked_queries=nq)
+            return self._search_large_k(qt, k)
+        if depth.deep_stats:
+            self.stats.update(large_k=k, deep=nq, deep_cap=cap, chunked_queries=0)
+        if first is None:               # empty index: FAISS padding
+            return (torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device),
+                    torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
+        enqueue = getattr(self, depth.enqueue)
+        D, I, status, tau_retry = first
         n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()   # one host round trip
         if self.kind == "f16" and n_range:
             self._rebuild_scaled()
-            rescaled = 1
-            D, I, status, tau_retry = self.search_device(qt, k, x3=x3)
+            self.stats["rescaled"] = 1
+            D, I, status, tau_retry = enqueue(qt, k, cap=cap, x3=x3)
             n_bad = int((status != 0).sum().item())
-        split_key = self._split_key
-        self.stats = {"retried": int(n_bad), "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": rescaled}
-        self.stats[split_key] = nq if x3 else 0
+        self.stats["retried"] = int(n_bad)
+        second = self.precision == "auto" and not x3        # the split scan is still ahead
         bad = []
-        if self.stats["retried"]:
-            if self.precision == "auto" and not x3:
-                # a band that already covers every emitted candidate only grows with a lower threshold: those queries go
-                # straight to the split scan, the others get their single-pass retries
-                emitted, band = self.last_counts(nq, k)
-                st = status.cpu().numpy()
-                sat = ((band >= emitted) & (emitted > 0)).cpu().numpy() & (st == STATUS_UNCERTAIN)
-                retry_idx = np.nonzero((st != 0) & ~sat)[0]
-                bad = list(np.nonzero(sat)[0])
-                if len(retry_idx):
-                    sub = torch.as_tensor(retry_idx, device=self.device)
-                    Db, Ib, sb, tb = D[sub], I[sub], status[sub], tau_retry[sub]
-                    left = self._certify(qt[sub].contiguous(), k, Db, Ib, sb, tb, False)
-                    D[sub], I[sub] = Db, Ib
-                    bad += list(retry_idx[np.asarray(left, dtype=np.int64)]) if len(left) else []
-                bad = np.asarray(sorted(bad), dtype=np.int64)
-            else:
-                bad = self._certify(qt, k, D, I, status, tau_retry, x3)
-        if len(bad) and self.precision == "auto" and not x3:
+        if n_bad and second and depth.shortcut:
+            # a band that already covers every emitted candidate only grows with a lower threshold: those queries go
+            # straight to the split scan, the others get their single-pass retries
+            emitted, band = self.last_counts(nq, k)
+            st = status.cpu().numpy()
+            sat = ((band >= emitted) & (emitted > 0)).cpu().numpy() & (st == STATUS_UNCERTAIN)
+            retry_idx = np.nonzero((st != 0) & ~sat)[0]
+            bad = list(np.nonzero(sat)[0])
+            if len(retry_idx):
+                sub = torch.as_tensor(retry_idx, device=self.device)
+                Db, Ib, sb, tb = D[sub], I[sub], status[sub], tau_retry[sub]
+                left = self._certify(depth, qt[sub].contiguous(), k, Db, Ib, sb, tb, False, cap)
+                D[sub], I[sub] = Db, Ib
+                bad += list(retry_idx[np.asarray(left, dtype=np.int64)]) if len(left) else []
+            bad = np.asarray(sorted(bad), dtype=np.int64)
+        elif n_bad:
+            bad = self._certify(depth, qt, k, D, I, status, tau_retry, x3, cap)
+        if len(bad) and second:
             # second rung: split scan for the queries the single-pass error band cannot separate
             idx = torch.as_tensor(bad, device=self.device)
             qs = qt[idx].contiguous()
             self.stats[split_key] = len(bad)
-            Db, Ib, sb, tb = self.search_device(qs, k, x3=True)
+            Db, Ib, sb, tb = enqueue(qs, k, cap=cap, x3=True)
             self.stats["rounds"] += 1
-            bad2 = self._certify(qs, k, Db, Ib, sb, tb, True) if int((sb != 0).sum().item()) else []
+            bad2 = self._certify(depth, qs, k, Db, Ib, sb, tb, True, cap) if int((sb != 0).sum().item()) else []
             D[idx], I[idx] = Db, Ib
             bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
         if self.precision == "auto":
             self._x3_first = self.stats[split_key] > nq // 2
         if len(bad):
-            # last rung: more than 8192 passages inside the error band of the k-th score even with the split scan
-            # (blocks whose norms spread over orders of magnitude: eps scales with the LARGEST norm).  Every slice of
-            # <= cap rows is searched with all of its rows as candidates -- exact by construction -- and the slices are
-            # merged in row order (earlier rows win ties): slow (one small launch chain per slice) but always an answer
+            # last rung: more than the largest list's worth of passages inside the error band of the k-th score even with the
+            # split scan (blocks whose norms spread over orders of magnitude: eps scales with the LARGEST norm).  Shallow:
+            # every slice of <= cap rows is searched with all of its rows as candidates -- exact by construction -- and the
+            # slices are merged in row order (earlier rows win ties): slow (one small launch chain per slice) but always an
+            # answer.  Deep: the chunked route of k > DEEP_MAX_K
             idx = torch.as_tensor(np.asarray(bad, dtype=np.int64), device=self.device)
-            Db, Ib = self._search_exhaustive(qt[idx].contiguous(), k)
+            Db, Ib = getattr(self, depth.last_rung)(qt[idx].contiguous(), k)
             D[idx], I[idx] = Db, Ib
-            self.stats["exhaustive_queries"] = len(bad)
+            self.stats[depth.last_stat] = len(bad)
+            if depth.deep_stats:
+                self.stats["deep"] = nq - len(bad)
         return D, I
 
     def search_distinct(self, q, k, keys, depth=None, strict=True, max_depth=None):
@@ -815,6 +789,11 @@ class FlatIPIndex:
     DEEP_MAX_K = 65536   # convdr_ip_search_deep: k <= cap / 2, cap <= 131072
     DEEP_MIN_CAP, DEEP_MAX_CAP = 16384, 131072
     DEEP_WS_BYTES = 4 << 30      # most workspace one deep call may ask for; search_deep_device splits the queries to stay under it
+    # the two depths of the ladder (search_begin / search_finish): the method that enqueues a pass, where the doubling of the
+    # candidate capacity ends, whether last_counts serves the saturated-band shortcut, the last rung and the stat it reports, whether stats carries
+    # the deep keys (large_k, deep, deep_cap, chunked_queries)
+    _SHALLOW = _Depth("search_device", 8192, True, "_search_exhaustive", "exhaustive_queries", False)
+    _DEEP = _Depth("search_deep_device", DEEP_MAX_CAP, False, "_search_large_k", "chunked_queries", True)
 
     def _deep_cap(self, k):
         """Candidate capacity of the first deep pass: the largest power of two <= 4k inside the kernel's range -- between 2k
@@ -825,113 +804,19 @@ class FlatIPIndex:
         return cap
 
     def search_deep_device(self, q, k, tau_in=None, cap=None, x3=False):
-        """``search_device`` for MAX_K < k <= DEEP_MAX_K: enqueues convdr_ip_search_deep[_f16]; device (D, I, status, tau_retry)
-        with the meanings of search_device; no sync.
-        Memory bound: the deep workspace is ~ nq * cap * 28 bytes (list id + scan score, band id + fp64 score, ordered fp64
-        score) plus the threshold sample's scores (sampled rows x padded queries x 4); 1,000 queries at cap = 131,072 would be
-        3.7 GB beside the resident corpus.  The queries are therefore split so that ONE call never asks for more than
-        DEEP_WS_BYTES = 4 GiB of workspace (the calls run back to back on the stream and share the buffer)."""
-        import torch
-        L = _lib.lib()
+        """``search_device`` for MAX_K < k <= DEEP_MAX_K: enqueues convdr_ip_search_deep[_f16 | _h16]; device (D, I, status,
+        tau_retry) with the meanings of search_device; no sync.  The queries are split under DEEP_WS_BYTES (see _enqueue)."""
         cap = int(cap or self._deep_cap(k))
-        if x3:
-            self._ensure_lo()
-        nq, n = int(q.shape[0]), self.ntotal
-        if n <= cap:
+        if self.ntotal <= cap:
             tau_in = None               # every row is a candidate: the list is complete whatever threshold a retry proposes
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        status = torch.empty(nq, dtype=torch.int32, device=self.device)
-        tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
-        step = nq
-        while step > 1 and L.convdr_ip_deep_workspace_bytes(step, n, self.d, k, cap) > self.DEEP_WS_BYTES:
-            step = (step + 1) // 2
-        need = L.convdr_ip_deep_workspace_bytes(step, n, self.d, k, cap)
-        if not need:
-            raise _lib.ConvdrError("convdr_ip_search_deep: sizes outside the contract (nq=%d n=%d d=%d k=%d cap=%d)"
-                                   % (nq, n, self.d, k, cap))
-        ws = self._workspace(need)
-        p32 = self._rows if n else q    # never dereferenced when n == 0
-        p16 = self._pbf if n else q
-        plo = self._plo if (x3 and n) else None
-        with torch.cuda.device(self.device):
-            for a in range(0, nq, step):
-                b = min(nq, a + step)
-                tin = None if tau_in is None else tau_in[a:b]
-                args = (b - a, _lib.ptr(p32), _lib.ptr(p16), _lib.ptr(plo))
-                tail = (n, self.d, k, _lib.ptr(self._max_norm), _lib.ptr(tin), cap, self.rank_target, _lib.ptr(ws), ws.numel(),
-                        _lib.ptr(D[a:b]), _lib.ptr(I[a:b]), _lib.ptr(status[a:b]), _lib.ptr(tau_retry[a:b]), _lib.stream_ptr())
-                if self._half:
-                    _lib.check(L.convdr_ip_search_deep_h16(_lib.ptr(q[a:b]), b - a, _lib.ptr(p16), float(self._scale),
-                                                           int(bool(x3)), *tail), "convdr_ip_search_deep_h16")
-                elif self.kind == "f16":
-                    _lib.check(L.convdr_ip_search_deep_f16(_lib.ptr(q[a:b]), *args, float(self._scale), *tail),
-                               "convdr_ip_search_deep_f16")
-                else:
-                    _lib.check(L.convdr_ip_search_deep(_lib.ptr(q[a:b]), *args, *tail), "convdr_ip_search_deep")
-        return D, I, status, tau_retry
+        return self._enqueue(q, k, tau_in, cap, x3, deep=True)
 
-    def _certify_deep(self, qt, k, D, I, status, tau_retry, x3, cap):
-        """``_certify`` with the deep bounds: single-pass retries with the threshold the kernel proposes, the capacity doubled
-        on OVERFLOW up to DEEP_MAX_CAP.  Returns the indices still uncertified."""
-        import torch
-        st = status.cpu().numpy()
-        bad = np.nonzero(st != 0)[0]
-        rounds = 0
-        while len(bad) and rounds < 6:
-            rounds += 1
-            self.stats["rounds"] += 1
-            idx = torch.as_tensor(bad, device=self.device)
-            tau = tau_retry[idx].contiguous()
-            if (st[bad] == STATUS_OVERFLOW).any():
-                if cap >= self.DEEP_MAX_CAP:
-                    break
-                cap *= 2
-                self.stats["deep_cap"] = max(self.stats["deep_cap"], cap)
-            Db, Ib, sb, tb = self.search_deep_device(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3)
-            D[idx], I[idx], tau_retry[idx] = Db, Ib, tb
-            sb = sb.cpu().numpy()
-            st[bad] = sb
-            bad = bad[sb != 0]
-        return bad
-
-    def _search_finish_deep(self, qt, k, x3, D, I, status, tau_retry, cap):
-        """The ladder of search_finish for MAX_K < k <= DEEP_MAX_K: fp16 (or pinned) first pass -> rebuild on RANGE -> retries
-        with tau_retry / a doubled list -> split scan -> whatever is still open goes to _search_large_k."""
-        import torch
-        nq = int(qt.shape[0])
-        split_key = self._split_key
-        self.stats = {"retried": 0, "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": 0, "large_k": k,
-                      "deep": nq, "deep_cap": cap, "chunked_queries": 0}
-        self.stats[split_key] = nq if x3 else 0
-        if D is None:                   # empty index: FAISS padding
-            return (torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device),
-                    torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
-        n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()
-        if self.kind == "f16" and n_range:
-            self._rebuild_scaled()
-            self.stats["rescaled"] = 1
-            D, I, status, tau_retry = self.search_deep_device(qt, k, cap=cap, x3=x3)
-            n_bad = int((status != 0).sum().item())
-        self.stats["retried"] = int(n_bad)
-        bad = self._certify_deep(qt, k, D, I, status, tau_retry, x3, cap) if n_bad else []
-        if len(bad) and self.precision == "auto" and not x3:
-            idx = torch.as_tensor(bad, device=self.device)
-            qs = qt[idx].contiguous()
-            self.stats[split_key] = len(bad)
-            Db, Ib, sb, tb = self.search_deep_device(qs, k, cap=cap, x3=True)
-            self.stats["rounds"] += 1
-            bad2 = self._certify_deep(qs, k, Db, Ib, sb, tb, True, cap) if int((sb != 0).sum().item()) else []
-            D[idx], I[idx] = Db, Ib
-            bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
-        if self.precision == "auto":
-            self._x3_first = self.stats[split_key] > nq // 2
-        if len(bad):
-            idx = torch.as_tensor(np.asarray(bad, dtype=np.int64), device=self.device)
-            Db, Ib = self._search_large_k(qt[idx].contiguous(), k)
-            D[idx], I[idx] = Db, Ib
-            self.stats["chunked_queries"] = len(bad)
-            self.stats["deep"] = nq - len(bad)
+    def _exact_slice(self, rows, kq, qq, cap):
+        """Top-kq of the slice `rows` = (re-score rows, scan copy) of at most `cap` rows: the plan takes every row as a candidate
+        (no threshold pass, tau = -inf), so the result is exact by construction."""
+        D, I, status, _ = self._enqueue(qq, kq, None, cap, False, rows=rows, rank_target=0)
+        if int((status != 0).sum().item()):
+            raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % rows[1].shape[0])
         return D, I
 
     def _search_large_k(self, q, k, q_chunk=8):
@@ -942,24 +827,12 @@ class FlatIPIndex:
         across slices), and every run of equal fp32 scores that spans slices or straddles rank k is ranked once more as one
         slice.  Slow (n / 4096 launch chains per 8 queries, an [8, n] sort), always the exhaustive exact answer."""
         import torch
-        L = _lib.lib()
         nq, n = int(q.shape[0]), self.ntotal
-        Dout = torch.full((nq, k), -3.4028234663852886e38, dtype=torch.float32, device=self.device)
+        Dout = torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device)
         Iout = torch.full((nq, k), -1, dtype=torch.int64, device=self.device)
         if n == 0:
             return Dout, Iout
         cap, step = 8192, 4096
-
-        def exact(p32, pbf, m, kq, qq):
-            D = torch.empty((qq.shape[0], kq), dtype=torch.float32, device=self.device)
-            I = torch.empty((qq.shape[0], kq), dtype=torch.int64, device=self.device)
-            status = torch.empty(qq.shape[0], dtype=torch.int32, device=self.device)
-            tau_retry = torch.empty(qq.shape[0], dtype=torch.float32, device=self.device)
-            ws = self._workspace(L.convdr_ip_workspace_bytes(int(qq.shape[0]), m, self.d, kq, cap))
-            self._search_call(qq, int(qq.shape[0]), p32, pbf, None, m, kq, None, cap, 0, ws, D, I, status, tau_retry)
-            if int((status != 0).sum().item()):
-                raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % m)
-            return D, I
 
         with torch.cuda.device(self.device):
             for j0 in range(0, nq, q_chunk):
@@ -967,7 +840,7 @@ class FlatIPIndex:
                 Ds, Is = [], []
                 for s0 in range(0, n, step):
                     m = min(n, s0 + step) - s0
-                    D, I = exact(self._rows[s0:s0 + m], self._pbf[s0:s0 + m], m, m, qq)
+                    D, I = self._exact_slice((self._rows[s0:s0 + m], self._pbf[s0:s0 + m]), m, qq, cap)
                     Ds.append(D)
                     Is.append(I + s0)
                 Dall, Iall = torch.cat(Ds, 1), torch.cat(Is, 1)
@@ -989,14 +862,13 @@ class FlatIPIndex:
                             raise _lib.ConvdrError("FlatIPIndex.search: %d passages share one fp32 score around rank %d; "
                                                    "k > %d cannot order a tie group that large" % (ln, b, self.MAX_K))
                         rows = torch.sort(i[b:b + ln]).values
-                        Dj, Ij = exact(*self._row_pair(rows), ln, ln, qq[j:j + 1].contiguous())
+                        Dj, Ij = self._exact_slice(self._row_pair(rows), ln, qq[j:j + 1].contiguous(), cap)
                         d[b:b + ln], i[b:b + ln] = Dj[0], rows[Ij[0]]
                     Dout[j0 + j, :kk], Iout[j0 + j, :kk] = d[:kk], i[:kk]
         return Dout, Iout
 
     def _search_exhaustive(self, q, k):
         import torch
-        L = _lib.lib()
         nq, n = int(q.shape[0]), self.ntotal
         kk = min(2 * k, 4096)           # candidates carried through the merges (see the re-ranking below)
         cap = 4096
@@ -1004,22 +876,11 @@ class FlatIPIndex:
             cap *= 2
         step = cap                      # n <= cap: the plan takes every row as a candidate (no threshold pass, tau = -inf)
 
-        def exact(p32, pbf, m, kq, qq):
-            D = torch.empty((qq.shape[0], kq), dtype=torch.float32, device=self.device)
-            I = torch.empty((qq.shape[0], kq), dtype=torch.int64, device=self.device)
-            status = torch.empty(qq.shape[0], dtype=torch.int32, device=self.device)
-            tau_retry = torch.empty(qq.shape[0], dtype=torch.float32, device=self.device)
-            ws = self._workspace(L.convdr_ip_workspace_bytes(int(qq.shape[0]), m, self.d, kq, cap))
-            self._search_call(qq, int(qq.shape[0]), p32, pbf, None, m, kq, None, cap, 0, ws, D, I, status, tau_retry)
-            if int((status != 0).sum().item()):
-                raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % m)
-            return D, I
-
         merged = None
         with torch.cuda.device(self.device):
             for s0 in range(0, n, step):
                 e0 = min(n, s0 + step)
-                D, I = exact(self._rows[s0:e0], self._pbf[s0:e0], e0 - s0, kk, q)
+                D, I = self._exact_slice((self._rows[s0:e0], self._pbf[s0:e0]), kk, q, cap)
                 I = torch.where(I >= 0, I + s0, I)
                 merged = (D, I) if merged is None else tuple(t[:, :kk].contiguous() for t in merge_topk_device(merged, (D, I), kk))
             # The merges compare the fp32-rounded scores; the result's order is defined on the canonical fp64 scores (two
@@ -1032,10 +893,10 @@ class FlatIPIndex:
                 rows = torch.sort(rows[rows >= 0]).values
                 m = int(rows.numel())
                 if m == 0:
-                    Dout[j] = -3.4028234663852886e38
+                    Dout[j] = PAD_SCORE
                     Iout[j] = -1
                     continue
-                Dj, Ij = exact(*self._row_pair(rows), m, k, q[j:j + 1].contiguous())
+                Dj, Ij = self._exact_slice(self._row_pair(rows), k, q[j:j + 1].contiguous(), cap)
                 Dout[j] = Dj[0]
                 Iout[j] = torch.where(Ij[0] >= 0, rows[Ij[0].clamp_min(0)], Ij[0])
         return Dout, Iout
@@ -1199,9 +1060,6 @@ def merge_topk_device(merged, cand, topN):
     return Do, Io
 
 
-PAD_SCORE = -3.4028234663852886e38      # what IndexFlatIP.search returns beside id -1
-
-
 def distinct_topk(D, I, k, key_map=None):
     """The reference's `seen_pid` walk (run_convdr_inference.py:58-69) over ranked lists, as array operations: the numpy
     restatement of convdr_topk_distinct (include/convdr_hip.h) for the host path.  D / I: [nq, n] scores and ids, every row a
@@ -1292,6 +1150,29 @@ def _check_max_depth(who, max_depth):
     return md
 
 
+def _distinct_row_depth(who, topN, rows_per_key, limit, limit_name):
+    """m = topN * rows_per_key, the row depth at which a walk over block files holds topN keys for every query."""
+    m = topN * rows_per_key
+    if topN < 1 or rows_per_key < 1 or m > limit:
+        raise ValueError("%s: topN * rows_per_key = %d * %d = %d is outside 1..%d (%s)" % (who, topN, rows_per_key, m, limit, limit_name))
+    return m
+
+
+def _check_distinct_certificate(who, counts, topN, m, rows_per_key, ann_data_dir, max_blocks, key_map):
+    """The certificate of the ONE distinct step after a block walk at row depth m: a query with fewer than topN keys in m rows
+    of a corpus that has more rows means rows_per_key was understated."""
+    from . import blocks
+    if (counts[:, 0] < 0).any():
+        raise _lib.ConvdrError("%s: a record offset lies outside key_map (%d entries)" % (who, len(key_map)))
+    open_ = np.nonzero((counts[:, 0] < topN) & (counts[:, 1] >= m))[0]
+    if len(open_):
+        most, total = blocks.key_row_stats(ann_data_dir, max_blocks, key_map)
+        if total > m:
+            raise _lib.ConvdrError("%s: %d queries hold fewer than %d keys in their top %d rows: "
+                                   "rows_per_key = %d is understated (the id files give %d)"
+                                   % (who, len(open_), topN, m, rows_per_key, most))
+
+
 def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, rows_per_key=None, key_map=None, max_blocks=8,
                                timings=None, max_depth=None):
     """``search_one_by_one`` at DOCUMENT level: per query the topN best distinct keys over all block files, each with the
@@ -1315,11 +1196,8 @@ def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, r
     if rows_per_key is None:
         rows_per_key = blocks.max_rows_per_key(ann_data_dir, max_blocks, key_map)
     rows_per_key = int(rows_per_key)
-    m = topN * rows_per_key
-    if topN < 1 or rows_per_key < 1 or m > max_depth:
-        raise ValueError("search_distinct_one_by_one: topN * rows_per_key = %d * %d = %d is outside 1..%d (%s)"
-                         % (topN, rows_per_key, m, max_depth,
-                            "FlatIPIndex.MAX_K" if max_depth == FlatIPIndex.MAX_K else "max_depth"))
+    m = _distinct_row_depth("search_distinct_one_by_one", topN, rows_per_key, max_depth,
+                            "FlatIPIndex.MAX_K" if max_depth == FlatIPIndex.MAX_K else "max_depth")
     merged = _search_block_list(ann_data_dir, gpu_index, query_embedding, m, range(max_blocks), True, timings)
     if merged is None:
         raise FileNotFoundError("no passage blocks under %s" % ann_data_dir)
@@ -1334,15 +1212,7 @@ def search_distinct_one_by_one(ann_data_dir, gpu_index, query_embedding, topN, r
     else:
         km = key_map.cpu().numpy() if hasattr(key_map, "cpu") else key_map
         D, I, _, counts = distinct_topk(merged[0][:, :m], merged[1][:, :m], topN, km)
-    if (counts[:, 0] < 0).any():
-        raise _lib.ConvdrError("search_distinct_one_by_one: a record offset lies outside key_map (%d entries)" % len(key_map))
-    open_ = np.nonzero((counts[:, 0] < topN) & (counts[:, 1] >= m))[0]
-    if len(open_):
-        most, total = blocks.key_row_stats(ann_data_dir, max_blocks, key_map)
-        if total > m:
-            raise _lib.ConvdrError("search_distinct_one_by_one: %d queries hold fewer than %d keys in their top %d rows: "
-                                   "rows_per_key = %d is understated (the id files give %d)"
-                                   % (len(open_), topN, m, rows_per_key, most))
+    _check_distinct_certificate("search_distinct_one_by_one", counts, topN, m, rows_per_key, ann_data_dir, max_blocks, key_map)
     return D, I
 
 

@@ -122,6 +122,44 @@ def test_reserved_index_fills_in_place(torch_cuda):
     np.testing.assert_array_equal(I, OS.flat_ip_search(Q, P[:3000], 10)[1])
 
 
+def test_reservation_survives_a_late_remainder_copy(torch_cuda):
+    """reserve(n, lo=False) on a pinned split precision: the first add() has to create the remainder copy.  It is allocated
+    beside the reserved block, with the reservation's row count; the fp32 block and the scan copy stay where they are."""
+    torch = torch_cuda
+    P, Q = synth_corpus(93, 3000, 128), synth_corpus(94, 5, 128)
+    idx = _index(128, precision="fp16x3")
+    idx.reserve(4000, lo=False)
+    assert idx._slo is None
+    base = (idx._s32.data_ptr(), idx._s16.data_ptr())
+    for a in (0, 1000):
+        idx.add(torch.from_numpy(P[a:a + 1000 + a]).cuda())
+        assert (idx._s32.data_ptr(), idx._s16.data_ptr()) == base
+        assert idx._s32.shape[0] == idx._s16.shape[0] == idx._slo.shape[0] == 4000
+    assert idx.ntotal == 3000 and idx._reserved
+    D, I = idx.search(Q, 50)
+    Dr, Ir = OS.flat_ip_search(Q, P, 50)
+    np.testing.assert_array_equal(I, Ir)
+    np.testing.assert_array_equal(D, Dr)
+
+
+def test_small_host_sources_of_other_dtypes_are_widened_to_fp32(torch_cuda):
+    """add() of a small host block that is not fp32: a pageable bfloat16 tensor (a dtype numpy does not have), a read-only
+    float16 array and a float64 array are widened / rounded to fp32 rows, like the same values given as fp32."""
+    torch = torch_cuda
+    P, Q = synth_corpus(95, 2000, 128), synth_corpus(96, 5, 128)
+    ro16 = P.astype(np.float16)
+    ro16.flags.writeable = False
+    for src, want in ((torch.from_numpy(P).bfloat16(), torch.from_numpy(P).bfloat16().float().numpy()),
+                      (ro16, ro16.astype(np.float32)), (P.astype(np.float64) * (1 + 2.0 ** -30), (P.astype(np.float64) * (1 + 2.0 ** -30)).astype(np.float32))):
+        idx = _index(128)
+        idx.add(src)
+        assert idx._p32.dtype == torch.float32 and np.array_equal(idx._p32.cpu().numpy(), want)
+        D, I = idx.search(Q, 20)
+        Dr, Ir = OS.flat_ip_search(Q, want, 20)
+        np.testing.assert_array_equal(I, Ir)
+        np.testing.assert_array_equal(D, Dr)
+
+
 def test_exact_ties_lower_index_first(torch_cuda):
     base = synth_corpus(21, 300, 768)
     P = np.concatenate([base[:200], base[50:60], base[50:60]])
@@ -442,6 +480,33 @@ def test_streamed_host_block_equals_resident_block(torch_cuda, tmp_path):
     oD, oI = OS.search_one_by_one([(P0, np.arange(len(P0), dtype=np.int64)), (P1, np.arange(len(P1), dtype=np.int64) + 10 ** 6)], Q, 100)
     np.testing.assert_array_equal(mI, oI)
     np.testing.assert_array_equal(mD, oD)
+
+
+def test_streamed_host_block_writes_the_remainder_copy_per_chunk(torch_cuda):
+    """A pinned split precision keeps a remainder copy, which the streamed add() writes chunk by chunk beside the scan copy:
+    512 rows per chunk is five full chunks and a ragged tail for the first block, two and a tail for the appended one.
+    (D, I) must be bit-identical to the same index filled from device tensors."""
+    torch = torch_cuda
+    d, k = 128, 50
+    P0, P1, Q = synth_corpus(61, 3001, d), synth_corpus(62, 1201, d), synth_corpus(63, 19, d)
+    ref = _index(d, precision="fp16x3")
+    ref.add(torch.from_numpy(P0).cuda())
+    ref.add(torch.from_numpy(P1).cuda())
+    Dr, Ir = ref.search(Q, k)
+    idx = _index(d, precision="fp16x3")
+    idx.host_chunk_bytes = 256 << 10
+    for P in (P0, P1):
+        host = P.copy()
+        host.flags.writeable = False
+        assert host.nbytes > idx.host_chunk_bytes // 2           # above the threshold that selects streaming
+        idx.stats.pop("add_host_bytes", None)
+        idx.add(host)
+        assert idx.stats["add_host_bytes"] == host.nbytes        # (set by the streamed path only)
+    assert idx.ntotal == 4202 and idx._slo is not None
+    D, I = idx.search(Q, k)
+    np.testing.assert_array_equal(I, Ir)
+    np.testing.assert_array_equal(D, Dr)
+    assert torch.equal(idx._p32, ref._p32)      # (the 16-bit copies differ: the streamed centre is the first CHUNK's column mean)
 
 
 @pytest.mark.parametrize("n", [33000, 47104, 70000, 150000])

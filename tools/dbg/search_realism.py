@@ -50,9 +50,9 @@ with torch.no_grad():
 idx = FlatIPIndex(d, device=dev); idx.add(P)
 import convdr_amd.search as S
 orig = idx._certify
-def spy(qt, k_, D, I, status, tau_retry, x3):
+def spy(depth, qt, k_, D, I, status, tau_retry, x3, cap):
     st0 = status.cpu().numpy().copy()
-    bad = orig(qt, k_, D, I, status, tau_retry, x3)
+    bad = orig(depth, qt, k_, D, I, status, tau_retry, x3, cap)
     print("   _certify x3=%s in: %s -> still bad %d" % (x3, np.bincount(st0, minlength=4), len(bad)), idx.stats)
     return bad
 idx._certify = spy
