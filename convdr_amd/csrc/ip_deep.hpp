@@ -304,7 +304,8 @@ static bool ip_deep_sizes_ok(int nq, int64_t n, int d, int k, int cap) {
 static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_half,
                           const void* p_half_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
                           int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                          float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false) {
+                          float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false,
+                          const uint32_t* row_bits = nullptr, int64_t n_allowed = -1) {
   CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search_deep: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
   CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search_deep: need d %% 64 == 0 and d <= 4096 (got %d)", d);
   CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search_deep: block too large (n=%lld >= 2^31)", (long long)n);
@@ -327,6 +328,8 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
   double* sort_x = (double*)(ws + p.o_sx);
   uint32_t* band = (uint32_t*)(ws + p.o_m);
   const bool x3 = p_half_lo != nullptr || two_pass;   // the query's remainder is an operand (ip_search: `split`)
+  const int64_t n_need = row_bits ? n_allowed : n;    // the row filter, as in ip_search
+  const bool all_candidates = p.mode < 0 || (row_bits && n_allowed <= cap);
 
   bf16_t* qlo = x3 ? (bf16_t*)(ws + p.o_qlo) : nullptr;
   const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
@@ -346,9 +349,10 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
     a.P = (const bf16_t*)p_half; a.Qb = qb; a.Plo = (const bf16_t*)p_half_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad;
     a.d = d; a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = list_id; a.cand_s = list_s; a.cap = cap; a.T = T;
     a.two_pass = two_pass ? 1 : 0;
+    a.bits = row_bits;
     if (tau_in) {
       CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
-    } else if (p.mode < 0) {
+    } else if (all_candidates) {
       hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
       CONVDR_CHECK_LAUNCH("k_fill_f32");
     } else {
@@ -358,6 +362,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
         ScanArgs b = a;
         b.P = a.P + row0 * d;
         if (a.Plo) b.Plo = a.Plo + row0 * d;
+        if (a.bits) b.bits = a.bits + row0 / 32;   // (row0 is a multiple of the tile height: whole words)
         b.n = rows;
         b.nPt = (int)ceil_div64(rows, p.tr);   // = segTiles: only the block's last tile is ragged
         b.pt_stride = 1;
@@ -373,7 +378,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
   }
   {
     ProfScope prof("ip_cut_deep", st);
-    hipLaunchKernelGGL(k_ip_cut_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, n, k, cap, counts, (uint32_t*)(ws + p.o_counts_packed),
+    hipLaunchKernelGGL(k_ip_cut_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, n_need, k, cap, counts, (uint32_t*)(ws + p.o_counts_packed),
                        list_id, list_s, band_id, tau, qnorm, p_max_norm, ip_eps_coef(d, x3, kind), ip_eps_abs(d, x3, kind),
                        kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, band, status,
                        tau_retry);

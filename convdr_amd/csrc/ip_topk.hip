@@ -276,11 +276,51 @@ struct ScanArgs {
   float* T;          // FULL: [nPt*128, nq_pad]; TOP2: [nPt*8, nq_pad]
   int dbg_prelanded; // timing experiment (TRACE library only): a tile's first K chunks are not waited for (garbage results)
   int two_pass;      // half store (fp16 only): S~ = P Qh + P Ql, the passage operand is exact and has no remainder copy
+  const uint32_t* bits;  // row filter (FILT kernels only): row r is allowed iff bit r & 31 of word r >> 5 is set; padded with
+                         // zero bits to whole TR-row tiles, word 0 = row 0 of P (a sub-block's pointer advances with its P)
 };
 
-template <int MODE, class T>
+// The row filter in the scan epilogues.  A wave's accumulator tile mt covers the 32 rows (wr * MT + mt) * 32 .. + 31 of the
+// passage tile -- exactly ONE bitmap word, wave-uniform -- and register r of lane l holds row (r & 3) + 8 (r >> 2) + 4 (l >> 5)
+// of them.  filter_lane_words clears the bits of rows past the block's end (the caller's padding is not trusted: a set bit
+// there would name a row that does not exist) and shifts by the lane's 4 * hi, so that the bit sits at a compile-time
+// position.  THE RULE, in every mode: a row whose bit is clear never reserves a list slot, whatever tau is, and contributes
+// -inf to a threshold sample.  filter_acc applies it to the accumulators in place, before the epilogue proper: a masked
+// score becomes NaN in the emitting scan (NaN >= tau is false for EVERY tau; -inf would pass the no-threshold plans'
+// tau = -inf and fill the list with masked rows) and -inf in the sampling modes.  Two VALU operations per accumulator (sign-
+// extended bit field, bit select), no compare: the sweeps that follow are the unfiltered ones and hold no extra masks.
+template <class T>
+__device__ __forceinline__ void filter_lane_words(const uint32_t (&fw)[T::MT], const WavePos<T>& w, int rows_left,
+                                                  uint32_t (&out)[T::MT]) {
+#pragma unroll
+  for (int mt = 0; mt < T::MT; ++mt) {
+    const int left = rows_left - (w.wr * T::MT + mt) * 32;
+    const uint32_t valid = left >= 32 ? 0xffffffffu : (left > 0 ? (1u << left) - 1u : 0u);
+    out[mt] = (fw[mt] & valid) >> (4 * w.hi);
+  }
+}
+template <class T>
+__device__ __forceinline__ void filter_acc(GemmAcc<T>& acc, const uint32_t (&fw)[T::MT], const WavePos<T>& w, int64_t rows_after_m0,
+                                           uint32_t masked_bits) {
+  uint32_t fl[T::MT];
+  filter_lane_words<T>(fw, w, (int)(rows_after_m0 < (int64_t)T::TR ? rows_after_m0 : (int64_t)T::TR), fl);
+#pragma unroll
+  for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t m = (uint32_t)((int32_t)(fl[mt] << (31 - ((r & 3) + 8 * (r >> 2)))) >> 31);   // all ones iff allowed
+#pragma unroll
+      for (int nt = 0; nt < T::NT; ++nt)
+        acc.c[mt][nt][r] = __uint_as_float((__float_as_uint(acc.c[mt][nt][r]) & m) | (masked_bits & ~m));
+    }
+}
+constexpr uint32_t IP_MASKED_EMIT = 0xffffffffu;     // a NaN
+constexpr uint32_t IP_MASKED_SAMPLE = 0xff800000u;   // -inf
+
+template <int MODE, class T, bool FILT>
 __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc, const WavePos<T>& w, int ts, int64_t m0,
-                                              int64_t n0, const float (&tau_lane)[T::NT]) {
+                                              int64_t n0, const float (&tau_lane)[T::NT], const uint32_t (&fw)[T::MT]) {
+  if constexpr (FILT) filter_acc<T>(acc, fw, w, a.n - m0, MODE == IP_MODE_EMIT ? IP_MASKED_EMIT : IP_MASKED_SAMPLE);
   if constexpr (MODE == IP_MODE_EMIT) {
     // A lane owns one query per 32-column tile and MT*16 of the tile's passages.  It counts its hits, reserves that
     // many slots of the query's candidate list with ONE atomic (a device-scope returning atomic is a ~1-2 us round
@@ -288,7 +328,8 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
     // the scan), then writes the hits into consecutive slots.  The list order differs from run to run either way;
     // the downstream kernels do not depend on it.
     const int rows_left = (int)(a.n - m0 < (int64_t)T::TR ? a.n - m0 : (int64_t)T::TR);
-    if (rows_left < T::TR) {   // the last passage tile: rows past n scored 0 (zero-filled operand) and must never hit
+    // the last passage tile: rows past n scored 0 (zero-filled operand) and must never hit (FILT: masked with the rest)
+    if (!FILT && rows_left < T::TR) {
 #pragma unroll
       for (int nt = 0; nt < T::NT; ++nt)
 #pragma unroll
@@ -350,7 +391,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int64_t row = m0 + w.r_index(mt, r);
-          a.T[row * a.nq_pad + q] = row < a.n ? acc.c[mt][nt][r] : -INFINITY;
+          a.T[row * a.nq_pad + q] = (FILT || row < a.n) ? acc.c[mt][nt][r] : -INFINITY;
         }
     }
   } else {  // TOP2: best two of this lane's MT*16 scores (one query, MT*16 of the tile's passages)
@@ -363,7 +404,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int64_t row = m0 + w.r_index(mt, r);
-          const float s = row < a.n ? acc.c[mt][nt][r] : -INFINITY;
+          const float s = (FILT || row < a.n) ? acc.c[mt][nt][r] : -INFINITY;
           const float lo = fminf(b0, s);
           b0 = fmaxf(b0, s);
           b1 = fmaxf(b1, lo);
@@ -381,7 +422,9 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 // tile is exposed (they were ~40 % of a 12-step tile).
 // PASSES: 1 = S~ = Ph Qh; 3 = the split scan Ph Qh + Ph Ql + Pl Qh; 2 = the half store's second rung P Qh + P Ql (the
 // stored halves ARE the passages: there is no Pl).
-template <int MODE, class T, int PASSES, bool F16>
+// FILT: the row filter (a.bits).  A compile-time parameter, not a test on the pointer: the unfiltered instantiations are
+// instruction for instruction the kernels they were before the filter existed.
+template <int MODE, class T, int PASSES, bool F16, bool FILT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t ntiles = (uint32_t)a.nPt * (uint32_t)a.nQt;
@@ -417,12 +460,27 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
     }
   };
   load_tau(n0);
+  // FILT: the tile's bitmap words -- the MT consecutive words of this wave's rows, one 16-byte load at a wave-uniform,
+  // 16-byte aligned address (m0 is a multiple of TR) -- travel with the thresholds: loaded one tile ahead, retired by the
+  // main loop's waits.  Strided TOP2 tiles index the bitmap by their own m0.
+  uint32_t fw_next[T::MT] = {};
+  auto load_bits = [&](int64_t m0_) {
+    if constexpr (FILT) {
+      static_assert(T::MT == 4, "one uint4 of bitmap words per wave");
+      const uint4 v = *(const uint4*)(a.bits + (m0_ >> 5) + w.wr * T::MT);
+      fw_next[0] = v.x; fw_next[1] = v.y; fw_next[2] = v.z; fw_next[3] = v.w;
+    }
+  };
+  load_bits(m0);
   for (;;) {
     GemmAcc<T> acc;
     acc.zero();
     float tau_lane[T::NT];
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) tau_lane[nt] = tau_next[nt];
+    uint32_t fw[T::MT];
+#pragma unroll
+    for (int mt = 0; mt < T::MT; ++mt) fw[mt] = fw_next[mt];
     int idle = gemm_nt_mainloop<T, F16>(src, a.d, smem, acc, w, buf, true);
     if constexpr (PASSES >= 2) {  // S~ = Ph Qh + Ph Ql + Pl Qh: fp32-class scores from three bf16 passes into the same accumulators
       __syncthreads();
@@ -436,6 +494,10 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
     }
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_lane[nt]));   // hipcc: the loads are retired HERE
+    if constexpr (FILT) {
+#pragma unroll
+      for (int mt = 0; mt < T::MT; ++mt) asm volatile("" : "+v"(fw[mt]));
+    }
     const uint32_t next = idx + stride;
     const bool has_next = next < chunk_len;
     const int ts_cur = ts;
@@ -443,13 +505,14 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
     if (has_next) {
       coords(next, ts, m0, n0);
       load_tau(n0);
+      load_bits(m0);
       src = TileSrc<T>(a.P, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
       gemm_issue_stage<T>(src, 0, smem + idle * T::STAGE_BYTES, w);
     }
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));   // opaque: the epilogue's lane-dependent addresses stay out of the main loop's registers
     const WavePos<T> we(tid_e);
-    scan_epilogue<MODE, T>(a, acc, we, ts_cur, m0_cur, n0_cur, tau_lane);
+    scan_epilogue<MODE, T, FILT>(a, acc, we, ts_cur, m0_cur, n0_cur, tau_lane, fw);
     if (!has_next) break;
     idx = next;
     buf = idle;
@@ -474,11 +537,13 @@ struct EmitPending {
   }
 };
 
-template <class T>
+template <class T, bool FILT>
 __device__ __forceinline__ void scan_emit_capture(const ScanArgs& a, GemmAcc<T>& acc, const WavePos<T>& w, int64_t m0, int64_t n0,
-                                                  const float (&tau_lane)[T::NT], EmitPending<T>& pd) {
+                                                  const float (&tau_lane)[T::NT], EmitPending<T>& pd,
+                                                  const uint32_t (&fw)[T::MT]) {
   const int rows_left = (int)(a.n - m0 < (int64_t)T::TR ? a.n - m0 : (int64_t)T::TR);
-  if (rows_left < T::TR) {   // the last passage tile: rows past n scored 0 (zero-filled operand) and must never hit
+  if constexpr (FILT) filter_acc<T>(acc, fw, w, a.n - m0, IP_MASKED_EMIT);   // masked rows and rows past n: NaN, never a hit
+  if (!FILT && rows_left < T::TR) {   // the last passage tile: rows past n scored 0 (zero-filled operand) and must never hit
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt)
 #pragma unroll
@@ -568,7 +633,7 @@ __device__ __forceinline__ void scan_emit_flush(const ScanArgs& a, const WavePos
 // The emitting scan of 256 x 256 tiles on the 3 R-slot / 2 L-slot main loop (gemm_nt_mainloop_r3); same persistent walk,
 // next-tile prologue under the epilogue and one-tile-ahead thresholds as k_ip_scan.  (The split-bf16 scan and the
 // sampling modes stay on the two-stage loop.)
-template <class T, bool F16>
+template <class T, bool F16, bool FILT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // the 256 x 128 tile serves scans with ONE query tile (at most 128 queries): every passage chunk is read exactly once,
@@ -604,6 +669,15 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
     }
   };
   load_tau(n0);
+  uint32_t fw_next[T::MT] = {};   // FILT: the tile's bitmap words, one tile ahead like the thresholds (see k_ip_scan)
+  auto load_bits = [&](int64_t m0_) {
+    if constexpr (FILT) {
+      static_assert(T::MT == 4, "one uint4 of bitmap words per wave");
+      const uint4 v = *(const uint4*)(a.bits + (m0_ >> 5) + w.wr * T::MT);
+      fw_next[0] = v.x; fw_next[1] = v.y; fw_next[2] = v.z; fw_next[3] = v.w;
+    }
+  };
+  load_bits(m0);
   EmitPending<T> pend;
   pend.clear();
   for (;;) {
@@ -612,9 +686,16 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
     float tau_lane[T::NT];
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) tau_lane[nt] = tau_next[nt];
+    uint32_t fw[T::MT];
+#pragma unroll
+    for (int mt = 0; mt < T::MT; ++mt) fw[mt] = fw_next[mt];
     slots = gemm_nt_mainloop_r3<T, F16, P_AUX>(src, a.d, smem, acc, w, slots, true, false, a.dbg_prelanded != 0);
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_lane[nt]));
+    if constexpr (FILT) {
+#pragma unroll
+      for (int mt = 0; mt < T::MT; ++mt) asm volatile("" : "+v"(fw[mt]));
+    }
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));
     const WavePos<T> we(tid_e);
@@ -625,10 +706,11 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
     if (has_next) {
       coords(next, ts, m0, n0);
       load_tau(n0);
+      load_bits(m0);
       src = TileSrcAll<T>(a.P, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
       gemm_r3_prologue<T, P_AUX>(src, a.d, smem, w, slots);
     }
-    scan_emit_capture<T>(a, acc, we, m0_cur, n0_cur, tau_lane, pend);
+    scan_emit_capture<T, FILT>(a, acc, we, m0_cur, n0_cur, tau_lane, pend, fw);
     if (!has_next) break;
     idx = next;
   }
@@ -1133,26 +1215,26 @@ static IpPlan ip_plan(int nq, int64_t n, int d, int k, int cap) {
   return p;
 }
 
-template <int MODE, class T, int PASSES, bool F16>
+template <int MODE, class T, int PASSES, bool F16, bool FILT>
 static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
   const unsigned tiles = (unsigned)a.nPt * (unsigned)a.nQt;
   if constexpr (MODE == IP_MODE_EMIT && PASSES == 1) {   // the two-stage loop
     constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
     static DeviceOnce attr3;  // > 48 KB dynamic LDS needs the opt-in once per kernel and device
     if (attr3.first())
-      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, R3_SMEM));
+      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16, FILT>, hipFuncAttributeMaxDynamicSharedMemorySize, R3_SMEM));
     ScanArgs b = a;
 #ifdef CONVDR_ENABLE_TRACE   // timing only (every threshold = +inf: results are garbage): `make TRACE=1` library only
     if (getenv("CONVDR_DBG_SCAN_NOEMIT")) b.nq = 0;
     if (getenv("CONVDR_DBG_PRELANDED")) b.dbg_prelanded = 1;
 #endif
     ProfScope prof("ip_scan_emit", st);
-    hipLaunchKernelGGL((k_ip_scan_r3<T, F16>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS), R3_SMEM, st, b);
+    hipLaunchKernelGGL((k_ip_scan_r3<T, F16, FILT>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS), R3_SMEM, st, b);
     CONVDR_CHECK_LAUNCH("k_ip_scan_r3");
   } else {
     static DeviceOnce attr_done;
     if (attr_done.first())
-      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, PASSES, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan<MODE, T, PASSES, F16, FILT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            T::SMEM_BYTES));
     const unsigned slots = (unsigned)device_cu_count() * (T::SMEM_BYTES > 80 * 1024 ? 1u : 2u);
     const unsigned grid = std::min(tiles, slots);
@@ -1162,29 +1244,33 @@ static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
     static const bool no_emit = getenv("CONVDR_DBG_SCAN_NOEMIT") != nullptr;   // timing only: every threshold = +inf
     if (no_emit) b.nq = 0;
 #endif
-    hipLaunchKernelGGL((k_ip_scan<MODE, T, PASSES, F16>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
+    hipLaunchKernelGGL((k_ip_scan<MODE, T, PASSES, F16, FILT>), dim3(grid), dim3(T::THREADS), T::SMEM_BYTES, st, b);
     CONVDR_CHECK_LAUNCH("k_ip_scan");
   }
   return 0;
 }
 
-template <int MODE, class T, bool F16>
+template <int MODE, class T, bool F16, bool FILT>
 static int launch_scan_t(const ScanArgs& a, hipStream_t st) {
   if (a.two_pass) {
-    if constexpr (F16) return launch_scan_x<MODE, T, 2, F16>(a, st);
+    if constexpr (F16) return launch_scan_x<MODE, T, 2, F16, FILT>(a, st);
     CONVDR_REQUIRE(false, "convdr_ip_search: the two-pass scan exists for fp16 only");
   }
-  return a.Plo ? launch_scan_x<MODE, T, 3, F16>(a, st) : launch_scan_x<MODE, T, 1, F16>(a, st);
+  return a.Plo ? launch_scan_x<MODE, T, 3, F16, FILT>(a, st) : launch_scan_x<MODE, T, 1, F16, FILT>(a, st);
 }
 
-template <int MODE, bool F16>
+template <int MODE, bool F16, bool FILT>
 static int launch_scan_k(const ScanArgs& a, int tile, hipStream_t st) {
-  if (tile == IP_TILE_256) return launch_scan_t<MODE, Tile256, F16>(a, st);
-  return launch_scan_t<MODE, TileTall, F16>(a, st);
+  if (tile == IP_TILE_256) return launch_scan_t<MODE, Tile256, F16, FILT>(a, st);
+  return launch_scan_t<MODE, TileTall, F16, FILT>(a, st);
+}
+template <int MODE, bool FILT>
+static int launch_scan_f(const ScanArgs& a, int tile, int kind, hipStream_t st) {
+  return kind == IP_KIND_F16 ? launch_scan_k<MODE, true, FILT>(a, tile, st) : launch_scan_k<MODE, false, FILT>(a, tile, st);
 }
 template <int MODE>
-static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) {
-  return kind == IP_KIND_F16 ? launch_scan_k<MODE, true>(a, tile, st) : launch_scan_k<MODE, false>(a, tile, st);
+static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) {   // a.bits selects the filtered kernels
+  return a.bits ? launch_scan_f<MODE, true>(a, tile, kind, st) : launch_scan_f<MODE, false>(a, tile, kind, st);
 }
 
 }  // namespace convdr
@@ -1602,10 +1688,14 @@ extern "C" const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, i
 
 // rows_f16: the half store -- p_f32 is not used, the re-score reads p_bf16 (halves of 2^s v, p_scale = 2^s) and
 // two_pass selects its second rung (no remainder copy: p_bf16_lo is NULL).
+// row_bits: the row filter (convdr_ip_search_filtered; NULL = every row, and then n_allowed is not read).  The scan emits
+// allowed rows only and samples -inf for the others; the finishing kernels take n_allowed where they took n (need = min(k,
+// n_allowed)); n_allowed <= cap: every allowed row is a candidate -- no threshold pass, tau = -inf.
 static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_bf16,
                      const void* p_bf16_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
                      int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                     float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false) {
+                     float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false,
+                     const uint32_t* row_bits = nullptr, int64_t n_allowed = -1) {
   CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
   CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search: need d %% 64 == 0 and d <= 4096 (got %d)", d);
   CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search: block too large (n=%lld >= 2^31)", (long long)n);
@@ -1615,6 +1705,8 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
   const IpPlan p = ip_plan(nq, n, d, k, cap);
   CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_ip_search: workspace too small (%zu < %zu)", workspace_bytes,
                  p.total);
+  const int64_t n_need = row_bits ? n_allowed : n;        // rows the result can hold: need = min(k, n_need)
+  const bool all_candidates = p.mode < 0 || (row_bits && n_allowed <= cap);
   char* ws = (char*)workspace;
   bf16_t* qb = (bf16_t*)(ws + p.o_qb);
   float* qnorm = (float*)(ws + p.o_qnorm);
@@ -1646,9 +1738,10 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
     a.P = (const bf16_t*)p_bf16; a.Qb = qb; a.Plo = (const bf16_t*)p_bf16_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad; a.d = d;
     a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = cand_id; a.cand_s = cand_s; a.cap = cap; a.T = T;
     a.two_pass = two_pass ? 1 : 0;
+    a.bits = row_bits;
     if (tau_in) {
       CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
-    } else if (p.mode < 0) {
+    } else if (all_candidates) {
       hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
       CONVDR_CHECK_LAUNCH("k_fill_f32");
     } else {
@@ -1695,11 +1788,11 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
   if (g_ip_fused_finish && n > 0) {
     ProfScope prof("ip_finish", st);
     if (rows_f16)
-      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n, k, cap, counts,
+      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n_need, k, cap, counts,
                          (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs, p_scale,
                          IP_F16_NORM_LIMIT, q_f32, (const _Float16*)p_bf16, d, band, status, tau_retry, D, I, unscale);
     else
-      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n, k, cap, counts,
+      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n_need, k, cap, counts,
                          (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs,
                          kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, q_f32, p_f32, d,
                          band, status, tau_retry, D, I, 1.0);
@@ -1708,7 +1801,7 @@ static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const 
   }
   {
   ProfScope prof("ip_cut", st);
-  hipLaunchKernelGGL(k_ip_cut, dim3(nq), dim3(1024), (size_t)cap * 8, st, n, k, cap, counts,
+  hipLaunchKernelGGL(k_ip_cut, dim3(nq), dim3(1024), (size_t)cap * 8, st, n_need, k, cap, counts,
                      (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm,
                      p_max_norm, eps_coef, eps_abs,
                      kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, band, status,
@@ -1794,4 +1887,43 @@ extern "C" int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void*
                  "convdr_ip_search_deep_h16: p_scale must be a power of two >= 1 (got %g)", (double)p_scale);
   return ip_search_deep(IP_KIND_F16, p_scale, q_f32, nq, nullptr, store_f16, nullptr, n, d, k, p_max_norm, tau_in, cap,
                         rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, true, two_pass != 0);
+}
+
+// ---- row-filtered search: the six entries above restricted to the rows whose bit is set ------------------------------
+extern "C" int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, const float* p_f32, const void* p_half,
+                                         const void* p_half_lo, float p_scale, int two_pass, int64_t n, int d, int k,
+                                         const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
+                                         size_t workspace_bytes, const uint32_t* row_bits, int64_t row_bits_words,
+                                         int64_t n_allowed, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                                         convdr_stream_t stream) {
+  CONVDR_REQUIRE(store >= 0 && store <= 2 && (deep == 0 || deep == 1),
+                 "convdr_ip_search_filtered: store must be 0 (bf16 copy), 1 (fp16 copy) or 2 (half store) and deep 0 or 1 "
+                 "(got store=%d deep=%d)", store, deep);
+  CONVDR_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "convdr_ip_search_filtered: bad block size n=%lld", (long long)n);
+  CONVDR_REQUIRE(row_bits != nullptr, "convdr_ip_search_filtered: row_bits is NULL");
+  CONVDR_REQUIRE(((uintptr_t)row_bits & 15u) == 0, "convdr_ip_search_filtered: row_bits must be 16-byte aligned (the scan reads "
+                 "four words at a time)");
+  const int64_t words = ceil_div64(n, 256) * 8;
+  CONVDR_REQUIRE(row_bits_words >= words,
+                 "convdr_ip_search_filtered: the bitmap holds %lld words, n=%lld rows need %lld (whole 256-row tiles, zero padded)",
+                 (long long)row_bits_words, (long long)n, (long long)words);
+  CONVDR_REQUIRE(n_allowed >= 0 && n_allowed <= n, "convdr_ip_search_filtered: n_allowed=%lld outside [0, n=%lld]",
+                 (long long)n_allowed, (long long)n);
+  CONVDR_REQUIRE(two_pass == 0 || (two_pass == 1 && store == 2),
+                 "convdr_ip_search_filtered: two_pass=%d (0, or 1 with the half store)", two_pass);
+  CONVDR_REQUIRE(store != 2 || p_half_lo == nullptr, "convdr_ip_search_filtered: the half store has no remainder copy");
+  if (store == 0) p_scale = 1.f;
+  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && (store != 2 || p_scale >= 1.f),
+                 "convdr_ip_search_filtered: p_scale must be a power of two%s (got %g)", store == 2 ? " >= 1" : "", (double)p_scale);
+  const int kind = store == 0 ? IP_KIND_BF16 : IP_KIND_F16;
+  const bool rows_f16 = store == 2;
+  // no allowed row: the empty block's path (no scan; the finishing kernels pad every row of D / I)
+  const int64_t n_run = n_allowed == 0 ? 0 : n;
+  if (deep)
+    return ip_search_deep(kind, p_scale, q_f32, nq, rows_f16 ? nullptr : p_f32, p_half, p_half_lo, n_run, d, k, p_max_norm, tau_in,
+                          cap, rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, rows_f16,
+                          two_pass != 0, row_bits, n_allowed);
+  return ip_search(kind, p_scale, q_f32, nq, rows_f16 ? nullptr : p_f32, p_half, p_half_lo, n_run, d, k, p_max_norm, tau_in, cap,
+                   rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, rows_f16, two_pass != 0,
+                   row_bits, n_allowed);
 }

@@ -12,6 +12,7 @@ Mirrors, name for name, what the reference does with FAISS:
 All scoring / selection runs in libconvdr_hip.so (csrc/ip_topk.hip).
 """
 import collections
+import functools
 import json
 import os
 import pickle
@@ -37,8 +38,45 @@ HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM
 
 _Depth = collections.namedtuple("_Depth", "enqueue max_cap shortcut last_rung last_stat deep_stats")
 # what search_begin hands to search_finish: depth None = k > DEEP_MAX_K (nothing enqueued), first = (D, I, status, tau_retry) of
-# the enqueued first pass or None (deep search of an empty index)
-_Pending = collections.namedtuple("_Pending", "qt k depth x3 cap first")
+# the enqueued first pass or None (nothing to scan: deep search of an empty index, or a filter that allows no row),
+# allowed = the RowFilter of a restricted search or None
+_Pending = collections.namedtuple("_Pending", "qt k depth x3 cap first allowed", defaults=(None,))
+
+ROW_FILTER_TILE = 256       # the bitmap covers whole scan tiles of this many rows (csrc/ip_topk.hip: Tile256::TR)
+
+
+def pack_row_mask(mask):
+    """bool / uint8 vector [n] (a torch tensor, on any device) -> the bitmap of convdr_ip_search_filtered: int32 words (the bytes
+    of uint32), row r allowed iff bit r & 31 of word r >> 5 is set, zero padded to whole 256-row tiles (ceil(n / 256) * 8 words).
+    Torch ops on the mask's device: eight rows make a byte (least significant bit first), four bytes a little-endian word."""
+    import torch
+    m = mask.reshape(-1) != 0
+    n = int(m.numel())
+    padded = (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * ROW_FILTER_TILE
+    if padded != n:
+        m = torch.cat([m, torch.zeros(padded - n, dtype=torch.bool, device=m.device)])
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=m.device)
+    by = (m.view(-1, 8).to(torch.int32) * weights).sum(1).to(torch.uint8)         # (at most 255)
+    return by.contiguous().view(torch.int32)
+
+
+class RowFilter:
+    """An allowed subset of an index's rows (FlatIPIndex.row_filter): `bits` the device bitmap (pack_row_mask), `n` the ntotal
+    it was built for -- searching an index of another size with it raises ValueError --, `n_allowed` the number of allowed rows."""
+
+    def __init__(self, bits, n, n_allowed):
+        self.bits, self.n, self.n_allowed = bits, int(n), int(n_allowed)
+        self._rows = None
+
+    def rows(self):
+        """ascending ids of the allowed rows (device int64 [n_allowed]), unpacked from the bitmap on first use: the last rungs
+        of the ladder rank explicit row lists"""
+        import torch
+        if self._rows is None:
+            by = self.bits.view(torch.uint8).to(torch.int32)
+            shifts = torch.arange(8, dtype=torch.int32, device=by.device)
+            self._rows = torch.nonzero(((by[:, None] >> shifts) & 1).reshape(-1)[:self.n]).flatten()
+        return self._rows
 
 
 class FlatIPIndex:
@@ -501,6 +539,30 @@ class FlatIPIndex:
         with torch.cuda.device(self.device):
             self._prepare_into(dst32, dstbf, dstlo)
 
+    def row_filter(self, mask):
+        """A RowFilter of this index from a bool / uint8 vector [ntotal] (numpy or torch, host or device; non-zero = allowed):
+        packed on the index's device with torch ops, the allowed count read ONCE, here (one host round trip at build time, none
+        per search).  Pass it as ``allowed=`` to search / search_tensors / search_begin / search_device / search_deep_device.
+        Valid while ntotal stays what it was: update_rows keeps it, add and reset do not."""
+        import torch
+        m = torch.as_tensor(mask)
+        if m.dim() != 1 or int(m.numel()) != self.ntotal:
+            raise ValueError("row_filter: the mask must be a vector of ntotal = %d entries (got shape %s)"
+                             % (self.ntotal, tuple(m.shape)))
+        m = m.to(self.device) != 0
+        return RowFilter(pack_row_mask(m), self.ntotal, int(m.sum().item()))
+
+    def _filter(self, allowed):
+        """allowed= of a search call -> None or a RowFilter that fits this index"""
+        if allowed is None:
+            return None
+        if not isinstance(allowed, RowFilter):
+            return self.row_filter(allowed)
+        if allowed.n != self.ntotal or allowed.bits.device != self.device:
+            raise ValueError("stale RowFilter: built for ntotal = %d on %s, the index holds %d rows on %s"
+                             % (allowed.n, allowed.bits.device, self.ntotal, self.device))
+        return allowed
+
     def _workspace(self, nbytes):
         import torch
         if self._ws is None or self._ws.numel() < nbytes:
@@ -508,9 +570,18 @@ class FlatIPIndex:
         return self._ws
 
     def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
-                     deep=False):
-        """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth."""
+                     deep=False, allowed=None):
+        """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth; with a
+        RowFilter, convdr_ip_search_filtered with the same operands."""
         ptr = _lib.ptr
+        if allowed is not None:
+            store = 2 if self._half else (1 if self.kind == "f16" else 0)
+            _lib.check(_lib.lib().convdr_ip_search_filtered(
+                store, int(bool(deep)), ptr(q), nq, None if self._half else ptr(p32), ptr(p16), None if self._half else ptr(plo),
+                float(self._scale) if store else 1.0, int(bool(split)) if self._half else 0, n, self.d, k, ptr(self._max_norm),
+                ptr(tau_in), cap, rank_target, ptr(ws), ws.numel(), ptr(allowed.bits), allowed.bits.numel(), allowed.n_allowed,
+                ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr()), "convdr_ip_search_filtered")
+            return
         if self._half:
             name, rows = "_h16", (ptr(p16), float(self._scale), int(bool(split)))
         elif self.kind == "f16":
@@ -522,7 +593,7 @@ class FlatIPIndex:
                                              ptr(ws), ws.numel(), ptr(D), ptr(I), ptr(status), ptr(tau_retry),
                                              _lib.stream_ptr()), name)
 
-    def _enqueue(self, q, k, tau_in, cap, x3, deep=False, rows=None, rank_target=None):
+    def _enqueue(self, q, k, tau_in, cap, x3, deep=False, rows=None, rank_target=None, allowed=None):
         """One enqueue of the kernel pipeline, shallow or deep, over the resident block or over `rows` = (re-score rows, scan
         copy) of an exhaustive slice: allocates (D, I, status, tau_retry), sizes the workspace and calls the entry.  No sync.
         Memory bound of the deep pipeline: its workspace is ~ nq * cap * 28 bytes (list id + scan score, band id + fp64 score,
@@ -554,16 +625,18 @@ class FlatIPIndex:
         rank_target = self.rank_target if rank_target is None else rank_target
         with torch.cuda.device(self.device):
             if step >= nq:
-                self._search_call(q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, x3, deep)
+                self._search_call(q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, x3, deep,
+                                  allowed)
             else:
                 for a in range(0, nq, step):
                     b = min(nq, a + step)
                     self._search_call(q[a:b], b - a, p32, p16, plo, n, k, None if tau_in is None else tau_in[a:b], cap, rank_target,
-                                      ws, D[a:b], I[a:b], status[a:b], tau_retry[a:b], x3, deep)
+                                      ws, D[a:b], I[a:b], status[a:b], tau_retry[a:b], x3, deep, allowed)
         return D, I, status, tau_retry
 
-    def search_device(self, q, k, tau_in=None, cap=None, x3=None):
-        """One enqueue of the kernel pipeline; q is a device fp32 [nq, d] tensor.
+    def search_device(self, q, k, tau_in=None, cap=None, x3=None, allowed=None):
+        """One enqueue of the kernel pipeline; q is a device fp32 [nq, d] tensor.  allowed: a RowFilter (or a mask, packed for
+        this call): only its rows can be returned, and the certificate holds over them.
         Returns device tensors (D, I, status, tau_retry); no sync.
         status (per query): 0 = certified exact; 1 / 2 / 3 = not certified, re-run with tau_retry (search_tensors walks that
         ladder); 4 = CONVDR_IP_RANGE, fp16 rungs only: the scan copy was built with a scale that later, longer rows (or an
@@ -573,7 +646,7 @@ class FlatIPIndex:
         cap = cap or self.cap
         while cap < 2 * k and cap < 8192:      # the candidate list holds at least 2k entries (csrc/ip_topk.hip: k <= cap / 2)
             cap *= 2
-        return self._enqueue(q, k, tau_in, cap, self.precision in _SPLIT if x3 is None else x3)
+        return self._enqueue(q, k, tau_in, cap, self.precision in _SPLIT if x3 is None else x3, allowed=self._filter(allowed))
 
     def last_counts(self, nq, k, cap=None):
         """(emitted, band) int32 tensors [nq] of the last search_device call (instrumentation)."""
@@ -585,10 +658,12 @@ class FlatIPIndex:
             out.append(self._ws[off:off + 4 * nq].view(_torch().int32))
         return tuple(out)
 
-    def _certify(self, depth, qt, k, D, I, status, tau_retry, x3, cap):
+    def _certify(self, depth, qt, k, D, I, status, tau_retry, x3, cap, kw=None):
         """Host loop around the kernel's certificate: re-run the queries that are not OK with the threshold the kernel
-        proposes, the candidate capacity doubled on OVERFLOW up to the depth's limit.  Returns the indices still uncertified."""
+        proposes, the candidate capacity doubled on OVERFLOW up to the depth's limit.  Returns the indices still uncertified.
+        kw: None or {"allowed": RowFilter}, handed to every enqueue."""
         import torch
+        kw = kw or {}
         st = status.cpu().numpy()
         bad = np.nonzero(st != 0)[0]
         rounds = 0
@@ -603,29 +678,31 @@ class FlatIPIndex:
                 cap *= 2
                 if depth.deep_stats:
                     self.stats["deep_cap"] = max(self.stats["deep_cap"], cap)
-            Db, Ib, sb, tb = getattr(self, depth.enqueue)(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3)
+            Db, Ib, sb, tb = getattr(self, depth.enqueue)(qt[idx].contiguous(), k, tau_in=tau, cap=cap, x3=x3, **kw)
             D[idx], I[idx], tau_retry[idx] = Db, Ib, tb
             sb = sb.cpu().numpy()
             st[bad] = sb
             bad = bad[sb != 0]
         return bad
 
-    def search(self, q, k):
+    def search(self, q, k, allowed=None):
         """FAISS ``index.search``: numpy in, numpy (D, I) out; always the exact top-k (queries no scan can certify take the
-        exhaustive rung, `stats["exhaustive_queries"]`)."""
-        D, I = self.search_tensors(q, k)
+        exhaustive rung, `stats["exhaustive_queries"]`).  allowed: a RowFilter (``row_filter``) or a bool / uint8 mask
+        [ntotal], packed for this call -- the search is restricted to those rows (FAISS ``IDSelector``): the exact top-k of the
+        allowed rows, I in the index's row numbers, padding where fewer than k rows are allowed."""
+        D, I = self.search_tensors(q, k, allowed=allowed)
         return D.cpu().numpy(), I.cpu().numpy()
 
-    def search_tensors(self, q, k):
+    def search_tensors(self, q, k, allowed=None):
         """``search`` with the certified result left on the device (torch fp32 [nq, k], int64 [nq, k]).
 
         precision="auto": the fp16 scan first; queries it cannot certify are re-run -- with a lower threshold while their
         error band still fits the candidate list, with the split scan (4x tighter band) once the band has swallowed
         the whole list.  The index remembers when most queries of a block ended on the split scan and starts there next
         time (`x3_first`)."""
-        return self.search_finish(self.search_begin(q, k))
+        return self.search_finish(self.search_begin(q, k, allowed=allowed))
 
-    def search_begin(self, q, k):
+    def search_begin(self, q, k, allowed=None):
         """First half of search_tensors: the first scan pass is ENQUEUED (no host round trip) and a handle returned;
         search_finish(handle) reads the certificates and walks the ladder for whatever the first pass left open.  Between the
         two the host is free -- search_one_by_one loads the next block file meanwhile."""
@@ -636,35 +713,38 @@ class FlatIPIndex:
         qt = (self._pad_columns(qt) if self.d != self.d_in else qt.to(self.device)).contiguous()
         assert qt.dim() == 2 and qt.shape[1] == self.d
         k = int(k)
+        f = self._filter(allowed)
+        kw = {} if f is None else {"allowed": f}
         if k > self.DEEP_MAX_K:
             # the reference takes any --top_n (run_convdr_inference.py:316-319); the deep kernel pipeline's candidate lists end
             # at 131,072 entries, so larger k takes the chunked host-side route (exact, slow): see _search_large_k
-            return _Pending(qt, k, None, None, None, None)
+            return _Pending(qt, k, None, None, None, None, f)
         x3 = self.precision in _SPLIT or (self.precision == "auto" and getattr(self, "_x3_first", False) and self.ntotal > 0)
         # 4096 < k <= 65536: the same pipeline with the lists in global memory (convdr_ip_search_deep*)
         depth, cap = (self._DEEP, self._deep_cap(k)) if k > self.MAX_K else (self._SHALLOW, self.cap)
-        if depth is self._DEEP and not self.ntotal:
-            return _Pending(qt, k, depth, x3, cap, None)        # (the shallow kernels pad an empty index's result themselves)
-        return _Pending(qt, k, depth, x3, cap, getattr(self, depth.enqueue)(qt, k, cap=cap, x3=x3))
+        if (depth is self._DEEP and not self.ntotal) or (f is not None and f.n_allowed == 0):
+            return _Pending(qt, k, depth, x3, cap, None, f)     # (the shallow kernels pad an empty index's result themselves)
+        return _Pending(qt, k, depth, x3, cap, getattr(self, depth.enqueue)(qt, k, cap=cap, x3=x3, **kw), f)
 
     def search_finish(self, handle):
         """The ladder, at either depth: fp16 (or pinned) first pass -> rebuild on RANGE -> retries with tau_retry / a doubled
         list -> split scan -> whatever is still open takes the depth's last rung."""
         import torch
-        qt, k, depth, x3, cap, first = handle
+        qt, k, depth, x3, cap, first, allowed = handle
+        kw = {} if allowed is None else {"allowed": allowed}    # (allowed=None: today's calls, argument for argument)
         nq = int(qt.shape[0])
         split_key = self._split_key
         self.stats = {"retried": 0, "rounds": 1, "x3_queries": 0, "x3_first": bool(x3), "rescaled": 0}
         self.stats[split_key] = nq if x3 else 0
         if depth is None:
             self.stats.update(rounds=0, large_k=k, deep=0, deep_cap=0, chunked_queries=nq)
-            return self._search_large_k(qt, k)
+            return self._search_large_k(qt, k, **kw)
         if depth.deep_stats:
             self.stats.update(large_k=k, deep=nq, deep_cap=cap, chunked_queries=0)
-        if first is None:               # empty index: FAISS padding
+        if first is None:               # empty index, or no row allowed: FAISS padding
             return (torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device),
                     torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
-        enqueue = getattr(self, depth.enqueue)
+        enqueue = functools.partial(getattr(self, depth.enqueue), **kw)
         D, I, status, tau_retry = first
         n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()   # one host round trip
         if self.kind == "f16" and n_range:
@@ -686,12 +766,12 @@ class FlatIPIndex:
             if len(retry_idx):
                 sub = torch.as_tensor(retry_idx, device=self.device)
                 Db, Ib, sb, tb = D[sub], I[sub], status[sub], tau_retry[sub]
-                left = self._certify(depth, qt[sub].contiguous(), k, Db, Ib, sb, tb, False, cap)
+                left = self._certify(depth, qt[sub].contiguous(), k, Db, Ib, sb, tb, False, cap, kw)
                 D[sub], I[sub] = Db, Ib
                 bad += list(retry_idx[np.asarray(left, dtype=np.int64)]) if len(left) else []
             bad = np.asarray(sorted(bad), dtype=np.int64)
         elif n_bad:
-            bad = self._certify(depth, qt, k, D, I, status, tau_retry, x3, cap)
+            bad = self._certify(depth, qt, k, D, I, status, tau_retry, x3, cap, kw)
         if len(bad) and second:
             # second rung: split scan for the queries the single-pass error band cannot separate
             idx = torch.as_tensor(bad, device=self.device)
@@ -699,7 +779,7 @@ class FlatIPIndex:
             self.stats[split_key] = len(bad)
             Db, Ib, sb, tb = enqueue(qs, k, cap=cap, x3=True)
             self.stats["rounds"] += 1
-            bad2 = self._certify(depth, qs, k, Db, Ib, sb, tb, True, cap) if int((sb != 0).sum().item()) else []
+            bad2 = self._certify(depth, qs, k, Db, Ib, sb, tb, True, cap, kw) if int((sb != 0).sum().item()) else []
             D[idx], I[idx] = Db, Ib
             bad = bad[np.asarray(bad2, dtype=np.int64)] if len(bad2) else []
         if self.precision == "auto":
@@ -711,7 +791,7 @@ class FlatIPIndex:
             # slices are merged in row order (earlier rows win ties): slow (one small launch chain per slice) but always an
             # answer.  Deep: the chunked route of k > DEEP_MAX_K
             idx = torch.as_tensor(np.asarray(bad, dtype=np.int64), device=self.device)
-            Db, Ib = getattr(self, depth.last_rung)(qt[idx].contiguous(), k)
+            Db, Ib = getattr(self, depth.last_rung)(qt[idx].contiguous(), k, **kw)
             D[idx], I[idx] = Db, Ib
             self.stats[depth.last_stat] = len(bad)
             if depth.deep_stats:
@@ -803,13 +883,14 @@ class FlatIPIndex:
             cap *= 2
         return cap
 
-    def search_deep_device(self, q, k, tau_in=None, cap=None, x3=False):
+    def search_deep_device(self, q, k, tau_in=None, cap=None, x3=False, allowed=None):
         """``search_device`` for MAX_K < k <= DEEP_MAX_K: enqueues convdr_ip_search_deep[_f16 | _h16]; device (D, I, status,
         tau_retry) with the meanings of search_device; no sync.  The queries are split under DEEP_WS_BYTES (see _enqueue)."""
         cap = int(cap or self._deep_cap(k))
-        if self.ntotal <= cap:
+        allowed = self._filter(allowed)
+        if self.ntotal <= cap or (allowed is not None and allowed.n_allowed <= cap):
             tau_in = None               # every row is a candidate: the list is complete whatever threshold a retry proposes
-        return self._enqueue(q, k, tau_in, cap, x3, deep=True)
+        return self._enqueue(q, k, tau_in, cap, x3, deep=True, allowed=allowed)
 
     def _exact_slice(self, rows, kq, qq, cap):
         """Top-kq of the slice `rows` = (re-score rows, scan copy) of at most `cap` rows: the plan takes every row as a candidate
@@ -819,7 +900,22 @@ class FlatIPIndex:
             raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % rows[1].shape[0])
         return D, I
 
-    def _search_large_k(self, q, k, q_chunk=8):
+    def _row_chunks(self, step, allowed):
+        """The rows the last rungs rank, in ascending chunks of at most `step`: ((re-score rows, scan copy), back) per chunk,
+        where back maps a chunk-local index tensor I >= 0 to row numbers.  Without a filter the chunks are slices of the
+        resident block; with one they are gathered from the ascending list of allowed row ids -- ascending chunks keep the rule
+        that the earlier row wins a tie, and no filtered kernel is needed."""
+        if allowed is None:
+            for s0 in range(0, self.ntotal, step):
+                e0 = min(self.ntotal, s0 + step)
+                yield (self._rows[s0:e0], self._pbf[s0:e0]), (lambda I, s0=s0: I + s0)
+        else:
+            ids = allowed.rows()
+            for s0 in range(0, int(ids.numel()), step):
+                chunk = ids[s0:s0 + step]
+                yield self._row_pair(chunk), (lambda I, chunk=chunk: chunk[I])
+
+    def _search_large_k(self, q, k, q_chunk=8, allowed=None):
         """Exact top-k for k > MAX_K (any --top_n, run_convdr_inference.py:316-319) by chunking on the host side of the
         same kernels: every slice of <= 4096 rows is RANKED COMPLETELY by the exhaustive plan (all rows candidates, canonical
         fp64 scores, kq = rows), the slices' sorted lists are merged by a stable descending sort of the fp32-rounded scores
@@ -827,7 +923,7 @@ class FlatIPIndex:
         across slices), and every run of equal fp32 scores that spans slices or straddles rank k is ranked once more as one
         slice.  Slow (n / 4096 launch chains per 8 queries, an [8, n] sort), always the exhaustive exact answer."""
         import torch
-        nq, n = int(q.shape[0]), self.ntotal
+        nq, n = int(q.shape[0]), self.ntotal if allowed is None else allowed.n_allowed      # n: the rows that can be returned
         Dout = torch.full((nq, k), PAD_SCORE, dtype=torch.float32, device=self.device)
         Iout = torch.full((nq, k), -1, dtype=torch.int64, device=self.device)
         if n == 0:
@@ -838,11 +934,10 @@ class FlatIPIndex:
             for j0 in range(0, nq, q_chunk):
                 qq = q[j0:j0 + q_chunk].contiguous()
                 Ds, Is = [], []
-                for s0 in range(0, n, step):
-                    m = min(n, s0 + step) - s0
-                    D, I = self._exact_slice((self._rows[s0:s0 + m], self._pbf[s0:s0 + m]), m, qq, cap)
+                for pair, back in self._row_chunks(step, allowed):
+                    D, I = self._exact_slice(pair, int(pair[1].shape[0]), qq, cap)
                     Ds.append(D)
-                    Is.append(I + s0)
+                    Is.append(back(I))
                 Dall, Iall = torch.cat(Ds, 1), torch.cat(Is, 1)
                 order = torch.sort(Dall, dim=1, descending=True, stable=True).indices
                 Dall, Iall = torch.gather(Dall, 1, order), torch.gather(Iall, 1, order)
@@ -867,9 +962,9 @@ class FlatIPIndex:
                     Dout[j0 + j, :kk], Iout[j0 + j, :kk] = d[:kk], i[:kk]
         return Dout, Iout
 
-    def _search_exhaustive(self, q, k):
+    def _search_exhaustive(self, q, k, allowed=None):
         import torch
-        nq, n = int(q.shape[0]), self.ntotal
+        nq = int(q.shape[0])
         kk = min(2 * k, 4096)           # candidates carried through the merges (see the re-ranking below)
         cap = 4096
         while cap < 2 * kk:
@@ -878,10 +973,9 @@ class FlatIPIndex:
 
         merged = None
         with torch.cuda.device(self.device):
-            for s0 in range(0, n, step):
-                e0 = min(n, s0 + step)
-                D, I = self._exact_slice((self._rows[s0:e0], self._pbf[s0:e0]), kk, q, cap)
-                I = torch.where(I >= 0, I + s0, I)
+            for pair, back in self._row_chunks(step, allowed):
+                D, I = self._exact_slice(pair, kk, q, cap)
+                I = torch.where(I >= 0, back(I.clamp_min(0)), I)
                 merged = (D, I) if merged is None else tuple(t[:, :kk].contiguous() for t in merge_topk_device(merged, (D, I), kk))
             # The merges compare the fp32-rounded scores; the result's order is defined on the canonical fp64 scores (two
             # rows whose scores round to the same fp32 value are NOT a tie).  So each query's <= 2k survivors -- a superset
@@ -889,7 +983,7 @@ class FlatIPIndex:
             Dout = torch.empty((nq, k), dtype=torch.float32, device=self.device)
             Iout = torch.empty((nq, k), dtype=torch.int64, device=self.device)
             for j in range(nq):
-                rows = merged[1][j]
+                rows = merged[1][j] if merged is not None else Iout.new_empty(0)
                 rows = torch.sort(rows[rows >= 0]).values
                 m = int(rows.numel())
                 if m == 0:

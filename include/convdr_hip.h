@@ -174,6 +174,37 @@ int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void* store_f16,
                               size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
                               convdr_stream_t stream);
 
+/* Row-filtered search: any of the six entries above restricted to an allowed subset of the block's rows (what FAISS calls an
+ * IDSelector: deleted rows, a sub-collection, a top-k that must not contain known positives).
+ *   bitmap       row_bits: device uint32 words, 16-BYTE ALIGNED (the scan reads a wave's four words as one 16-byte load; any
+ *                hipMalloc pointer is); row r is allowed iff bit (r & 31) of word (r >> 5) is set.  The bitmap covers
+ *                whole 256-row scan tiles, zero padded: row_bits_words >= ceil(n / 256) * 8, and the bits of the rows past n are
+ *                zero (the scan does not trust them: a set bit past n is ignored).
+ *   n_allowed    the number of set bits among rows 0..n-1, a HOST value the library cannot check (it would cost a device round
+ *                trip per search): it takes n's place in need = min(k, n_allowed) -- padding with -FLT_MAX / -1 begins there,
+ *                TOO_FEW means fewer than that many candidates -- and n_allowed <= cap selects the one-pass plan: every allowed
+ *                row is a candidate, no threshold sample, tau = -inf.  A wrong n_allowed gives wrong padding or a status that
+ *                never clears, never an out-of-bounds access: the list is bounded by cap and only rows < n are ever named.
+ *                n_allowed == 0: no scan, D / I are all padding.
+ *   scan         a row whose bit is clear never becomes a candidate, whatever the threshold is, and counts as -inf in the
+ *                threshold samples (which therefore estimate ranks among the allowed rows).
+ *   certificate  unchanged, over the allowed rows: the list holds every ALLOWED row with S~ >= tau, cut = S~(k) - 2 eps is taken
+ *                over allowed rows, and OK means the list is complete down to the cut -- the result is the exhaustive exact
+ *                top-k of the allowed rows, canonical fp64 scores, (score desc, index asc); I holds row indices of the block.
+ *   store, deep  store = 0: the bf16 scan copy (convdr_ip_search[_deep]; p_scale and two_pass are not read / must be 0);
+ *                store = 1: the fp16 scan copy (.._f16; p_scale a power of two); store = 2: the half store (.._h16; p_half is
+ *                the store, p_f32 is not read, p_half_lo must be NULL, p_scale a power of two >= 1, two_pass 0 or 1).
+ *                deep = 0 / 1: the shallow or the deep entry, with that entry's contract for cap and k and its workspace size
+ *                (convdr_ip_workspace_bytes / convdr_ip_deep_workspace_bytes, planned by n, not by n_allowed).
+ * Every other argument, output and status word is the matching entry's; both settings of the option ip_fused_finish work.
+ * Arguments are validated before anything touches a device (row_bits != NULL and 16-byte aligned, row_bits_words, 0 <= n_allowed <= n, store and
+ * deep in range, then the matching entry's size contracts). */
+int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, const float* p_f32, const void* p_half,
+                              const void* p_half_lo, float p_scale, int two_pass, int64_t n, int d, int k, const float* p_max_norm,
+                              const float* tau_in, int cap, int rank_target, void* workspace, size_t workspace_bytes,
+                              const uint32_t* row_bits, int64_t row_bits_words, int64_t n_allowed, float* D, int64_t* I,
+                              int32_t* status, float* tau_retry, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
