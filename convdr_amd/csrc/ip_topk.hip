@@ -1927,3 +1927,6 @@ extern "C" int convdr_ip_search_filtered(int store, int deep, const float* q_f32
                    rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, rows_f16, two_pass != 0,
                    row_bits, n_allowed);
 }
+
+// ---- range search: every row scoring above a per-query radius (convdr_ip_range_*) -------------------------------------
+#include "ip_range.hpp"

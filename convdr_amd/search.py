@@ -995,6 +995,201 @@ class FlatIPIndex:
                 Iout[j] = torch.where(Ij[0] >= 0, rows[Ij[0].clamp_min(0)], Ij[0])
         return Dout, Iout
 
+    # -- range search: every row scoring above a per-query radius ----------------------------------------------------
+    RANGE_MAX_CAP = 131072      # longest candidate list of convdr_ip_range_search (a power of two); beyond it: row slices
+
+    def range_search(self, q, radius, allowed=None):
+        """FAISS ``index.range_search`` with one radius per query: numpy ``(lims int64 [nq + 1], D float32, I int64)``; query j
+        owns D / I [lims[j], lims[j + 1]) = every row whose canonical fp64 score is STRICTLY greater than float64(radius[j]),
+        ordered by (score desc, row asc); D is that score rounded to fp32 (so it may equal the radius for a score above it by
+        less than half an ulp).  radius: a float, or an fp32 vector [nq] (numpy or torch, host or device); a wrong length or a
+        NaN raises ValueError.  allowed: a RowFilter or a mask, as for ``search`` -- the same set intersected with the allowed
+        rows.  Exact whatever the store and the precision (include/convdr_hip.h, "Range search")."""
+        lims, D, I = self.range_search_tensors(q, radius, allowed=allowed)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    def range_search_tensors(self, q, radius, allowed=None):
+        """``range_search`` with the result left on the device.
+
+        The ladder is a host loop with ONE host read (status, counts, total) per pass: the first pass lists up to ``self.cap``
+        rows per query; a query whose scan hit more is re-run at the smallest power of two that holds its reported hit count
+        (exact: no doubling), up to RANGE_MAX_CAP; CONVDR_IP_RANGE rebuilds the scan copy once (as search_finish).  Queries
+        with more than RANGE_MAX_CAP hits take the last rung: the index is searched in row slices of at most RANGE_MAX_CAP
+        rows (with a filter: slices of the ascending allowed rows), none of which can overflow, and the slices are merged on
+        the device by the fp64 scores.  Memory bound of that rung: the result itself (fp64 score, row and query number per
+        result row while merging) beside one call's workspace, which stays under DEEP_WS_BYTES.
+        ``stats``: range_results, range_rounds (passes), range_cap (the longest list used), range_chunked_queries."""
+        return self._range(q, radius, allowed, False)
+
+    def range_count(self, q, radius, allowed=None):
+        """int64 numpy [nq]: how many rows ``range_search`` would return per query, without ordering or packing them
+        (1 + range_count(q, score of a known positive) is that positive's exact rank in the whole index)."""
+        return self._range(q, radius, allowed, True)
+
+    def _range_radius(self, radius, nq):
+        import torch
+        r = torch.as_tensor(radius)
+        if r.dim() == 0:
+            r = r.reshape(1).expand(nq)
+        elif r.dim() != 1 or int(r.numel()) != nq:
+            raise ValueError("range_search: radius must be a number or a vector of nq = %d entries (got shape %s)"
+                             % (nq, tuple(r.shape)))
+        r = r.to(torch.float32).to(self.device).contiguous()
+        if nq and bool(torch.isnan(r).any()):
+            raise ValueError("range_search: a radius is NaN")
+        return r
+
+    def _range_step(self, nq, n, cap):
+        """queries per call, so that one call's workspace stays under DEEP_WS_BYTES (as _enqueue splits the deep search)"""
+        ws_bytes = _lib.lib().convdr_ip_range_workspace_bytes
+        step = nq
+        while step > 1 and ws_bytes(step, n, self.d, cap) > self.DEEP_WS_BYTES:
+            step = (step + 1) // 2
+        if not ws_bytes(step, n, self.d, cap):
+            raise _lib.ConvdrError("convdr_ip_range_search: sizes outside the contract (nq=%d n=%d d=%d cap=%d)" % (nq, n, self.d, cap))
+        return step
+
+    def _range_pass(self, q, rad, cap, count_only, allowed=None, rows=None, want_x=False):
+        """One pass of convdr_ip_range_search (+ convdr_ip_range_pack) over the resident block, or over `rows` = (re-score rows,
+        scan copy) of a slice.  Returns (counts int64 numpy [nq], status numpy [nq], lims, D, I, X): the device result of the
+        queries whose status is OK (the others own an empty run); lims / D / I / X are None when count_only, X unless want_x.
+        One host read per call (status, counts and the total that sizes D and I)."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        p32, p16 = (self._rows, self._pbf) if rows is None else rows
+        nq, n = int(q.shape[0]), int(p16.shape[0])
+        store = 2 if self._half else (1 if self.kind == "f16" else 0)
+        step = self._range_step(nq, n, cap)
+        ws = self._workspace(L.convdr_ip_range_workspace_bytes(step, n, self.d, cap))
+        bits = None if allowed is None else allowed.bits
+        counts, status, parts = [], [], []
+        with torch.cuda.device(self.device):
+            for a in range(0, nq, step):
+                b = min(nq, a + step)
+                out = torch.empty(3 * (b - a) + 1, dtype=torch.int64, device=self.device)     # counts | lims | status (int32)
+                cnt, lims, st = out[:b - a], out[b - a:2 * (b - a) + 1], out[2 * (b - a) + 1:].view(torch.int32)[:b - a]
+                _lib.check(L.convdr_ip_range_search(
+                    store, ptr(q[a:b]), b - a, None if self._half else ptr(p32), ptr(p16), float(self._scale) if store else 1.0,
+                    None if self._half else ptr(self._centre), n, self.d, ptr(self._max_norm), ptr(rad[a:b]), cap, int(count_only),
+                    ptr(bits), 0 if bits is None else bits.numel(), ptr(ws), ws.numel(), ptr(cnt), ptr(lims), ptr(st),
+                    _lib.stream_ptr()), "convdr_ip_range_search")
+                host = out.cpu().numpy()                                                       # the pass's one host read
+                counts.append(host[:b - a])
+                status.append(host[2 * (b - a) + 1:].view(np.int32)[:b - a])
+                if count_only:
+                    continue
+                total = int(host[2 * (b - a)])
+                D = torch.empty(total, dtype=torch.float32, device=self.device)
+                I = torch.empty(total, dtype=torch.int64, device=self.device)
+                X = torch.empty(total, dtype=torch.float64, device=self.device) if want_x else None
+                if total:       # (an empty tensor has no storage: its pointer is NULL, which the entry refuses)
+                    _lib.check(L.convdr_ip_range_pack(ptr(ws), b - a, n, self.d, cap, ptr(lims), ptr(D), ptr(I), ptr(X),
+                                                      _lib.stream_ptr()), "convdr_ip_range_pack")
+                parts.append((lims, D, I, X, total))
+        counts, status = np.concatenate(counts), np.concatenate(status)
+        if count_only:
+            return counts, status, None, None, None, None
+        if len(parts) == 1:
+            return (counts, status) + parts[0][:4]
+        offs = np.concatenate([[0], np.cumsum([p[4] for p in parts])])
+        lims = torch.cat([p[0][:-1] + int(o) for p, o in zip(parts, offs)] + [torch.tensor([int(offs[-1])], device=self.device)])
+        return (counts, status, lims, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
+                torch.cat([p[3] for p in parts]) if want_x else None)
+
+    def _range_chunked(self, q, rad, allowed, count_only):
+        """The last rung: row slices of at most RANGE_MAX_CAP rows, each searched by the same entry with a list that holds the
+        whole slice, merged per query into the canonical order -- stable sorts by row, then by fp64 score (descending), then
+        by query.  Returns (counts numpy [nq], lims, D, I)."""
+        import torch
+        nq, cap = int(q.shape[0]), int(self.RANGE_MAX_CAP)
+        counts = np.zeros(nq, np.int64)
+        Xs, Is, Js = [], [], []
+        for pair, back in self._row_chunks(cap, allowed):
+            cnt, st, lims, D, I, X = self._range_pass(q, rad, cap, count_only, rows=pair, want_x=True)
+            if (st != STATUS_OK).any():
+                raise _lib.ConvdrError("convdr_ip_range_search: a slice of %d rows came back with status %s" % (pair[1].shape[0], st))
+            counts += cnt
+            if not count_only:
+                Xs.append(X)
+                Is.append(back(I))
+                Js.append(torch.repeat_interleave(torch.arange(nq, device=self.device), torch.diff(lims)))
+        if count_only:
+            return counts, None, None, None
+        X, I, J = torch.cat(Xs), torch.cat(Is), torch.cat(Js)
+        for key, desc in ((lambda: I, False), (lambda: X, True), (lambda: J, False)):
+            o = torch.sort(key(), stable=True, descending=desc).indices
+            X, I, J = X[o], I[o], J[o]
+        lims = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]), device=self.device)
+        return counts, lims, X.to(torch.float32), I
+
+    def _range(self, q, radius, allowed, count_only):
+        import torch
+        qt = torch.as_tensor(q)
+        if qt.dtype != torch.float32:
+            qt = qt.float()
+        qt = (self._pad_columns(qt) if self.d != self.d_in else qt.to(self.device)).contiguous()
+        assert qt.dim() == 2 and qt.shape[1] == self.d
+        nq = int(qt.shape[0])
+        rad = self._range_radius(radius, nq)
+        f = self._filter(allowed)
+        self.stats = {"range_results": 0, "range_rounds": 0, "range_cap": 0, "range_chunked_queries": 0, "rescaled": 0}
+        counts = np.zeros(nq, np.int64)
+        pieces = []                         # (query numbers, lims, D, I) of every pass that certified a query
+        cap_max = int(self.RANGE_MAX_CAP)
+        groups = [(np.arange(nq), min(int(self.cap), cap_max))] if nq and self.ntotal and (f is None or f.n_allowed) else []
+        chunked = []
+        while groups:
+            idx, cap = groups.pop(0)
+            whole = len(idx) == nq
+            sub = None if whole else torch.as_tensor(idx, device=self.device)
+            cnt, st, lims, D, I, _ = self._range_pass(qt if whole else qt[sub].contiguous(), rad if whole else rad[sub].contiguous(),
+                                                      cap, count_only, allowed=f)
+            self.stats["range_rounds"] += 1
+            self.stats["range_cap"] = max(self.stats["range_cap"], cap)
+            if (st == STATUS_RANGE).any():
+                if self.kind != "f16" or self.stats["rescaled"]:
+                    raise _lib.ConvdrError("convdr_ip_range_search: CONVDR_IP_RANGE %s" % ("after the scan copy was rebuilt"
+                                           if self.stats["rescaled"] else "from a bf16 scan"))
+                self._rebuild_scaled()
+                self.stats["rescaled"] = 1
+                groups.insert(0, (idx, cap))
+                continue
+            ok, over = st == STATUS_OK, st == STATUS_OVERFLOW
+            if not (ok | over).all() or self.stats["range_rounds"] > 64:
+                raise _lib.ConvdrError("convdr_ip_range_search: unexpected status %s" % (st,))
+            counts[idx[ok]] = cnt[ok]
+            if not count_only and ok.any():
+                pieces.append((idx, lims, D, I))
+            # the reported hit count is exact: the list that holds it cannot overflow -- one jump, no doubling
+            need = np.asarray([1 << int(c - 1).bit_length() for c in cnt[over]], dtype=np.int64)
+            chunked += list(idx[over][need > cap_max])
+            for c in sorted(set(need[need <= cap_max].tolist())):
+                groups.append((idx[over][need == c], int(c)))
+        if chunked:
+            idx = np.asarray(sorted(chunked), dtype=np.int64)
+            sub = torch.as_tensor(idx, device=self.device)
+            cnt, lims, D, I = self._range_chunked(qt[sub].contiguous(), rad[sub].contiguous(), f, count_only)
+            counts[idx] = cnt
+            self.stats["range_chunked_queries"] = len(idx)
+            self.stats["range_cap"] = max(self.stats["range_cap"], cap_max)      # (every slice's list)
+            if not count_only:
+                pieces.append((idx, lims, D, I))
+        self.stats["range_results"] = int(counts.sum())
+        if count_only:
+            return counts
+        if len(pieces) == 1 and len(pieces[0][0]) == nq:
+            return pieces[0][1:]
+        lims = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]), device=self.device)
+        total = self.stats["range_results"]
+        Dout = torch.empty(total, dtype=torch.float32, device=self.device)
+        Iout = torch.empty(total, dtype=torch.int64, device=self.device)
+        for idx, lp, D, I in pieces:
+            # result row e of the piece, owned by its query j, goes to lims[idx[j]] + (e - lp[j])
+            shift = lims[torch.as_tensor(idx, device=self.device)] - lp[:-1]
+            dest = torch.repeat_interleave(shift, torch.diff(lp)) + torch.arange(int(D.numel()), device=self.device)
+            Dout[dest], Iout[dest] = D, I
+        return lims, Dout, Iout
+
 
 # Pinned staging buffers and the copy thread pool are process-wide: pinning 64 MB costs ~20 ms (hipHostMalloc), i.e. a
 # fresh set per index would cost as much as loading a 3 GB block through them.

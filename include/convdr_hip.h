@@ -205,6 +205,52 @@ int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, c
                               const uint32_t* row_bits, int64_t row_bits_words, int64_t n_allowed, float* D, int64_t* I,
                               int32_t* status, float* tau_retry, convdr_stream_t stream);
 
+/* Range search: every row of the block whose score EXCEEDS a per-query radius (IndexFlatIP.range_search, with one radius
+ * per query), exact and ragged.
+ *   result       with X the canonical fp64 score of the search entries (same summation order, same corpus per store: the
+ *                fp32 block, or the stored halves widened -- the centre and the scale are the scan's private business and do
+ *                not show), row i belongs to query q iff X[q, i] > (double)radius[q]: STRICT, as FAISS's inner-product
+ *                range search.  Per query the rows are ordered by (X desc, index asc).  D is X rounded to fp32 -- so a
+ *                reported D may EQUAL the radius, for a score above it by less than half an ulp --, I the int64 row number,
+ *                lims int64 [nq + 1] with lims[0] = 0: query q owns D / I [lims[q], lims[q + 1]).  With a bitmap (the
+ *                contract of convdr_ip_search_filtered: 16-byte aligned, whole 256-row tiles, bits past n ignored; NULL, 0:
+ *                no filter) the result is the same set intersected with the allowed rows.
+ *   radius       device fp32 [nq].  -inf: every row; +inf: no row.  NaN is the caller's to refuse (never true: no row).
+ *   threshold    one single-pass scan (the index's kind: store 0 bf16, 1 / 2 fp16; the half store one pass) lists the rows with
+ *                S~ >= tau[q] = round_down(qs[q] * p_scale * (radius[q] - q . centre)) - eps[q], where qs is the query's
+ *                power-of-two scale (1 for bf16), q . centre is summed in fp64 (centre may be NULL; must be for store 2), eps
+ *                is the error band of the top-k certificate, and every rounding -- the fp64 sums' own error bounds, the
+ *                conversion to fp32, the subtraction -- pushes tau DOWN.  Claim: every row with X > radius has S~ >= tau
+ *                (proof beside k_ip_range_tau), so a list that did not overflow holds every result row; all its entries are
+ *                re-scored canonically and the predicate is decided on X.  There is no sample, no k-th score, no TOO_FEW or
+ *                UNCERTAIN.  The split scans would only narrow the band of wasted re-scores and are not used.
+ *   status       CONVDR_IP_OK: the query's run is exact and complete, counts[q] = its length.  CONVDR_IP_OVERFLOW: the scan
+ *                hit more than cap rows; counts[q] = the scan's total hit count (>= the result's length): re-run with
+ *                cap >= counts[q], which cannot overflow again.  CONVDR_IP_RANGE (fp16 kinds): the scale no longer fits the
+ *                block's norms (or the query is astronomically long): rebuild the scan copy.  A query that is not OK has an
+ *                empty run in lims.
+ *   cap          a power of two in [1024, 131072]: entries of a query's list, which lives in global memory at every cap.
+ *   count_only   1: re-score, predicate and count only -- counts and status are written, lims too unless it is NULL (it
+ *                may be), nothing is ordered and convdr_ip_range_pack must not follow.
+ *   workspace    convdr_ip_range_workspace_bytes(nq, n, d, cap) bytes (0 for sizes outside the contract), 256-byte aligned
+ *                regions in this order: query operands [nq_pad, d] x 2 | query norms [nq_pad] | tau [nq_pad] | hit counters
+ *                [nq_pad x 32] | min(hits, cap) [nq_pad] | survivor counts [nq_pad] | list ids [nq, cap] u32 | list scan
+ *                scores [nq, cap] f32 (then: the survivors' ids) | list canonical scores [nq, cap] f64 | survivors' scores
+ *                [nq, cap] f64 -- about 24 bytes per list entry.  Nothing of it is read before this call wrote it.
+ *   two calls    the caller sizes D and I from lims[nq] -- one host read -- and calls convdr_ip_range_pack with the same
+ *                workspace, nq, n, d, cap and lims: it copies every query's ordered run to D + lims[q], I + lims[q] and, when X
+ *                is not NULL, the fp64 scores to X + lims[q] (a host-side merge of row slices orders by them).  Exactly
+ *                lims[nq] entries of each are written.
+ * nq > 0, 0 <= n < 2^31, d % 64 == 0, d <= 4096; store and p_scale as for convdr_ip_search_filtered.  n == 0: counts and lims
+ * are zero, status OK, no scan.  Arguments are validated before anything touches a device; no allocation, no sync. */
+size_t convdr_ip_range_workspace_bytes(int nq, int64_t n, int d, int cap);
+int convdr_ip_range_search(int store, const float* q_f32, int nq, const float* p_f32, const void* p_half, float p_scale,
+                           const float* centre, int64_t n, int d, const float* p_max_norm, const float* radius, int cap,
+                           int count_only, const uint32_t* row_bits, int64_t row_bits_words, void* workspace,
+                           size_t workspace_bytes, int64_t* counts, int64_t* lims, int32_t* status, convdr_stream_t stream);
+int convdr_ip_range_pack(const void* workspace, int nq, int64_t n, int d, int cap, const int64_t* lims, float* D, int64_t* I,
+                         double* X, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);

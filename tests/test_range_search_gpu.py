@@ -1,0 +1,470 @@
+"""Exact range search: FlatIPIndex.range_search / range_count / convdr_ip_range_search + convdr_ip_range_pack.
+
+Expected value everywhere, no tolerances: with S = oracle.search.canonical_scores(Q, P), row i belongs to query j iff
+S[j, i] > float64(radius32[j]) -- the fp32 radius actually passed --, ordered by np.lexsort((index, -S)); D = S rounded to fp32.
+With a mask the oracle runs over P[rows] and is mapped back through rows.  lims, D and I are compared with
+assert_array_equal.  Both stores hold the SAME corpus (rounded to half and widened), so one oracle run per shape serves every
+store and precision.  Radii are the fp32 rounding of the midpoint between ranks m and m + 1 of the oracle's scores; because the
+expected set is recomputed from that fp32 value, no separation is needed, and every test asserts on the ORACLE's counts that it
+lands in the regime it is named for."""
+import numpy as np
+import pytest
+
+from oracle import search as OS
+from tests.golden.make_golden import synth_corpus
+from tests.helpers import fill_bytes
+
+pytestmark = pytest.mark.gpu
+
+CONFIGS = [("fp32", "auto"), ("fp32", "bf16"), ("fp16", "auto")]
+# n, nq, d, clustered
+SHAPES = [
+    (300, 3, 64, False),          # ragged last tile, one K step
+    (257, 1, 100, False),         # padded width (d_in = 100), one query
+    (5000, 37, 768, False),
+    (33000, 130, 128, False),     # two query tiles: Tile256 and the r3 emit path
+    (5000, 37, 768, True),        # a common component of norm ~30 plus unit noise: q . centre matters
+]
+MASKS = ["half", "one", "last_tile", "word_edges", "none"]
+
+_CORPUS, _SCORES, _INDEX = {}, {}, {}
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch
+
+
+def _corpus(shape):
+    """(P = halves widened to fp32, Q); computed once, never written to afterwards"""
+    if shape not in _CORPUS:
+        n, nq, d, clustered = shape
+        P, Q = synth_corpus(100 + n % 97, n, d), synth_corpus(7, nq, d)
+        if clustered:
+            c = synth_corpus(9, 1, d)
+            c *= np.float32(30.0) / np.linalg.norm(c)
+            P, Q = P + c, Q + c
+        P = P.astype(np.float16).astype(np.float32)
+        P.setflags(write=False), Q.setflags(write=False)
+        _CORPUS[shape] = (P, Q)
+    return _CORPUS[shape]
+
+
+def _scores(shape):
+    if shape not in _SCORES:
+        P, Q = _corpus(shape)
+        S = OS.canonical_scores(Q, P)
+        S.setflags(write=False)
+        _SCORES[shape] = S
+    return _SCORES[shape]
+
+
+def _midpoint_radii(S, ms):
+    """fp32 radius per query: the midpoint between ranks m and m + 1 of the query's scores (m = 0: above the best score,
+    m = n: below the worst)"""
+    out = np.empty(S.shape[0], np.float32)
+    for j, m in enumerate(ms):
+        s = np.sort(S[j])[::-1]
+        n = len(s)
+        if n == 0:
+            out[j] = 0.0
+        elif m <= 0:
+            out[j] = np.nextafter(np.float32(s[0]), np.float32(np.inf))
+        elif m >= n:
+            out[j] = np.nextafter(np.float32(s[-1]), np.float32(-np.inf))
+        else:
+            out[j] = np.float32(0.5 * (s[m - 1] + s[m]))
+    return out
+
+
+def _cycle(nq, n, values=None):
+    values = [37, min(n, 900), 0, 1] if values is None else values
+    return [min(n, values[j % len(values)]) for j in range(nq)]
+
+
+def _expected(S, rad32, rows=None):
+    """(lims, D, I) of the definition; S over the allowed rows, `rows` their row numbers (None: all rows)"""
+    nq, n = S.shape
+    idx = np.arange(n)
+    lims, Ds, Is = [0], [], []
+    for j in range(nq):
+        keep = np.flatnonzero(S[j] > np.float64(rad32[j]))
+        order = keep[np.lexsort((idx[keep], -S[j, keep]))]
+        Ds.append(S[j, order].astype(np.float32))
+        Is.append(order if rows is None else rows[order])
+        lims.append(lims[-1] + len(order))
+    return (np.asarray(lims, np.int64), np.concatenate(Ds).astype(np.float32) if Ds else np.zeros(0, np.float32),
+            np.concatenate(Is).astype(np.int64) if Is else np.zeros(0, np.int64))
+
+
+def _index(shape, storage, precision):
+    """one resident index per (shape, store, precision); one at a time"""
+    from convdr_amd.search import FlatIPIndex
+    key = (shape, storage, precision)
+    if key not in _INDEX:
+        _INDEX.clear()
+        P, _ = _corpus(shape)
+        idx = FlatIPIndex(shape[2], storage=storage, precision=precision, prepin=False)
+        idx.add(P.astype(np.float16) if storage == "fp16" else P)
+        _INDEX[key] = idx
+    idx = _INDEX[key]
+    idx.cap, idx.RANGE_MAX_CAP = 4096, 131072
+    return idx
+
+
+def _poison(idx, seed=1):
+    if idx._ws is not None:
+        fill_bytes(idx._ws, "R", seed)
+
+
+def _check(idx, Q, rad, want, allowed=None, what=""):
+    _poison(idx)
+    lims, D, I = idx.range_search(Q, rad, allowed=allowed)
+    assert lims.dtype == np.int64 and D.dtype == np.float32 and I.dtype == np.int64
+    np.testing.assert_array_equal(lims, want[0], err_msg=what)
+    np.testing.assert_array_equal(I, want[2], err_msg=what)
+    np.testing.assert_array_equal(D, want[1], err_msg=what)
+    stats = dict(idx.stats)
+    _poison(idx, 2)
+    cnt = idx.range_count(Q, rad, allowed=allowed)
+    assert cnt.dtype == np.int64
+    np.testing.assert_array_equal(cnt, np.diff(want[0]), err_msg=what)
+    assert stats["range_results"] == int(want[0][-1]) == idx.stats["range_results"]
+    return stats
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+@pytest.mark.parametrize("n,nq,d,clustered", SHAPES)
+def test_range_search_equals_the_oracle(torch_cuda, n, nq, d, clustered, storage, precision):
+    shape = (n, nq, d, clustered)
+    _, Q = _corpus(shape)
+    S = _scores(shape)
+    ms = _cycle(nq, n)
+    rad = _midpoint_radii(S, ms)
+    want = _expected(S, rad)
+    got = np.diff(want[0])
+    assert (np.abs(got - np.asarray(ms)) <= 1).all()
+    if nq >= 4:         # one call mixes empty, tiny and large results
+        assert got.min() == 0 and got.max() >= min(n, 900) - 1
+    if clustered:       # the common component dominates every score: radius - q . centre is a small difference of large numbers
+        assert np.abs(rad).min() > 500 and S.std(axis=1).max() < 60
+    idx = _index(shape, storage, precision)
+    stats = _check(idx, Q, rad, want, what="%s %s" % (storage, precision))
+    assert stats["range_chunked_queries"] == 0 and stats["range_cap"] >= 4096
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_scalar_vector_and_infinite_radius(torch_cuda, storage, precision):
+    torch = torch_cuda
+    shape = (300, 3, 64, False)
+    _, Q = _corpus(shape)
+    S = _scores(shape)
+    idx = _index(shape, storage, precision)
+    r = np.float32(np.median(S))
+    want = _expected(S, np.full(3, r, np.float32))
+    assert 0 < np.diff(want[0]).min() and np.diff(want[0]).max() < 300
+    for radius in (float(r), r, np.full(3, r, np.float32), torch.full((3,), float(r)), torch.full((3,), float(r), device="cuda"),
+                   np.full(3, r, np.float64)):
+        _check(idx, Q, radius, want)
+    everything = _expected(S, np.full(3, -np.inf, np.float32))
+    assert np.diff(everything[0]).tolist() == [300] * 3
+    _check(idx, Q, -np.inf, everything)
+    for j in range(3):          # all n rows, in canonical order
+        np.testing.assert_array_equal(everything[2][300 * j:300 * (j + 1)], np.lexsort((np.arange(300), -S[j])))
+    nothing = _expected(S, np.full(3, np.inf, np.float32))
+    assert nothing[0].tolist() == [0] * 4
+    _check(idx, Q, np.inf, nothing)
+    _check(idx, Q, np.array([-np.inf, r, np.inf], np.float32), _expected(S, np.array([-np.inf, r, np.inf], np.float32)))
+    with pytest.raises(ValueError):
+        idx.range_search(Q, np.zeros(2, np.float32))
+    with pytest.raises(ValueError):
+        idx.range_search(Q, np.array([0.0, np.nan, 0.0], np.float32))
+    with pytest.raises(ValueError):
+        idx.range_count(Q, float("nan"))
+
+
+def _integer_corpus():
+    rs = np.random.RandomState(5)
+    P = rs.randint(-3, 4, size=(600, 64)).astype(np.float32)
+    P[400:440] = P[20:60]                    # duplicate rows far apart: equal scores, index order decides
+    P[500:520] = P[20:40]
+    Q = rs.randint(-3, 4, size=(3, 64)).astype(np.float32)
+    return P, Q
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_strict_inequality_and_ties(torch_cuda, storage, precision):
+    """Small-integer P and Q: every score is an exact integer.  The radius EQUALS a score that occurs: the rows that score
+    exactly the radius are excluded, and equal scores above it come out in index order."""
+    from convdr_amd.search import FlatIPIndex
+    P, Q = _integer_corpus()
+    S = OS.canonical_scores(Q, P)
+    assert (S == np.rint(S)).all()
+    rad = np.empty(3, np.float32)
+    for j in range(3):
+        # the score of a duplicated row that at least 30 rows beat, some of them tied with each other
+        cands = [S[j, r] for r in range(20, 40) if (S[j] > S[j, r]).sum() >= 30]
+        rad[j] = np.float32(max(cands))
+        assert np.float64(rad[j]) == max(cands) and (S[j] == rad[j]).sum() >= 3
+        above = S[j][S[j] > rad[j]]
+        assert len(above) > len(np.unique(above))                              # ties among the results
+    want = _expected(S, rad)
+    for j in range(3):
+        assert not np.isin(np.flatnonzero(S[j] == rad[j]), want[2][want[0][j]:want[0][j + 1]]).any()
+    idx = FlatIPIndex(64, storage=storage, precision=precision, prepin=False)
+    idx.add(P.astype(np.float16) if storage == "fp16" else P)
+    _check(idx, Q, rad, want)
+    # a planted positive with an exactly representable, unique score: range_count at its score is its rank minus one
+    for j in range(3):
+        uniq = [r for r in range(600) if (S[j] == S[j, r]).sum() == 1 and 5 <= (S[j] > S[j, r]).sum() <= 200]
+        assert uniq
+        pos = uniq[0]
+        rank = int(np.flatnonzero(np.lexsort((np.arange(600), -S[j])) == pos)[0]) + 1
+        d_pos = np.float32(S[j, pos])
+        assert np.float64(d_pos) == S[j, pos]
+        assert int(idx.range_count(Q[j:j + 1], d_pos)[0]) == rank - 1
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_overflow_ladder_jumps_to_the_reported_count(torch_cuda, storage, precision):
+    shape = (20000, 4, 64, False)
+    _, Q = _corpus(shape)
+    S = _scores(shape)
+    rad = _midpoint_radii(S, [3000, 6000, 12000, 20000])
+    want = _expected(S, rad)
+    got = np.diff(want[0])
+    assert 2900 <= got[0] <= 3100 and 5900 <= got[1] <= 6100 and 11900 <= got[2] <= 12100 and got[3] == 20000
+    idx = _index(shape, storage, precision)
+    stats = _check(idx, Q, rad, want)
+    assert stats["range_cap"] == 32768 and stats["range_rounds"] == 4 and stats["range_chunked_queries"] == 0, stats
+    # the query with every row alone: ONE jump from 4,096 to 32,768, where doubling would take three passes
+    one = _expected(S[3:4], rad[3:4])
+    stats = _check(idx, Q[3:4], rad[3:4], one)
+    assert stats["range_rounds"] == 2 and stats["range_cap"] == 32768, stats
+    # ~3,000 results fit the first list
+    stats = _check(idx, Q[0:1], rad[0:1], _expected(S[0:1], rad[0:1]))
+    assert stats["range_rounds"] == 1 and stats["range_cap"] == 4096, stats
+
+
+@pytest.mark.parametrize("filtered", [False, True])
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_last_rung_searches_row_slices(torch_cuda, storage, precision, filtered):
+    shape = (5000, 3, 64, False)
+    P, Q = _corpus(shape)
+    S = _scores(shape)
+    if filtered:
+        mask = np.random.RandomState(11 + 5000).rand(5000) < 0.7
+        rows = np.flatnonzero(mask)
+        Sr = OS.canonical_scores(Q, np.ascontiguousarray(P[rows]))
+        ms = [3000, 10, 500]
+    else:
+        mask, rows, Sr, ms = None, None, S, [4000, 10, 500]
+    rad = _midpoint_radii(Sr, ms)
+    want = _expected(Sr, rad, rows)
+    assert np.abs(np.diff(want[0]) - ms).max() <= 1
+    idx = _index(shape, storage, precision)
+    try:
+        idx.RANGE_MAX_CAP, idx.cap = 2048, 1024
+        _poison(idx)
+        lims, D, I = idx.range_search(Q, rad, allowed=mask)
+        stats = dict(idx.stats)
+        cnt = idx.range_count(Q, rad, allowed=mask)
+        assert idx.stats["range_chunked_queries"] == 1
+    finally:
+        idx.RANGE_MAX_CAP, idx.cap = 131072, 4096
+    np.testing.assert_array_equal(lims, want[0])
+    np.testing.assert_array_equal(I, want[2])
+    np.testing.assert_array_equal(D, want[1])
+    np.testing.assert_array_equal(cnt, np.diff(want[0]))
+    assert stats["range_chunked_queries"] == 1 and stats["range_cap"] == 2048 and stats["range_rounds"] == 1, stats
+    # the other queries alone: the same runs, no last rung
+    l2, D2, I2 = idx.range_search(Q[1:], rad[1:], allowed=mask)
+    assert idx.stats["range_chunked_queries"] == 0
+    np.testing.assert_array_equal(I2, want[2][want[0][1]:])
+    np.testing.assert_array_equal(D2, want[1][want[0][1]:])
+
+
+def _mask(n, name):
+    m = np.zeros(n, bool)
+    if name == "half":
+        m = np.random.RandomState(11 + n).rand(n) < 0.5
+    elif name == "one":
+        m[n // 3] = True
+    elif name == "last_tile":
+        assert n % 256
+        m[n // 256 * 256:] = True
+    elif name == "word_edges":
+        m[[31, 32, 63, 64, 255, 256]] = True
+    else:
+        assert name == "none"
+    return m
+
+
+@pytest.mark.parametrize("name", MASKS)
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+@pytest.mark.parametrize("n,nq,d", [(5000, 37, 768), (300, 3, 64)])
+def test_row_filter(torch_cuda, n, nq, d, storage, precision, name):
+    shape = (n, nq, d, False)
+    P, Q = _corpus(shape)
+    mask = _mask(n, name)
+    rows = np.flatnonzero(mask)
+    key = (shape, name)
+    if key not in _SCORES:
+        _SCORES[key] = OS.canonical_scores(Q, np.ascontiguousarray(P[rows])) if len(rows) else np.zeros((nq, 0))
+    Sr = _SCORES[key]
+    rad = _midpoint_radii(Sr, _cycle(nq, len(rows)))
+    want = _expected(Sr, rad, rows)
+    if name == "none":
+        assert want[0].tolist() == [0] * (nq + 1)
+    else:
+        assert np.diff(want[0]).max() >= min(len(rows), 900) - 1 and np.isin(want[2], rows).all()
+    idx = _index(shape, storage, precision)
+    _check(idx, Q, rad, want, allowed=mask, what=name)
+    f = idx.row_filter(mask)
+    lims, D, I = idx.range_search(Q, rad, allowed=f)
+    np.testing.assert_array_equal(I, want[2])
+    np.testing.assert_array_equal(lims, want[0])
+
+
+def test_stale_filter_raises(torch_cuda):
+    from convdr_amd.search import FlatIPIndex
+    P, Q = synth_corpus(3, 600, 64), synth_corpus(4, 2, 64)
+    idx = FlatIPIndex(64, prepin=False)
+    idx.add(P[:500])
+    f = idx.row_filter(np.ones(500, bool))
+    idx.range_search(Q, 0.0, allowed=f)
+    idx.add(P[500:])
+    for call in (lambda: idx.range_search(Q, 0.0, allowed=f), lambda: idx.range_count(Q, 0.0, allowed=f),
+                 lambda: idx.range_search_tensors(Q, 0.0, allowed=f), lambda: idx.range_search(Q, 0.0, allowed=np.ones(500, bool))):
+        with pytest.raises(ValueError):
+            call()
+
+
+def test_scan_copy_is_rebuilt_when_later_rows_outgrow_its_scale(torch_cuda):
+    """fp32 store, fp16 kind: rows added later that are ~100x longer than the first block's: CONVDR_IP_RANGE, the scale is
+    re-derived, the copy rebuilt and the range search run again (the recipe of the top-k test of that case)."""
+    from convdr_amd.search import FlatIPIndex
+    P0 = synth_corpus(81, 600, 64).astype(np.float16).astype(np.float32)
+    P1 = (synth_corpus(82, 500, 64) * np.float32(100.0)).astype(np.float16).astype(np.float32)
+    Q = synth_corpus(83, 5, 64)
+    P = np.concatenate([P0, P1])
+    S = OS.canonical_scores(Q, P)
+    rad = _midpoint_radii(S, [0, 1, 37, 400, 1100])
+    want = _expected(S, rad)
+    idx = FlatIPIndex(64, prepin=False)
+    idx.add(P0)
+    s0 = idx._scale
+    idx.add(P1)
+    stats = _check_first(idx, Q, rad, want)
+    assert stats["rescaled"] == 1 and idx._scale < s0
+    assert _check_first(idx, Q, rad, want)["rescaled"] == 0
+
+
+def _check_first(idx, Q, rad, want):
+    lims, D, I = idx.range_search(Q, rad)
+    stats = dict(idx.stats)
+    np.testing.assert_array_equal(lims, want[0])
+    np.testing.assert_array_equal(I, want[2])
+    np.testing.assert_array_equal(D, want[1])
+    np.testing.assert_array_equal(idx.range_count(Q, rad), np.diff(want[0]))
+    return stats
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_empty_index_and_update_rows(torch_cuda, storage, precision):
+    torch = torch_cuda
+    from convdr_amd.search import FlatIPIndex
+    Q = synth_corpus(4, 2, 64)
+    idx = FlatIPIndex(64, storage=storage, precision=precision, prepin=False)
+    lims, D, I = idx.range_search(Q, 0.0)
+    assert lims.tolist() == [0, 0, 0] and D.shape == (0,) and I.shape == (0,) and D.dtype == np.float32 and I.dtype == np.int64
+    assert idx.range_count(Q, -np.inf).tolist() == [0, 0]
+    P = synth_corpus(3, 600, 64).astype(np.float16).astype(np.float32)
+    idx.add(P.astype(np.float16) if storage == "fp16" else P)
+    new = (synth_corpus(5, 3, 64) * np.float32(1.5)).astype(np.float16).astype(np.float32)
+    P2 = P.copy()
+    P2[100:103] = new
+    idx.update_rows(100, torch.from_numpy(new).cuda())
+    S = OS.canonical_scores(Q, P2)
+    rad = _midpoint_radii(S, [37, 600])
+    want = _expected(S, rad)
+    assert np.isin([100, 101, 102], want[2]).all()          # the new rows are in the result: they are honoured
+    assert not np.array_equal(OS.canonical_scores(Q, P)[:, 100:103], S[:, 100:103])
+    _check(idx, Q, rad, want)
+    one = _expected(S[:1], rad[:1])                          # nq = 1
+    _check(idx, Q[:1], rad[:1], one)
+
+
+@pytest.mark.parametrize("storage,precision", CONFIGS)
+def test_c_abi_overflow_counts_and_untouched_tails(torch_cuda, storage, precision):
+    """convdr_ip_range_search + convdr_ip_range_pack called directly at cap = 1,024 with the workspace and every output
+    pre-filled with zeros, 0xFF bytes and random bytes: the three runs agree bit for bit; OK queries equal the oracle; an
+    OVERFLOW query reports the scan's hit count (>= its survivors, > cap) and owns an empty run; nothing past lims[nq] entries
+    of the oversized D / I / X is written."""
+    torch = torch_cuda
+    from convdr_amd import _lib
+    shape = (5000, 37, 768, False)
+    n, nq, d, _ = shape
+    _, Q = _corpus(shape)
+    S = _scores(shape)
+    ms = _cycle(nq, n, [0, 1, 37, 900, 2000])
+    rad = _midpoint_radii(S, ms)
+    want = _expected(S, rad)
+    surv = np.diff(want[0])
+    assert (surv > 1024).sum() >= 5 and (surv < 1000).sum() >= 20
+    idx = _index(shape, storage, precision)
+    cap, pad = 1024, 777
+    L, ptr = _lib.lib(), _lib.ptr
+    store = 2 if idx._half else (1 if idx.kind == "f16" else 0)
+    need = L.convdr_ip_range_workspace_bytes(nq, n, d, cap)
+    q, r = torch.from_numpy(Q).cuda(), torch.from_numpy(rad).cuda()
+    runs = {}
+    for fill in ("Z", "N", "R"):
+        ws = fill_bytes(torch.empty(need, dtype=torch.uint8, device="cuda"), fill, 9)
+        cnt = fill_bytes(torch.empty(nq, dtype=torch.int64, device="cuda"), fill, 10)
+        lims = fill_bytes(torch.empty(nq + 1, dtype=torch.int64, device="cuda"), fill, 11)
+        st = fill_bytes(torch.empty(nq, dtype=torch.int32, device="cuda"), fill, 12)
+        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx._half else ptr(idx._rows), ptr(idx._pbf),
+                                            float(idx._scale) if store else 1.0, None if idx._half else ptr(idx._centre), n, d,
+                                            ptr(idx._max_norm), ptr(r), cap, 0, None, 0, ptr(ws), need, ptr(cnt), ptr(lims), ptr(st),
+                                            _lib.stream_ptr()), "convdr_ip_range_search")
+        total = int(lims[-1].item())
+        D = fill_bytes(torch.empty(total + pad, dtype=torch.float32, device="cuda"), fill, 13)
+        I = fill_bytes(torch.empty(total + pad, dtype=torch.int64, device="cuda"), fill, 14)
+        X = fill_bytes(torch.empty(total + pad, dtype=torch.float64, device="cuda"), fill, 15)
+        tails = [t[total:].clone() for t in (D, I, X)]
+        _lib.check(L.convdr_ip_range_pack(ptr(ws), nq, n, d, cap, ptr(lims), ptr(D), ptr(I), ptr(X), _lib.stream_ptr()),
+                   "convdr_ip_range_pack")
+        torch.cuda.synchronize()
+        for t, tail in zip((D, I, X), tails):
+            assert torch.equal(t[total:].view(torch.uint8), tail.view(torch.uint8)), "written past lims[nq] (fill %s)" % fill
+        runs[fill] = (cnt.cpu().numpy(), lims.cpu().numpy(), st.cpu().numpy(), D[:total].cpu().numpy().view(np.uint32),
+                      I[:total].cpu().numpy(), X[:total].cpu().numpy().view(np.uint64))
+        # count-only mode: the same counts and status, lims may be NULL
+        cnt2 = fill_bytes(torch.empty(nq, dtype=torch.int64, device="cuda"), fill, 16)
+        st2 = fill_bytes(torch.empty(nq, dtype=torch.int32, device="cuda"), fill, 17)
+        fill_bytes(ws, fill, 18)
+        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx._half else ptr(idx._rows), ptr(idx._pbf),
+                                            float(idx._scale) if store else 1.0, None if idx._half else ptr(idx._centre), n, d,
+                                            ptr(idx._max_norm), ptr(r), cap, 1, None, 0, ptr(ws), need, ptr(cnt2), None, ptr(st2),
+                                            _lib.stream_ptr()), "convdr_ip_range_search")
+        np.testing.assert_array_equal(cnt2.cpu().numpy(), runs[fill][0])
+        np.testing.assert_array_equal(st2.cpu().numpy(), runs[fill][2])
+    for fill in ("N", "R"):
+        for a, b in zip(runs["Z"], runs[fill]):
+            np.testing.assert_array_equal(a, b, err_msg="fill %s" % fill)
+    cnt, lims, st, D, I, X = runs["Z"]
+    assert set(st.tolist()) == {0, 1}
+    ok = st == 0
+    assert (surv[ok] <= cap).all() and (st[surv > cap] == 1).all()
+    np.testing.assert_array_equal(cnt[ok], surv[ok])
+    assert (cnt[~ok] >= surv[~ok]).all() and (cnt[~ok] > cap).all()
+    np.testing.assert_array_equal(np.diff(lims), np.where(ok, surv, 0))
+    assert lims[0] == 0
+    for j in np.flatnonzero(ok):
+        a, b = want[0][j], want[0][j + 1]
+        np.testing.assert_array_equal(I[lims[j]:lims[j + 1]], want[2][a:b])
+        np.testing.assert_array_equal(D[lims[j]:lims[j + 1]], want[1][a:b].view(np.uint32))
+        np.testing.assert_array_equal(X[lims[j]:lims[j + 1]].view(np.float64), S[j, want[2][a:b]])
