@@ -14,7 +14,6 @@
 
 namespace convdr {
 
-constexpr int IP_DEEP_MIN_CAP = 16384, IP_DEEP_MAX_CAP = 131072;
 constexpr int IP_DEEP_THREADS = 1024;
 constexpr int IP_DEEP_TILE = 4096;             // pairs ordered in LDS at a time: 4096 x (8 + 4) bytes = 48 KB
 constexpr int IP_DEEP_SAMPLE_RANK = 512;       // expected rank of the threshold inside the row sample (see ip_deep_plan)
@@ -213,14 +212,13 @@ __global__ void __launch_bounds__(IP_DEEP_THREADS) k_ip_select_deep(int k, int c
 // ------------------------------------------------------------------------------------------
 // host-side plan of the deep search
 // ------------------------------------------------------------------------------------------
-struct IpDeepPlan {
-  int big, tr, tl, nq_pad, nQt, nPt;
+struct IpDeepPlan : IpPlanHead {
   int mode;            // -1: n <= cap, every row is a candidate; IP_MODE_FULL: threshold from a row sample
   int R;               // rank the threshold aims at in the whole block
   int nSeg, segTiles;  // the sample: nSeg runs of segTiles passage tiles, run g starting at tile g * nPt / nSeg
   int64_t sampled_rows, t_rows;   // rows of the block in the sample / rows of T the sample fills
   int r;               // rank selected inside the sample
-  size_t o_qb, o_qlo, o_qnorm, o_tau, o_counts, o_counts_packed, o_m, o_T, o_id, o_s, o_bid, o_bx, o_sx, total;
+  size_t o_qlo, o_counts_packed, o_T, o_bid, o_bx, o_sx;
 };
 
 // Threshold rule.  The list has `cap` slots, the cut needs the k best scan scores in it and the band below them.  The
@@ -238,13 +236,7 @@ struct IpDeepPlan {
 // as the block; the sample is therefore IP_DEEP_SAMPLE_SEGMENTS evenly spaced runs of whole tiles, each scanned by one
 // launch over a sub-block (its own P pointer and row count), writing its rows of T contiguously.
 static IpDeepPlan ip_deep_plan(int nq, int64_t n, int d, int k, int cap, int rank_target) {
-  IpDeepPlan p;
-  p.big = nq > 128 ? IP_TILE_256 : IP_TILE_TALL;
-  p.tr = Tile256::TR;
-  p.tl = p.big == IP_TILE_256 ? Tile256::TL : TileTall::TL;
-  p.nq_pad = (nq + p.tl - 1) / p.tl * p.tl;
-  p.nQt = p.nq_pad / p.tl;
-  p.nPt = (int)ceil_div64(n, p.tr);
+  IpDeepPlan p{ip_plan_head(nq, n)};
   int R = rank_target > 0 ? rank_target : cap / 2;
   if (2 * (int64_t)R < 3 * (int64_t)k) R = k + (cap - k) / 2;
   if (R > cap) R = cap;
@@ -269,15 +261,15 @@ static IpDeepPlan ip_deep_plan(int nq, int64_t n, int d, int k, int cap, int ran
     if (r > p.sampled_rows) r = p.sampled_rows;
     p.r = (int)r;
   }
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  p.o_qb = take((size_t)p.nq_pad * d * 2);
-  p.o_qlo = take((size_t)p.nq_pad * d * 2);
-  p.o_qnorm = take((size_t)p.nq_pad * 4);
-  p.o_tau = take((size_t)p.nq_pad * 4);
-  p.o_counts = take((size_t)p.nq_pad * IP_COUNT_STRIDE * 4);
-  p.o_counts_packed = take((size_t)p.nq_pad * 4);
-  p.o_m = take((size_t)p.nq_pad * 4);
+  // Layout as before the shared head: qb|qlo|qnorm|tau|counts|counts_packed|m|T|id|s|bid|bx|sx, same sizes (no accessors).
+  WsCursor ws;
+  p.o_qb = ws.take((size_t)p.nq_pad * d * 2);
+  p.o_qlo = ws.take((size_t)p.nq_pad * d * 2);
+  p.o_qnorm = ws.take((size_t)p.nq_pad * 4);
+  p.o_tau = ws.take((size_t)p.nq_pad * 4);
+  p.o_counts = ws.take((size_t)p.nq_pad * IP_COUNT_STRIDE * 4);
+  p.o_counts_packed = ws.take((size_t)p.nq_pad * 4);
+  p.o_m = ws.take((size_t)p.nq_pad * 4);
   // T is sized for the tallest sample any threshold rank allows (R >= 1.5 k), whether or not this call samples: the size
   // then depends on neither rank_target nor the plan's branch, and never shrinks when cap grows
   int64_t s_max = ceil_div64((int64_t)2 * IP_DEEP_SAMPLE_RANK * n, (int64_t)3 * k);
@@ -286,40 +278,27 @@ static IpDeepPlan ip_deep_plan(int nq, int64_t n, int d, int k, int cap, int ran
   int64_t t_tiles = ceil_div64(s_max, p.tr) + IP_DEEP_SAMPLE_SEGMENTS;
   if (t_tiles > p.nPt) t_tiles = p.nPt;
   if (t_tiles * p.tr < p.t_rows) t_tiles = p.t_rows / p.tr;
-  p.o_T = take((size_t)t_tiles * p.tr * p.nq_pad * 4);
-  p.o_id = take((size_t)nq * cap * 4);     // the scan's list: ids; after the cut: the survivors' ids (k_ip_select_deep)
-  p.o_s = take((size_t)nq * cap * 4);      // the scan's list: scan scores
-  p.o_bid = take((size_t)nq * cap * 4);    // the band: ids
-  p.o_bx = take((size_t)nq * cap * 8);     // the band: canonical fp64 scores
-  p.o_sx = take((size_t)nq * cap * 8);     // the survivors' scores, ordered in place
-  p.total = o;
+  p.o_T = ws.take((size_t)t_tiles * p.tr * p.nq_pad * 4);
+  p.o_id = ws.take((size_t)nq * cap * 4);     // the scan's list: ids; after the cut: the survivors' ids (k_ip_select_deep)
+  p.o_s = ws.take((size_t)nq * cap * 4);      // the scan's list: scan scores
+  p.o_bid = ws.take((size_t)nq * cap * 4);    // the band: ids
+  p.o_bx = ws.take((size_t)nq * cap * 8);     // the band: canonical fp64 scores
+  p.o_sx = ws.take((size_t)nq * cap * 8);     // the survivors' scores, ordered in place
+  p.total = ws.at;
   return p;
 }
 
-static bool ip_deep_sizes_ok(int nq, int64_t n, int d, int k, int cap) {
-  return nq > 0 && k > 0 && n >= 0 && n < ((int64_t)1 << 31) && d > 0 && d % 64 == 0 && d <= 4096 && cap >= IP_DEEP_MIN_CAP &&
-         cap <= IP_DEEP_MAX_CAP && (cap & (cap - 1)) == 0 && k <= cap / 2;
-}
-
-static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_half,
-                          const void* p_half_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
-                          int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                          float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false,
-                          const uint32_t* row_bits = nullptr, int64_t n_allowed = -1) {
-  CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search_deep: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
-  CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search_deep: need d %% 64 == 0 and d <= 4096 (got %d)", d);
-  CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search_deep: block too large (n=%lld >= 2^31)", (long long)n);
-  CONVDR_REQUIRE(cap >= IP_DEEP_MIN_CAP && cap <= IP_DEEP_MAX_CAP && (cap & (cap - 1)) == 0,
-                 "convdr_ip_search_deep: cap must be a power of two in [16384, 131072] (got %d)", cap);
-  CONVDR_REQUIRE(k <= cap / 2, "convdr_ip_search_deep: k=%d too large for cap=%d", k, cap);
-  CONVDR_REQUIRE(rank_target >= 0, "convdr_ip_search_deep: rank_target=%d", rank_target);
-  const IpDeepPlan p = ip_deep_plan(nq, n, d, k, cap, rank_target);
-  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_ip_search_deep: workspace too small (%zu < %zu)", workspace_bytes, p.total);
-  char* ws = (char*)workspace;
-  bf16_t* qb = (bf16_t*)(ws + p.o_qb);
+// The deep pipeline.  p plans the arguments ip_topk validated; the row filter as in ip_search (ip_host.hpp).
+static int ip_search_deep(const char* name, const IpBlock& b, const IpTopkArgs& c, const IpDeepPlan& p) {
+  if (int e = ip_check_workspace(name, c.workspace_bytes, p.total)) return e;
+  const int nq = c.nq, k = c.k, cap = c.cap;
+  const int64_t n = b.n;
+  hipStream_t st = c.st;
+  char* ws = (char*)c.workspace;
   float* qnorm = (float*)(ws + p.o_qnorm);
   float* tau = (float*)(ws + p.o_tau);
   uint32_t* counts = (uint32_t*)(ws + p.o_counts);
+  uint32_t* counts_packed = (uint32_t*)(ws + p.o_counts_packed);
   float* T = (float*)(ws + p.o_T);
   uint32_t* list_id = (uint32_t*)(ws + p.o_id);
   float* list_s = (float*)(ws + p.o_s);
@@ -327,73 +306,43 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
   double* band_x = (double*)(ws + p.o_bx);
   double* sort_x = (double*)(ws + p.o_sx);
   uint32_t* band = (uint32_t*)(ws + p.o_m);
-  const bool x3 = p_half_lo != nullptr || two_pass;   // the query's remainder is an operand (ip_search: `split`)
-  const int64_t n_need = row_bits ? n_allowed : n;    // the row filter, as in ip_search
-  const bool all_candidates = p.mode < 0 || (row_bits && n_allowed <= cap);
+  bf16_t* qlo = b.split() ? (bf16_t*)(ws + p.o_qlo) : nullptr;
+  const bool all_candidates = p.mode < 0 || (b.row_bits && b.n_allowed <= cap);
 
-  bf16_t* qlo = x3 ? (bf16_t*)(ws + p.o_qlo) : nullptr;
-  const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
-  if (kind == IP_KIND_F16)
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);
-  else
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_BF16, false>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);
-  CONVDR_CHECK_LAUNCH("k_rows_to_half(Q)");
-
-  if (n == 0) {
-    hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
-    CONVDR_CHECK_LAUNCH("k_fill_f32");
+  if (int e = ip_prepare_queries(b, p, ws, c.q_f32, nq, qlo, st)) return e;
+  const ScanArgs emit = ip_scan_args(b, p, ws, nq, cap, qlo, T);
+  if (n == 0 || c.tau_in || all_candidates) {   // (an empty block is not scanned: -inf, whatever tau_in is)
+    if (int e = ip_given_tau(p, ws, n > 0 ? c.tau_in : nullptr, nq, st)) return e;
   } else {
-    ScanArgs a{};
-    a.P = (const bf16_t*)p_half; a.Qb = qb; a.Plo = (const bf16_t*)p_half_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad;
-    a.d = d; a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = list_id; a.cand_s = list_s; a.cap = cap; a.T = T;
-    a.two_pass = two_pass ? 1 : 0;
-    a.bits = row_bits;
-    if (tau_in) {
-      CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
-    } else if (all_candidates) {
-      hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
-      CONVDR_CHECK_LAUNCH("k_fill_f32");
-    } else {
-      for (int g = 0; g < p.nSeg; ++g) {
-        const int64_t row0 = (int64_t)g * p.nPt / p.nSeg * p.tr;
-        const int64_t rows = std::min<int64_t>((int64_t)p.segTiles * p.tr, n - row0);
-        ScanArgs b = a;
-        b.P = a.P + row0 * d;
-        if (a.Plo) b.Plo = a.Plo + row0 * d;
-        if (a.bits) b.bits = a.bits + row0 / 32;   // (row0 is a multiple of the tile height: whole words)
-        b.n = rows;
-        b.nPt = (int)ceil_div64(rows, p.tr);   // = segTiles: only the block's last tile is ragged
-        b.pt_stride = 1;
-        b.T = T + (int64_t)g * p.segTiles * p.tr * p.nq_pad;
-        if (int e = launch_scan<IP_MODE_FULL>(b, p.big, kind, st)) return e;
-      }
-      ProfScope prof("ip_tau_deep", st);
-      hipLaunchKernelGGL(k_tau_select_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, T, (int)p.t_rows, p.nq_pad, p.r, tau);
-      CONVDR_CHECK_LAUNCH("k_tau_select_deep");
+    for (int g = 0; g < p.nSeg; ++g) {
+      const int64_t row0 = (int64_t)g * p.nPt / p.nSeg * p.tr;
+      const int64_t rows = std::min<int64_t>((int64_t)p.segTiles * p.tr, n - row0);
+      ScanArgs a = emit;
+      a.P = emit.P + row0 * b.d;
+      if (emit.Plo) a.Plo = emit.Plo + row0 * b.d;
+      if (emit.bits) a.bits = emit.bits + row0 / 32;   // (row0 is a multiple of the tile height: whole words)
+      a.n = rows;
+      a.nPt = (int)ceil_div64(rows, p.tr);   // = segTiles: only the block's last tile is ragged
+      a.T = T + (int64_t)g * p.segTiles * p.tr * p.nq_pad;
+      if (int e = launch_scan<IP_MODE_FULL>(a, p.big, b.kind(), st)) return e;
     }
-    a.nPt = p.nPt; a.pt_stride = 1;
-    if (int e = launch_scan<IP_MODE_EMIT>(a, p.big, kind, st)) return e;
+    ProfScope prof("ip_tau_deep", st);
+    hipLaunchKernelGGL(k_tau_select_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, T, (int)p.t_rows, p.nq_pad, p.r, tau);
+    CONVDR_CHECK_LAUNCH("k_tau_select_deep");
   }
+  if (n > 0)
+    if (int e = launch_scan<IP_MODE_EMIT>(emit, p.big, b.kind(), st)) return e;
   {
     ProfScope prof("ip_cut_deep", st);
-    hipLaunchKernelGGL(k_ip_cut_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, n_need, k, cap, counts, (uint32_t*)(ws + p.o_counts_packed),
-                       list_id, list_s, band_id, tau, qnorm, p_max_norm, ip_eps_coef(d, x3, kind), ip_eps_abs(d, x3, kind),
-                       kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, band, status,
-                       tau_retry);
+    hipLaunchKernelGGL(k_ip_cut_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, b.n_need(), k, cap, counts, counts_packed, list_id, list_s,
+                       band_id, tau, qnorm, b.p_max_norm, b.eps_coef(), b.eps_abs(), b.scan_scale(), b.norm_limit(), band, c.status,
+                       c.tau_retry);
     CONVDR_CHECK_LAUNCH("k_ip_cut_deep");
   }
   if (n > 0) {
     // (bands are thousands of rows per query here: more waves per query than the shallow call's 64 when queries are few)
     ProfScope prof("ip_rescore_deep", st);
-    if (rows_f16)   // the half store: its halves are the rows, the fp64 sum is multiplied by 1 / p_scale once (k_ip_rescore)
-      hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, nq < 64 ? 128 : 16), dim3(256), 0, st, q_f32, (const _Float16*)p_half, d,
-                         cap, band, band_id, band_x, 1.0 / (double)p_scale);
-    else
-      hipLaunchKernelGGL(k_ip_rescore<float>, dim3(nq, nq < 64 ? 128 : 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, band_id,
-                         band_x, 1.0);
-    CONVDR_CHECK_LAUNCH("k_ip_rescore");
+    if (int e = ip_rescore(b, c.q_f32, nq, nq < 64 ? 128 : 16, cap, band, band_id, band_x, st)) return e;
   }
   static DeviceOnce attr_done;
   if (attr_done.first())
@@ -401,7 +350,7 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
                                          IP_DEEP_TILE * 12));
   ProfScope prof("ip_select_deep", st);
   hipLaunchKernelGGL(k_ip_select_deep, dim3(nq), dim3(IP_DEEP_THREADS), (size_t)IP_DEEP_TILE * 12, st, k, cap, band, band_id, band_x,
-                     list_id, sort_x, D, I);
+                     list_id, sort_x, c.D, c.I);
   CONVDR_CHECK_LAUNCH("k_ip_select_deep");
   return 0;
 }
@@ -410,27 +359,6 @@ static int ip_search_deep(int kind, float p_scale, const float* q_f32, int nq, c
 
 extern "C" size_t convdr_ip_deep_workspace_bytes(int nq, int64_t n, int d, int k, int cap) {
   using namespace convdr;
-  if (!ip_deep_sizes_ok(nq, n, d, k, cap)) return 0;
+  if (ip_check_sizes(IP_DEEP, nq, n, d, k, cap)) return 0;
   return ip_deep_plan(nq, n, d, k, cap, 0).total;
-}
-
-extern "C" int convdr_ip_search_deep(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo,
-                                     int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
-                                     int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
-                                     int32_t* status, float* tau_retry, convdr_stream_t stream) {
-  using namespace convdr;
-  return ip_search_deep(IP_KIND_BF16, 1.f, q_f32, nq, p_f32, p_bf16, p_bf16_lo, n, d, k, p_max_norm, tau_in, cap, rank_target,
-                        workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream);
-}
-
-extern "C" int convdr_ip_search_deep_f16(const float* q_f32, int nq, const float* p_f32, const void* p_f16, const void* p_f16_lo,
-                                         float p_scale, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in,
-                                         int cap, int rank_target, void* workspace, size_t workspace_bytes, float* D,
-                                         int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream) {
-  using namespace convdr;
-  int ex = 0;
-  CONVDR_REQUIRE(p_scale > 0.f && frexpf(p_scale, &ex) == 0.5f, "convdr_ip_search_deep_f16: p_scale must be a power of two (got %g)",
-                 (double)p_scale);
-  return ip_search_deep(IP_KIND_F16, p_scale, q_f32, nq, p_f32, p_f16, p_f16_lo, n, d, k, p_max_norm, tau_in, cap, rank_target,
-                        workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream);
 }

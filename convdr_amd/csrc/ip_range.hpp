@@ -20,7 +20,6 @@
 
 namespace convdr {
 
-constexpr int IP_RANGE_MIN_CAP = 1024, IP_RANGE_MAX_CAP = 131072;
 constexpr int IP_RANGE_THREADS = 1024;
 constexpr int IP_RANGE_LDS_SORT = 8192;        // survivors ordered by the LDS network; more take deep_bitonic
 
@@ -229,49 +228,101 @@ __global__ void __launch_bounds__(256) k_ip_range_pack(int cap, const uint32_t* 
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-struct IpRangePlan {
-  int big, tr, tl, nq_pad, nQt, nPt;
-  size_t o_qb, o_qnorm, o_tau, o_counts, o_m, o_nsurv, o_id, o_s, o_x, o_sx, total;
+struct IpRangePlan : IpPlanHead {
+  size_t o_nsurv, o_x, o_sx;
 };
 
-static bool ip_range_sizes_ok(int nq, int64_t n, int d, int cap) {
-  return nq > 0 && n >= 0 && n < ((int64_t)1 << 31) && d > 0 && d % 64 == 0 && d <= 4096 && cap >= IP_RANGE_MIN_CAP &&
-         cap <= IP_RANGE_MAX_CAP && (cap & (cap - 1)) == 0;
+// Workspace layout: the regions of the contract (include/convdr_hip.h, "Range search": workspace), order and sizes as before
+// the shared head.  Only the total has an accessor; convdr_ip_range_pack finds o_s (after the scan: the survivors' ids) and o_sx.
+static IpRangePlan ip_range_plan(int nq, int64_t n, int d, int cap) {
+  IpRangePlan p{ip_plan_head(nq, n)};
+  WsCursor ws;
+  p.o_qb = ws.take((size_t)p.nq_pad * d * 2);
+  p.o_qnorm = ws.take((size_t)p.nq_pad * 4);
+  p.o_tau = ws.take((size_t)p.nq_pad * 4);
+  p.o_counts = ws.take((size_t)p.nq_pad * IP_COUNT_STRIDE * 4);
+  p.o_m = ws.take((size_t)p.nq_pad * 4);
+  p.o_nsurv = ws.take((size_t)p.nq_pad * 4);
+  p.o_id = ws.take((size_t)nq * cap * 4);
+  p.o_s = ws.take((size_t)nq * cap * 4);
+  p.o_x = ws.take((size_t)nq * cap * 8);
+  p.o_sx = ws.take((size_t)nq * cap * 8);
+  p.total = ws.at;
+  return p;
 }
 
-// Workspace layout (every region 256-byte aligned), in this order:
-//   qb [nq_pad, d] 16-bit query operands | qnorm [nq_pad] | tau [nq_pad] | counts [nq_pad * 32] (one counter per 128-byte
-//   line) | m [nq_pad] = min(hits, cap) | nsurv [nq_pad] | list ids [nq, cap] u32 | list scan scores [nq, cap] f32, after the
-//   scan the survivors' ids | list canonical scores [nq, cap] f64 | survivors' scores [nq, cap] f64
-static IpRangePlan ip_range_plan(int nq, int64_t n, int d, int cap) {
-  IpRangePlan p;
-  p.big = nq > 128 ? IP_TILE_256 : IP_TILE_TALL;
-  p.tr = Tile256::TR;
-  p.tl = p.big == IP_TILE_256 ? Tile256::TL : TileTall::TL;
-  p.nq_pad = (nq + p.tl - 1) / p.tl * p.tl;
-  p.nQt = p.nq_pad / p.tl;
-  p.nPt = (int)ceil_div64(n, p.tr);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  p.o_qb = take((size_t)p.nq_pad * d * 2);
-  p.o_qnorm = take((size_t)p.nq_pad * 4);
-  p.o_tau = take((size_t)p.nq_pad * 4);
-  p.o_counts = take((size_t)p.nq_pad * IP_COUNT_STRIDE * 4);
-  p.o_m = take((size_t)p.nq_pad * 4);
-  p.o_nsurv = take((size_t)p.nq_pad * 4);
-  p.o_id = take((size_t)nq * cap * 4);
-  p.o_s = take((size_t)nq * cap * 4);
-  p.o_x = take((size_t)nq * cap * 8);
-  p.o_sx = take((size_t)nq * cap * 8);
-  p.total = o;
-  return p;
+// The range pipeline behind convdr_ip_range_search: every check of its arguments, then the launches.  b.store is in range.
+static int ip_range_search(const IpBlock& b, const float* q_f32, int nq, const float* centre, const float* radius, int cap,
+                           int count_only, void* workspace, size_t workspace_bytes, int64_t* counts, int64_t* lims,
+                           int32_t* status, hipStream_t st) {
+  const char* name = "convdr_ip_range_search";
+  if (int e = ip_check_sizes(IP_RANGE, nq, b.n, b.d, 0, cap)) return e;
+  CONVDR_REQUIRE(count_only == 0 || count_only == 1, "%s: count_only=%d (0 or 1)", name, count_only);
+  CONVDR_REQUIRE(!b.rows_f16() || centre == nullptr, "%s: the half store has no centre", name);
+  CONVDR_REQUIRE(b.row_bits != nullptr || b.row_bits_words == 0, "%s: row_bits is NULL but row_bits_words=%lld", name,
+                 (long long)b.row_bits_words);
+  if (int e = ip_check_block(name, b)) return e;
+  const IpRangePlan p = ip_range_plan(nq, b.n, b.d, cap);
+  if (int e = ip_check_workspace(name, workspace_bytes, p.total)) return e;
+  CONVDR_REQUIRE(q_f32 && radius && counts && status && (lims || count_only) && workspace,
+                 "%s: a NULL argument (q_f32, radius, workspace, counts, status; lims unless count_only)", name);
+  CONVDR_REQUIRE(b.n == 0 || (b.p_half && b.p_max_norm && (b.rows_f16() || b.p_f32)),
+                 "%s: a NULL block pointer (p_half, p_max_norm; p_f32 unless store = 2)", name);
+  if (b.n == 0) {
+    hipLaunchKernelGGL(k_ip_range_zero, dim3((nq + 256) / 256), dim3(256), 0, st, nq, counts, lims, status);
+    CONVDR_CHECK_LAUNCH("k_ip_range_zero");
+    return 0;
+  }
+  char* ws = (char*)workspace;
+  float* qnorm = (float*)(ws + p.o_qnorm);
+  float* tau = (float*)(ws + p.o_tau);
+  uint32_t* hits = (uint32_t*)(ws + p.o_counts);
+  uint32_t* m = (uint32_t*)(ws + p.o_m);
+  uint32_t* nsurv = (uint32_t*)(ws + p.o_nsurv);
+  uint32_t* list_id = (uint32_t*)(ws + p.o_id);
+  uint32_t* sort_id = (uint32_t*)(ws + p.o_s);     // (the scan scores are dead once the scan has ended)
+  double* list_x = (double*)(ws + p.o_x);
+  double* sort_x = (double*)(ws + p.o_sx);
+
+  if (int e = ip_prepare_queries(b, p, ws, q_f32, nq, nullptr, st)) return e;   // (one pass: no remainders)
+  hipLaunchKernelGGL(k_ip_range_tau, dim3((nq + 3) / 4), dim3(256), 0, st, q_f32, nq, b.d, centre, radius, qnorm, b.p_max_norm,
+                     b.scan_scale(), b.eps_coef(), b.eps_abs(), b.kind() == IP_KIND_F16 ? 1 : 0, tau);
+  CONVDR_CHECK_LAUNCH("k_ip_range_tau");
+  if (int e = launch_scan<IP_MODE_EMIT>(ip_scan_args(b, p, ws, nq, cap, nullptr, nullptr), p.big, b.kind(), st)) return e;
+  hipLaunchKernelGGL(k_ip_range_clamp, dim3((nq + 255) / 256), dim3(256), 0, st, hits, nq, cap, m);
+  CONVDR_CHECK_LAUNCH("k_ip_range_clamp");
+  {
+    ProfScope prof("ip_range_rescore", st);
+    if (int e = ip_rescore(b, q_f32, nq, nq < 64 ? 128 : 16, cap, m, list_id, list_x, st)) return e;
+  }
+  {
+    ProfScope prof("ip_range_select", st);
+    if (count_only) {
+      hipLaunchKernelGGL(k_ip_range_select<true>, dim3(nq), dim3(IP_RANGE_THREADS), 0, st, cap, hits, list_id, list_x, radius, qnorm,
+                         b.p_max_norm, b.scan_scale(), b.norm_limit(), sort_id, sort_x, nsurv, counts, status);
+    } else {
+      const int lds_n = cap < IP_RANGE_LDS_SORT ? cap : IP_RANGE_LDS_SORT;     // (>= IP_DEEP_TILE whenever deep_bitonic can run)
+      static DeviceOnce attr_done;
+      if (attr_done.first())
+        CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_range_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             IP_RANGE_LDS_SORT * 12));
+      hipLaunchKernelGGL(k_ip_range_select<false>, dim3(nq), dim3(IP_RANGE_THREADS), (size_t)lds_n * 12, st, cap, hits, list_id,
+                         list_x, radius, qnorm, b.p_max_norm, b.scan_scale(), b.norm_limit(), sort_id, sort_x, nsurv, counts, status);
+    }
+    CONVDR_CHECK_LAUNCH("k_ip_range_select");
+  }
+  if (lims) {
+    hipLaunchKernelGGL(k_ip_range_lims, dim3(1), dim3(IP_RANGE_THREADS), 0, st, nsurv, nq, lims);
+    CONVDR_CHECK_LAUNCH("k_ip_range_lims");
+  }
+  return 0;
 }
 
 }  // namespace convdr
 
 extern "C" size_t convdr_ip_range_workspace_bytes(int nq, int64_t n, int d, int cap) {
   using namespace convdr;
-  if (!ip_range_sizes_ok(nq, n, d, cap)) return 0;
+  if (ip_check_sizes(IP_RANGE, nq, n, d, 0, cap)) return 0;
   return ip_range_plan(nq, n, d, cap).total;
 }
 
@@ -283,113 +334,16 @@ extern "C" int convdr_ip_range_search(int store, const float* q_f32, int nq, con
   using namespace convdr;
   CONVDR_REQUIRE(store >= 0 && store <= 2, "convdr_ip_range_search: store must be 0 (bf16 copy), 1 (fp16 copy) or 2 (half store) "
                  "(got %d)", store);
-  CONVDR_REQUIRE(nq > 0, "convdr_ip_range_search: bad sizes nq=%d", nq);
-  CONVDR_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "convdr_ip_range_search: bad block size n=%lld (0 <= n < 2^31)", (long long)n);
-  CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_range_search: need d %% 64 == 0 and d <= 4096 (got %d)", d);
-  CONVDR_REQUIRE(cap >= IP_RANGE_MIN_CAP && cap <= IP_RANGE_MAX_CAP && (cap & (cap - 1)) == 0,
-                 "convdr_ip_range_search: cap must be a power of two in [1024, 131072] (got %d)", cap);
-  CONVDR_REQUIRE(count_only == 0 || count_only == 1, "convdr_ip_range_search: count_only=%d (0 or 1)", count_only);
-  if (store == 0) p_scale = 1.f;
-  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && (store != 2 || p_scale >= 1.f),
-                 "convdr_ip_range_search: p_scale must be a power of two%s (got %g)", store == 2 ? " >= 1" : "", (double)p_scale);
-  CONVDR_REQUIRE(store != 2 || centre == nullptr, "convdr_ip_range_search: the half store has no centre");
-  CONVDR_REQUIRE(row_bits != nullptr || row_bits_words == 0, "convdr_ip_range_search: row_bits is NULL but row_bits_words=%lld",
-                 (long long)row_bits_words);
-  if (row_bits) {
-    CONVDR_REQUIRE(((uintptr_t)row_bits & 15u) == 0, "convdr_ip_range_search: row_bits must be 16-byte aligned (the scan reads "
-                   "four words at a time)");
-    const int64_t words = ceil_div64(n, 256) * 8;
-    CONVDR_REQUIRE(row_bits_words >= words,
-                   "convdr_ip_range_search: the bitmap holds %lld words, n=%lld rows need %lld (whole 256-row tiles, zero padded)",
-                   (long long)row_bits_words, (long long)n, (long long)words);
-  }
-  const IpRangePlan p = ip_range_plan(nq, n, d, cap);
-  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_ip_range_search: workspace too small (%zu < %zu)", workspace_bytes, p.total);
-  CONVDR_REQUIRE(q_f32 && radius && counts && status && (lims || count_only) && workspace,
-                 "convdr_ip_range_search: a NULL argument (q_f32, radius, workspace, counts, status; lims unless count_only)");
-  CONVDR_REQUIRE(n == 0 || (p_half && p_max_norm && (store == 2 || p_f32)),
-                 "convdr_ip_range_search: a NULL block pointer (p_half, p_max_norm; p_f32 unless store = 2)");
-  hipStream_t st = (hipStream_t)stream;
-  if (n == 0) {
-    hipLaunchKernelGGL(k_ip_range_zero, dim3((nq + 256) / 256), dim3(256), 0, st, nq, counts, lims, status);
-    CONVDR_CHECK_LAUNCH("k_ip_range_zero");
-    return 0;
-  }
-  const int kind = store == 0 ? IP_KIND_BF16 : IP_KIND_F16;
-  const bool rows_f16 = store == 2;
-  char* ws = (char*)workspace;
-  bf16_t* qb = (bf16_t*)(ws + p.o_qb);
-  float* qnorm = (float*)(ws + p.o_qnorm);
-  float* tau = (float*)(ws + p.o_tau);
-  uint32_t* hits = (uint32_t*)(ws + p.o_counts);
-  uint32_t* m = (uint32_t*)(ws + p.o_m);
-  uint32_t* nsurv = (uint32_t*)(ws + p.o_nsurv);
-  uint32_t* list_id = (uint32_t*)(ws + p.o_id);
-  float* list_s = (float*)(ws + p.o_s);
-  uint32_t* sort_id = (uint32_t*)(ws + p.o_s);     // (the scan scores are dead once the scan has ended)
-  double* list_x = (double*)(ws + p.o_x);
-  double* sort_x = (double*)(ws + p.o_sx);
-
-  const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
-  if (kind == IP_KIND_F16)
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, (bf16_t*)nullptr, qnorm, (float*)nullptr, (int64_t)p.nq_pad, hits, n_count);
-  else
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_BF16, false>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, (bf16_t*)nullptr, qnorm, (float*)nullptr, (int64_t)p.nq_pad, hits, n_count);
-  CONVDR_CHECK_LAUNCH("k_rows_to_half(Q)");
-  const float eps_coef = ip_eps_coef(d, false, kind), eps_abs = ip_eps_abs(d, false, kind);
-  const float scan_scale = kind == IP_KIND_F16 ? p_scale : 1.f;
-  const float norm_limit = kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY;
-  hipLaunchKernelGGL(k_ip_range_tau, dim3((nq + 3) / 4), dim3(256), 0, st, q_f32, nq, d, rows_f16 ? (const float*)nullptr : centre,
-                     radius, qnorm, p_max_norm, scan_scale, eps_coef, eps_abs, kind == IP_KIND_F16 ? 1 : 0, tau);
-  CONVDR_CHECK_LAUNCH("k_ip_range_tau");
-  {
-    ScanArgs a{};
-    a.P = (const bf16_t*)p_half; a.Qb = qb; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad; a.d = d; a.nQt = p.nQt; a.tau = tau;
-    a.counts = hits; a.cand_id = list_id; a.cand_s = list_s; a.cap = cap; a.bits = row_bits;
-    a.nPt = p.nPt; a.pt_stride = 1;
-    if (int e = launch_scan<IP_MODE_EMIT>(a, p.big, kind, st)) return e;
-  }
-  hipLaunchKernelGGL(k_ip_range_clamp, dim3((nq + 255) / 256), dim3(256), 0, st, hits, nq, cap, m);
-  CONVDR_CHECK_LAUNCH("k_ip_range_clamp");
-  {
-    ProfScope prof("ip_range_rescore", st);
-    const int waves = nq < 64 ? 128 : 16;
-    if (rows_f16)
-      hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, waves), dim3(256), 0, st, q_f32, (const _Float16*)p_half, d, cap, m, list_id,
-                         list_x, 1.0 / (double)p_scale);
-    else
-      hipLaunchKernelGGL(k_ip_rescore<float>, dim3(nq, waves), dim3(256), 0, st, q_f32, p_f32, d, cap, m, list_id, list_x, 1.0);
-    CONVDR_CHECK_LAUNCH("k_ip_rescore");
-  }
-  {
-    ProfScope prof("ip_range_select", st);
-    if (count_only) {
-      hipLaunchKernelGGL(k_ip_range_select<true>, dim3(nq), dim3(IP_RANGE_THREADS), 0, st, cap, hits, list_id, list_x, radius, qnorm,
-                         p_max_norm, scan_scale, norm_limit, sort_id, sort_x, nsurv, counts, status);
-    } else {
-      const int lds_n = cap < IP_RANGE_LDS_SORT ? cap : IP_RANGE_LDS_SORT;     // (>= IP_DEEP_TILE whenever deep_bitonic can run)
-      static DeviceOnce attr_done;
-      if (attr_done.first())
-        CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_range_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             IP_RANGE_LDS_SORT * 12));
-      hipLaunchKernelGGL(k_ip_range_select<false>, dim3(nq), dim3(IP_RANGE_THREADS), (size_t)lds_n * 12, st, cap, hits, list_id,
-                         list_x, radius, qnorm, p_max_norm, scan_scale, norm_limit, sort_id, sort_x, nsurv, counts, status);
-    }
-    CONVDR_CHECK_LAUNCH("k_ip_range_select");
-  }
-  if (lims) {
-    hipLaunchKernelGGL(k_ip_range_lims, dim3(1), dim3(IP_RANGE_THREADS), 0, st, nsurv, nq, lims);
-    CONVDR_CHECK_LAUNCH("k_ip_range_lims");
-  }
-  return 0;
+  // (one pass: no remainder copy; n_allowed is top-k's)
+  const IpBlock b = {store, p_f32, p_half, nullptr, store == 0 ? 1.f : p_scale, false, n, d, p_max_norm, row_bits, row_bits_words, 0};
+  return ip_range_search(b, q_f32, nq, centre, radius, cap, count_only, workspace, workspace_bytes, counts, lims, status,
+                         (hipStream_t)stream);
 }
 
 extern "C" int convdr_ip_range_pack(const void* workspace, int nq, int64_t n, int d, int cap, const int64_t* lims, float* D,
                                     int64_t* I, double* X, convdr_stream_t stream) {
   using namespace convdr;
-  CONVDR_REQUIRE(ip_range_sizes_ok(nq, n, d, cap),
+  CONVDR_REQUIRE(ip_check_sizes(IP_RANGE, nq, n, d, 0, cap) == 0,
                  "convdr_ip_range_pack: sizes outside the contract of convdr_ip_range_search (nq=%d n=%lld d=%d cap=%d)", nq,
                  (long long)n, d, cap);
   CONVDR_REQUIRE(workspace && lims && D && I, "convdr_ip_range_pack: a NULL argument (workspace, lims, D, I)");

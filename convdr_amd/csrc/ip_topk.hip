@@ -1155,65 +1155,10 @@ __global__ void __launch_bounds__(1024) k_ip_finish(int64_t n, int k, int cap, c
 }
 
 // ------------------------------------------------------------------------------------------
-// host-side plan shared by workspace sizing and the search call
+// the scan launcher: one entry, launch_scan<MODE>, for every caller (the host pipelines follow in ip_host.hpp)
 // ------------------------------------------------------------------------------------------
-constexpr int IP_TILE_256 = 1, IP_TILE_TALL = 2;
-struct IpPlan {
-  int big;           // scan tile class: IP_TILE_256 (more than 128 queries), IP_TILE_TALL (256 passages x 128 queries: the
-                     // HBM-bound regime)
-  int tr, tl;        // tile extent over passages / queries
-  int nq_pad, nQt, nPt;
-  int mode;          // -1: no threshold pass (n <= cap), else IP_MODE_FULL / IP_MODE_TOP2
-  int nSt, stride;   // sampled passage tiles / tile stride
-  int64_t nvals;     // values per query handed to k_tau_select
-  int npow2;
-  size_t o_qb, o_qlo, o_qnorm, o_tau, o_counts, o_counts_packed, o_m, o_T, o_id, o_s, o_x, total;
-};
-
+constexpr int IP_TILE_256 = 1, IP_TILE_TALL = 2;   // scan tile classes (IpPlanHead::big)
 int64_t g_ip_fused_finish = 1;   // convdr_set_option("ip_fused_finish"): 1 = k_ip_finish, 0 = k_ip_cut + k_ip_rescore + k_ip_select
-
-static IpPlan ip_plan(int nq, int64_t n, int d, int k, int cap) {
-  IpPlan p;
-  p.big = nq > 128 ? IP_TILE_256 : IP_TILE_TALL;
-  p.tr = Tile256::TR;   // = TileTall::TR
-  p.tl = p.big == IP_TILE_256 ? Tile256::TL : TileTall::TL;
-  p.nq_pad = (nq + p.tl - 1) / p.tl * p.tl;
-  p.nQt = p.nq_pad / p.tl;
-  p.nPt = (int)ceil_div64(n, p.tr);
-  p.nSt = 0; p.stride = 1; p.nvals = 0; p.npow2 = 2;
-  if (n <= cap) {
-    p.mode = -1;
-  } else if (n <= IP_FULL_MAX_N) {
-    p.mode = IP_MODE_FULL; p.nSt = p.nPt; p.nvals = n;
-  } else {
-    p.mode = IP_MODE_TOP2;
-    int64_t S = n / 32;
-    if (S < IP_SAMPLE_MIN) S = IP_SAMPLE_MIN;
-    if (S > IP_SAMPLE_MAX) S = IP_SAMPLE_MAX;
-    p.nSt = (int)(S / p.tr);
-    if (p.nSt > p.nPt) p.nSt = p.nPt;
-    p.stride = p.nPt / p.nSt;
-    p.nvals = (int64_t)p.nSt * 8;   // WR * 2 halves * 2 values per tile, WR = 2 for both tile shapes
-  }
-  while (p.npow2 < p.nvals) p.npow2 <<= 1;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  p.o_qb = take((size_t)p.nq_pad * d * 2);
-  p.o_qlo = take((size_t)p.nq_pad * d * 2);
-  p.o_qnorm = take((size_t)p.nq_pad * 4);
-  p.o_tau = take((size_t)p.nq_pad * 4);
-  p.o_counts = take((size_t)p.nq_pad * IP_COUNT_STRIDE * 4);
-  p.o_counts_packed = take((size_t)p.nq_pad * 4);
-  p.o_m = take((size_t)p.nq_pad * 4);
-  const size_t t_rows = p.mode == IP_MODE_FULL ? (size_t)p.nPt * p.tr : (size_t)p.nvals;
-  p.o_T = take(t_rows * p.nq_pad * 4);
-  p.o_id = take((size_t)nq * cap * 4);
-  p.o_s = take((size_t)nq * cap * 4);
-  p.o_x = take((size_t)nq * cap * 8);
-  p.total = o;
-  (void)k;
-  return p;
-}
 
 template <int MODE, class T, int PASSES, bool F16, bool FILT>
 static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
@@ -1275,8 +1220,12 @@ static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) { 
 
 }  // namespace convdr
 
-// k > 4096: the same cut / re-score / select through global memory (convdr_ip_search_deep*)
+// the host side: block descriptor, argument checks, plan head, shared steps and the shallow pipeline (k <= 4096)
+#include "ip_host.hpp"
+// k > 4096: the same cut / re-score / select through global memory
 #include "ip_deep.hpp"
+// range search: every row scoring above a per-query radius (convdr_ip_range_*)
+#include "ip_range.hpp"
 
 using namespace convdr;
 
@@ -1673,181 +1622,21 @@ extern "C" float convdr_ip_f16_scale(float max_norm) {
   return ldexpf(1.f, sh);
 }
 
+// The shallow plan's size for any nq, n, d it can be computed for: k and cap are not checked here (the search entries do).
 extern "C" size_t convdr_ip_workspace_bytes(int nq, int64_t n, int d, int k, int cap) {
   if (nq <= 0 || n < 0 || d <= 0) return 0;
-  return ip_plan(nq, n, d, k, cap).total;
+  return ip_plan(nq, n, d, cap).total;
 }
 
 extern "C" const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap) {
-  return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, k, cap).o_counts_packed);
+  return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, cap).o_counts_packed);
 }
 
 extern "C" const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, int64_t n, int d, int k, int cap) {
-  return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, k, cap).o_m);
-}
-
-// rows_f16: the half store -- p_f32 is not used, the re-score reads p_bf16 (halves of 2^s v, p_scale = 2^s) and
-// two_pass selects its second rung (no remainder copy: p_bf16_lo is NULL).
-// row_bits: the row filter (convdr_ip_search_filtered; NULL = every row, and then n_allowed is not read).  The scan emits
-// allowed rows only and samples -inf for the others; the finishing kernels take n_allowed where they took n (need = min(k,
-// n_allowed)); n_allowed <= cap: every allowed row is a candidate -- no threshold pass, tau = -inf.
-static int ip_search(int kind, float p_scale, const float* q_f32, int nq, const float* p_f32, const void* p_bf16,
-                     const void* p_bf16_lo, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
-                     int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
-                     float* tau_retry, hipStream_t st, bool rows_f16 = false, bool two_pass = false,
-                     const uint32_t* row_bits = nullptr, int64_t n_allowed = -1) {
-  CONVDR_REQUIRE(nq > 0 && k > 0 && n >= 0, "convdr_ip_search: bad sizes nq=%d k=%d n=%lld", nq, k, (long long)n);
-  CONVDR_REQUIRE(d > 0 && d % 64 == 0 && d <= 4096, "convdr_ip_search: need d %% 64 == 0 and d <= 4096 (got %d)", d);
-  CONVDR_REQUIRE(n < ((int64_t)1 << 31), "convdr_ip_search: block too large (n=%lld >= 2^31)", (long long)n);
-  CONVDR_REQUIRE(cap >= 1024 && cap <= 8192 && (cap & (cap - 1)) == 0,
-                 "convdr_ip_search: cap must be a power of two in [1024, 8192] (got %d)", cap);
-  CONVDR_REQUIRE(k <= cap / 2, "convdr_ip_search: k=%d too large for cap=%d", k, cap);
-  const IpPlan p = ip_plan(nq, n, d, k, cap);
-  CONVDR_REQUIRE(workspace_bytes >= p.total, "convdr_ip_search: workspace too small (%zu < %zu)", workspace_bytes,
-                 p.total);
-  const int64_t n_need = row_bits ? n_allowed : n;        // rows the result can hold: need = min(k, n_need)
-  const bool all_candidates = p.mode < 0 || (row_bits && n_allowed <= cap);
-  char* ws = (char*)workspace;
-  bf16_t* qb = (bf16_t*)(ws + p.o_qb);
-  float* qnorm = (float*)(ws + p.o_qnorm);
-  float* tau = (float*)(ws + p.o_tau);
-  uint32_t* counts = (uint32_t*)(ws + p.o_counts);
-  float* T = (float*)(ws + p.o_T);
-  uint32_t* cand_id = (uint32_t*)(ws + p.o_id);
-  float* cand_s = (float*)(ws + p.o_s);
-  double* cand_x = (double*)(ws + p.o_x);
-  uint32_t* band = (uint32_t*)(ws + p.o_m);
-
-  // queries -> 16-bit operands (+ norms); the kernel also zeroes the padding rows and the candidate counters
-  const bool split = p_bf16_lo != nullptr || two_pass;   // the query's remainder is an operand: the tighter error band
-  const double unscale = 1.0 / (double)p_scale;
-  bf16_t* qlo = split ? (bf16_t*)(ws + p.o_qlo) : nullptr;
-  const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
-  if (kind == IP_KIND_F16)
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);
-  else
-    hipLaunchKernelGGL((k_rows_to_half<IP_KIND_BF16, false>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, d,
-                       (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);
-  CONVDR_CHECK_LAUNCH("k_rows_to_half(Q)");
-
-  if (n == 0) {
-    hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
-  } else {
-    ScanArgs a{};
-    a.P = (const bf16_t*)p_bf16; a.Qb = qb; a.Plo = (const bf16_t*)p_bf16_lo; a.Qlo = qlo; a.n = n; a.nq = nq; a.nq_pad = p.nq_pad; a.d = d;
-    a.nQt = p.nQt; a.tau = tau; a.counts = counts; a.cand_id = cand_id; a.cand_s = cand_s; a.cap = cap; a.T = T;
-    a.two_pass = two_pass ? 1 : 0;
-    a.bits = row_bits;
-    if (tau_in) {
-      CONVDR_CHECK_HIP(hipMemcpyAsync(tau, tau_in, (size_t)nq * 4, hipMemcpyDeviceToDevice, st));
-    } else if (all_candidates) {
-      hipLaunchKernelGGL(k_fill_f32, dim3((p.nq_pad + 255) / 256), dim3(256), 0, st, tau, p.nq_pad, -INFINITY);
-      CONVDR_CHECK_LAUNCH("k_fill_f32");
-    } else {
-      int R = rank_target > 0 ? rank_target : 16 * k;
-      if (R > cap / 2) R = cap / 2;
-      if (R < k) R = k;
-      int r;
-      a.nPt = p.nSt; a.pt_stride = p.stride;
-      if (p.mode == IP_MODE_FULL) {
-        r = (int64_t)R < n ? R : (int)n;
-        if (int e = launch_scan<IP_MODE_FULL>(a, p.big, kind, st)) return e;
-      } else {
-        // The sample keeps the two best scores of every 64 sampled passages, so it can only represent a rank whose expected
-        // hits per 64 passages stay well below 2: R <= n / 128 (half a hit per 64).  Blocks of 32 k .. 200 k passages
-        // therefore aim at a lower rank than 16 k (n = 47,104 asked for rank 1,113 of a 1,024-value sample: no threshold,
-        // every passage emitted, every query overflowed and was re-run); a band that then reaches below the threshold
-        // comes back UNCERTAIN with the threshold to retry, as for any clustered block.
-        if ((int64_t)R > n / 128) R = (int)(n / 128 > k ? n / 128 : k);
-        const double frac = (double)p.nSt * p.tr / (double)n;
-        r = (int)lrint(R * frac);
-        if (r < 8) r = 8;
-        if (r > p.nvals / 4) r = (int)(p.nvals / 4);
-        if (int e = launch_scan<IP_MODE_TOP2>(a, p.big, kind, st)) return e;
-      }
-      static DeviceOnce attr_done;
-      if (attr_done.first())
-        CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_tau_select, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             IP_FULL_MAX_N * 4));
-      hipLaunchKernelGGL(k_tau_select, dim3(nq), dim3(1024), (size_t)p.npow2 * 4, st, T, p.nvals, p.nq_pad, r, tau);
-      CONVDR_CHECK_LAUNCH("k_tau_select");
-    }
-    a.nPt = p.nPt; a.pt_stride = 1;
-    if (int e = launch_scan<IP_MODE_EMIT>(a, p.big, kind, st)) return e;
-  }
-  static DeviceOnce attr_done2;
-  if (attr_done2.first()) {
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_cut, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    CONVDR_CHECK_HIP(
-        hipFuncSetAttribute((const void*)k_ip_select, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 12));
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
-  }
-  const float eps_coef = ip_eps_coef(d, split, kind), eps_abs = ip_eps_abs(d, split, kind);
-  if (g_ip_fused_finish && n > 0) {
-    ProfScope prof("ip_finish", st);
-    if (rows_f16)
-      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n_need, k, cap, counts,
-                         (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs, p_scale,
-                         IP_F16_NORM_LIMIT, q_f32, (const _Float16*)p_bf16, d, band, status, tau_retry, D, I, unscale);
-    else
-      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(1024), (size_t)cap * 16, st, n_need, k, cap, counts,
-                         (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm, p_max_norm, eps_coef, eps_abs,
-                         kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, q_f32, p_f32, d,
-                         band, status, tau_retry, D, I, 1.0);
-    CONVDR_CHECK_LAUNCH("k_ip_finish");
-    return 0;
-  }
-  {
-  ProfScope prof("ip_cut", st);
-  hipLaunchKernelGGL(k_ip_cut, dim3(nq), dim3(1024), (size_t)cap * 8, st, n_need, k, cap, counts,
-                     (uint32_t*)(ws + p.o_counts_packed), cand_id, cand_s, tau, qnorm,
-                     p_max_norm, eps_coef, eps_abs,
-                     kind == IP_KIND_F16 ? p_scale : 1.f, kind == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY, band, status,
-                     tau_retry);
-  CONVDR_CHECK_LAUNCH("k_ip_cut");
-  }
-  if (n > 0) {
-    ProfScope prof("ip_rescore", st);
-    if (rows_f16)
-      hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, 16), dim3(256), 0, st, q_f32, (const _Float16*)p_bf16, d, cap, band,
-                         cand_id, cand_x, unscale);
-    else
-      hipLaunchKernelGGL(k_ip_rescore<float>, dim3(nq, 16), dim3(256), 0, st, q_f32, p_f32, d, cap, band, cand_id, cand_x, 1.0);
-    CONVDR_CHECK_LAUNCH("k_ip_rescore");
-  }
-  ProfScope prof("ip_select", st);
-  hipLaunchKernelGGL(k_ip_select, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 12, st, k, cap, band, cand_id, cand_x, D, I);
-  CONVDR_CHECK_LAUNCH("k_ip_select");
-  return 0;
-}
-
-extern "C" int convdr_ip_search(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo,
-                                int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
-                                int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
-                                int32_t* status, float* tau_retry, convdr_stream_t stream) {
-  return ip_search(IP_KIND_BF16, 1.f, q_f32, nq, p_f32, p_bf16, p_bf16_lo, n, d, k, p_max_norm, tau_in, cap, rank_target,
-                   workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream);
-}
-
-extern "C" int convdr_ip_search_f16(const float* q_f32, int nq, const float* p_f32, const void* p_f16, const void* p_f16_lo,
-                                    float p_scale, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in,
-                                    int cap, int rank_target, void* workspace, size_t workspace_bytes, float* D,
-                                    int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream) {
-  int ex = 0;
-  CONVDR_REQUIRE(p_scale > 0.f && frexpf(p_scale, &ex) == 0.5f, "convdr_ip_search_f16: p_scale must be a power of two (got %g)",
-                 (double)p_scale);
-  return ip_search(IP_KIND_F16, p_scale, q_f32, nq, p_f32, p_f16, p_f16_lo, n, d, k, p_max_norm, tau_in, cap, rank_target,
-                   workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream);
+  return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, cap).o_m);
 }
 
 // ---- the half store ------------------------------------------------------------------------------------------------
-static bool ip_pow2_scale_ok(float s) {   // a finite power of two
-  int ex = 0;
-  return s > 0.f && s < INFINITY && frexpf(s, &ex) == 0.5f;
-}
-
 extern "C" int convdr_ip_store_rows_f16(const void* src, int src_is_f32, int64_t n, int d, float scale, void* store,
                                         float* max_norm, int32_t* flags, convdr_stream_t stream) {
   CONVDR_REQUIRE(n >= 0 && d > 0 && d % 64 == 0, "convdr_ip_store_rows_f16: need d %% 64 == 0 (got n=%lld d=%d)", (long long)n, d);
@@ -1869,64 +1658,81 @@ extern "C" int convdr_ip_store_rows_f16(const void* src, int src_is_f32, int64_t
   return 0;
 }
 
+// ---- exact top-k: seven entries, one validated call ------------------------------------------------------------------
+// Every top-k entry ends here, the direct ones with a block that has no bitmap: the checks, then the depth's plan and pipeline
+// (which checks the workspace against its plan first).  `name`: the entry that was called.
+static int ip_topk(const char* name, bool deep, IpBlock b, const IpTopkArgs& c) {
+  if (int e = ip_check_sizes(deep ? IP_DEEP : IP_SHALLOW, c.nq, b.n, b.d, c.k, c.cap)) return e;
+  CONVDR_REQUIRE(!deep || c.rank_target >= 0, "%s: rank_target=%d", name, c.rank_target);
+  if (int e = ip_check_block(name, b)) return e;
+  // no allowed row: the empty block's path (no scan; the finishing kernels pad every row of D / I)
+  if (b.row_bits && b.n_allowed == 0) b.n = 0;
+  if (deep) return ip_search_deep(name, b, c, ip_deep_plan(c.nq, b.n, b.d, c.k, c.cap, c.rank_target));
+  return ip_search(name, b, c, ip_plan(c.nq, b.n, b.d, c.cap));
+}
+
+// the per-call arguments, which the seven entries name alike (as include/convdr_hip.h does)
+#define IP_TOPK_ARGS {q_f32, nq, k, tau_in, cap, rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream}
+
+extern "C" int convdr_ip_search(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo,
+                                int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
+                                int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
+                                int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search", false, {0, p_f32, p_bf16, p_bf16_lo, 1.f, false, n, d, p_max_norm}, IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_search_f16(const float* q_f32, int nq, const float* p_f32, const void* p_f16, const void* p_f16_lo,
+                                    float p_scale, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in,
+                                    int cap, int rank_target, void* workspace, size_t workspace_bytes, float* D,
+                                    int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search_f16", false, {1, p_f32, p_f16, p_f16_lo, p_scale, false, n, d, p_max_norm}, IP_TOPK_ARGS);
+}
+
 extern "C" int convdr_ip_search_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n, int d,
                                     int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
                                     size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
                                     convdr_stream_t stream) {
-  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && p_scale >= 1.f,
-                 "convdr_ip_search_h16: p_scale must be a power of two >= 1 (got %g)", (double)p_scale);
-  return ip_search(IP_KIND_F16, p_scale, q_f32, nq, nullptr, store_f16, nullptr, n, d, k, p_max_norm, tau_in, cap, rank_target,
-                   workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, true, two_pass != 0);
+  return ip_topk("convdr_ip_search_h16", false,
+                 {2, nullptr, store_f16, nullptr, p_scale, two_pass != 0, n, d, p_max_norm}, IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_search_deep(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo,
+                                     int64_t n, int d, int k, const float* p_max_norm, const float* tau_in, int cap,
+                                     int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
+                                     int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search_deep", true, {0, p_f32, p_bf16, p_bf16_lo, 1.f, false, n, d, p_max_norm}, IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_search_deep_f16(const float* q_f32, int nq, const float* p_f32, const void* p_f16, const void* p_f16_lo,
+                                         float p_scale, int64_t n, int d, int k, const float* p_max_norm, const float* tau_in,
+                                         int cap, int rank_target, void* workspace, size_t workspace_bytes, float* D,
+                                         int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search_deep_f16", true, {1, p_f32, p_f16, p_f16_lo, p_scale, false, n, d, p_max_norm}, IP_TOPK_ARGS);
 }
 
 extern "C" int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void* store_f16, float p_scale, int two_pass, int64_t n,
                                          int d, int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target,
                                          void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
                                          float* tau_retry, convdr_stream_t stream) {
-  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && p_scale >= 1.f,
-                 "convdr_ip_search_deep_h16: p_scale must be a power of two >= 1 (got %g)", (double)p_scale);
-  return ip_search_deep(IP_KIND_F16, p_scale, q_f32, nq, nullptr, store_f16, nullptr, n, d, k, p_max_norm, tau_in, cap,
-                        rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, true, two_pass != 0);
+  return ip_topk("convdr_ip_search_deep_h16", true,
+                 {2, nullptr, store_f16, nullptr, p_scale, two_pass != 0, n, d, p_max_norm}, IP_TOPK_ARGS);
 }
 
-// ---- row-filtered search: the six entries above restricted to the rows whose bit is set ------------------------------
+// Row-filtered search: the six entries above restricted to the rows whose bit is set; its own arguments are checked here.
 extern "C" int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, const float* p_f32, const void* p_half,
                                          const void* p_half_lo, float p_scale, int two_pass, int64_t n, int d, int k,
                                          const float* p_max_norm, const float* tau_in, int cap, int rank_target, void* workspace,
                                          size_t workspace_bytes, const uint32_t* row_bits, int64_t row_bits_words,
                                          int64_t n_allowed, float* D, int64_t* I, int32_t* status, float* tau_retry,
                                          convdr_stream_t stream) {
+  const char* name = "convdr_ip_search_filtered";
   CONVDR_REQUIRE(store >= 0 && store <= 2 && (deep == 0 || deep == 1),
-                 "convdr_ip_search_filtered: store must be 0 (bf16 copy), 1 (fp16 copy) or 2 (half store) and deep 0 or 1 "
-                 "(got store=%d deep=%d)", store, deep);
-  CONVDR_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "convdr_ip_search_filtered: bad block size n=%lld", (long long)n);
-  CONVDR_REQUIRE(row_bits != nullptr, "convdr_ip_search_filtered: row_bits is NULL");
-  CONVDR_REQUIRE(((uintptr_t)row_bits & 15u) == 0, "convdr_ip_search_filtered: row_bits must be 16-byte aligned (the scan reads "
-                 "four words at a time)");
-  const int64_t words = ceil_div64(n, 256) * 8;
-  CONVDR_REQUIRE(row_bits_words >= words,
-                 "convdr_ip_search_filtered: the bitmap holds %lld words, n=%lld rows need %lld (whole 256-row tiles, zero padded)",
-                 (long long)row_bits_words, (long long)n, (long long)words);
-  CONVDR_REQUIRE(n_allowed >= 0 && n_allowed <= n, "convdr_ip_search_filtered: n_allowed=%lld outside [0, n=%lld]",
-                 (long long)n_allowed, (long long)n);
-  CONVDR_REQUIRE(two_pass == 0 || (two_pass == 1 && store == 2),
-                 "convdr_ip_search_filtered: two_pass=%d (0, or 1 with the half store)", two_pass);
-  CONVDR_REQUIRE(store != 2 || p_half_lo == nullptr, "convdr_ip_search_filtered: the half store has no remainder copy");
-  if (store == 0) p_scale = 1.f;
-  CONVDR_REQUIRE(ip_pow2_scale_ok(p_scale) && (store != 2 || p_scale >= 1.f),
-                 "convdr_ip_search_filtered: p_scale must be a power of two%s (got %g)", store == 2 ? " >= 1" : "", (double)p_scale);
-  const int kind = store == 0 ? IP_KIND_BF16 : IP_KIND_F16;
-  const bool rows_f16 = store == 2;
-  // no allowed row: the empty block's path (no scan; the finishing kernels pad every row of D / I)
-  const int64_t n_run = n_allowed == 0 ? 0 : n;
-  if (deep)
-    return ip_search_deep(kind, p_scale, q_f32, nq, rows_f16 ? nullptr : p_f32, p_half, p_half_lo, n_run, d, k, p_max_norm, tau_in,
-                          cap, rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, rows_f16,
-                          two_pass != 0, row_bits, n_allowed);
-  return ip_search(kind, p_scale, q_f32, nq, rows_f16 ? nullptr : p_f32, p_half, p_half_lo, n_run, d, k, p_max_norm, tau_in, cap,
-                   rank_target, workspace, workspace_bytes, D, I, status, tau_retry, (hipStream_t)stream, rows_f16, two_pass != 0,
-                   row_bits, n_allowed);
+                 "%s: store must be 0 (bf16 copy), 1 (fp16 copy) or 2 (half store) and deep 0 or 1 (got store=%d deep=%d)", name, store,
+                 deep);
+  CONVDR_REQUIRE(row_bits != nullptr, "%s: row_bits is NULL", name);
+  CONVDR_REQUIRE(n_allowed >= 0 && n_allowed <= n, "%s: n_allowed=%lld outside [0, n=%lld]", name, (long long)n_allowed, (long long)n);
+  CONVDR_REQUIRE(two_pass == 0 || (two_pass == 1 && store == 2), "%s: two_pass=%d (0, or 1 with the half store)", name, two_pass);
+  CONVDR_REQUIRE(store != 2 || p_half_lo == nullptr, "%s: the half store has no remainder copy", name);
+  return ip_topk(name, deep != 0, {store, p_f32, p_half, p_half_lo, store == 0 ? 1.f : p_scale, two_pass != 0, n, d, p_max_norm,
+                                   row_bits, row_bits_words, n_allowed}, IP_TOPK_ARGS);
 }
-
-// ---- range search: every row scoring above a per-query radius (convdr_ip_range_*) -------------------------------------
-#include "ip_range.hpp"

@@ -126,7 +126,7 @@ int convdr_ip_search_f16(const float* q_f32, int nq, const float* p_f32, const v
  * 4 x [nq_pad] x 4, hit counters [nq_pad] x 128, the sample's scores [rows, nq_pad] x 4 (rows: the tallest sample k allows, reserved for every n), then per query and list
  * slot 28 bytes: list id 4 + list scan score 4 + band id 4 + band fp64 score 8 + ordered fp64 score 8 (the ordered ids
  * reuse the list ids) = nq * cap * 28.  Arguments are validated before anything touches a device. */
-size_t convdr_ip_deep_workspace_bytes(int nq, int64_t n, int d, int k, int cap);   /* 0 for sizes outside the contract */
+size_t convdr_ip_deep_workspace_bytes(int nq, int64_t n, int d, int k, int cap);   /* 0 outside the contract: convdr_last_error says why */
 int convdr_ip_search_deep(const float* q_f32, int nq, const float* p_f32, const void* p_bf16, const void* p_bf16_lo, int64_t n,
                           int d, int k, const float* p_max_norm, const float* tau_in, int cap, int rank_target,
                           void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status,
@@ -197,8 +197,7 @@ int convdr_ip_search_deep_h16(const float* q_f32, int nq, const void* store_f16,
  *                deep = 0 / 1: the shallow or the deep entry, with that entry's contract for cap and k and its workspace size
  *                (convdr_ip_workspace_bytes / convdr_ip_deep_workspace_bytes, planned by n, not by n_allowed).
  * Every other argument, output and status word is the matching entry's; both settings of the option ip_fused_finish work.
- * Arguments are validated before anything touches a device (row_bits != NULL and 16-byte aligned, row_bits_words, 0 <= n_allowed <= n, store and
- * deep in range, then the matching entry's size contracts). */
+ * Arguments are validated before anything touches a device. */
 int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, const float* p_f32, const void* p_half,
                               const void* p_half_lo, float p_scale, int two_pass, int64_t n, int d, int k, const float* p_max_norm,
                               const float* tau_in, int cap, int rank_target, void* workspace, size_t workspace_bytes,
@@ -232,7 +231,7 @@ int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, c
  *   cap          a power of two in [1024, 131072]: entries of a query's list, which lives in global memory at every cap.
  *   count_only   1: re-score, predicate and count only -- counts and status are written, lims too unless it is NULL (it
  *                may be), nothing is ordered and convdr_ip_range_pack must not follow.
- *   workspace    convdr_ip_range_workspace_bytes(nq, n, d, cap) bytes (0 for sizes outside the contract), 256-byte aligned
+ *   workspace    convdr_ip_range_workspace_bytes(nq, n, d, cap) bytes (0 outside the contract: convdr_last_error says why), 256-byte aligned
  *                regions in this order: query operands [nq_pad, d] x 2 | query norms [nq_pad] | tau [nq_pad] | hit counters
  *                [nq_pad x 32] | min(hits, cap) [nq_pad] | survivor counts [nq_pad] | list ids [nq, cap] u32 | list scan
  *                scores [nq, cap] f32 (then: the survivors' ids) | list canonical scores [nq, cap] f64 | survivors' scores

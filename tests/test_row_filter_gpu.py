@@ -310,6 +310,58 @@ def test_both_settings_of_ip_fused_finish(torch_cuda, storage, precision):
         L.convdr_set_option(b"ip_fused_finish", 1)
 
 
+@pytest.mark.parametrize("n,nq,k,cap", [(5 * 256 + 37, 3, 10, 1024),            # shallow, n > cap: threshold pass; tall tile, ragged last tile
+                                        (5 * 256 + 37, 129, 10, 1024),          # the 256 x 256 tile
+                                        (0, 3, 10, 1024),
+                                        (16384 + 256 + 37, 3, 4097, 16384),     # deep, n > cap: segment samples
+                                        (0, 3, 4097, 16384)])
+@pytest.mark.parametrize("storage,precision", [("fp32", "bf16"), ("fp32", "fp16"), ("fp16", "fp16")])
+def test_all_ones_bitmap_is_the_direct_entry_bit_for_bit(torch_cuda, storage, precision, n, nq, k, cap):
+    """The direct entry of the store and depth, then convdr_ip_search_filtered with every bit set and n_allowed = n, on the same
+    operands and the same workspace size: one host pipeline serves both, so D, I and status agree bit for bit -- and tau_retry
+    where a status asks for a retry.  (Every query of these shapes is certified on its first pass, so the tau_retry clause
+    compares nothing today; it stands for shapes added later.)"""
+    torch = torch_cuda
+    from convdr_amd import _lib
+    from convdr_amd.search import FlatIPIndex, RowFilter
+    d = 64
+    idx = FlatIPIndex(d, storage=storage, precision=precision, prepin=False)
+    Q = synth_corpus(7, nq, d)
+    q = torch.from_numpy(Q).cuda()
+    if n:
+        P = synth_corpus(100 + n % 97, n, d).astype(np.float16)
+        idx.add(P if storage == "fp16" else P.astype(np.float32))
+        f = idx.row_filter(np.ones(n, bool))
+        p32, p16 = idx._rows, idx._pbf
+    else:                                    # an empty block: the pointers are never dereferenced, the bitmap must still be one
+        f = RowFilter(torch.full((8,), -1, dtype=torch.int32, device="cuda"), 0, 0)
+        p32 = p16 = q
+    assert f.n_allowed == n
+    deep = k > idx.MAX_K
+    L = _lib.lib()
+    need = (L.convdr_ip_deep_workspace_bytes if deep else L.convdr_ip_workspace_bytes)(nq, n, d, k, cap)
+    runs = []
+    for allowed in (None, f):
+        ws = fill_bytes(torch.empty(need, dtype=torch.uint8, device="cuda"), "R", 9)
+        D = fill_bytes(torch.empty((nq, k), dtype=torch.float32, device="cuda"), "R", 10)
+        I = fill_bytes(torch.empty((nq, k), dtype=torch.int64, device="cuda"), "R", 11)
+        st = fill_bytes(torch.empty(nq, dtype=torch.int32, device="cuda"), "R", 12)
+        tr = fill_bytes(torch.empty(nq, dtype=torch.float32, device="cuda"), "R", 13)
+        idx._search_call(q, nq, p32, p16, None, n, k, None, cap, 0, ws, D, I, st, tr, False, deep, allowed)
+        torch.cuda.synchronize()
+        runs.append((D.cpu().numpy().view(np.uint32), I.cpu().numpy(), st.cpu().numpy(), tr.cpu().numpy().view(np.uint32)))
+    (Da, Ia, sa, ta), (Db, Ib, sb, tb) = runs
+    print("status direct", np.bincount(sa, minlength=5).tolist(), "filtered", np.bincount(sb, minlength=5).tolist())
+    np.testing.assert_array_equal(sa, sb)
+    np.testing.assert_array_equal(Ia, Ib)
+    np.testing.assert_array_equal(Da, Db)
+    np.testing.assert_array_equal(ta[sa != 0], tb[sa != 0])
+    if n == 0:
+        assert (sa == 0).all() and (Ia == -1).all()
+    else:
+        assert (Ia[sa == 0][:, :min(k, n)] >= 0).all()
+
+
 @pytest.mark.parametrize("storage,n,nq,k,d", [("fp32", 5000, 37, 100, 768), ("fp16", 5000, 37, 100, 768),
                                               ("fp32", 40000, 24, 100, 768), ("fp16", 20000, 4, 5000, 64)])
 def test_result_does_not_depend_on_stale_workspace_or_outputs(torch_cuda, storage, n, nq, k, d):
