@@ -155,6 +155,7 @@ register("convdr_encoder_train_workspace_bytes", C.c_size_t, [C.POINTER(EncoderC
 register("convdr_encoder_train_forward", C.c_int, [C.POINTER(EncoderConfig), C.POINTER(EncoderWeights), _p, C.c_int, _p,
                                                    C.c_int, C.c_int, _p, _p, C.c_int64, C.c_int, _p, C.c_size_t, _p,
                                                    C.POINTER(Dropout), _p])
+register("convdr_encoder_train_debug_layout", C.c_int, [C.POINTER(EncoderConfig), C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int])
 register("convdr_encoder_backward", C.c_int, [C.POINTER(EncoderConfig), C.POINTER(EncoderWeights), C.POINTER(LayerWeightsT),
                                               _p, _p, _p, C.c_int, C.c_int64, C.c_int, _p, C.c_size_t, _p,
                                               C.POINTER(EncoderGrads), C.POINTER(Dropout), _p])

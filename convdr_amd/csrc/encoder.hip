@@ -422,6 +422,10 @@ extern "C" int convdr_set_option(const char* name, int64_t value) {
     g_ln_bwd_rows = value;
     return 0;
   }
+  if (strcmp(name, "train_bwd_stop_layer") == 0) {   // test aid: the training backward stops after this layer's step (-1 = off; gemm_launch.hpp)
+    g_train_bwd_stop_layer = value;
+    return 0;
+  }
   if (strcmp(name, "fused_ln_max_k") == 0) {
     g_fused_ln_max_k = value;
     return 0;

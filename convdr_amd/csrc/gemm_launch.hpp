@@ -86,6 +86,10 @@ inline int64_t g_gelu_gp = 1;
 // convdr_set_option "ln_bwd_rows": LayerNorm backward of the encoder layers (H = 768): 0 = the general kernel, 1 = the straight-line
 // form (k_layernorm_bwd_rows) without, 2 (default) = with the register prefetch of the next row.  Same formulas; rounding-level differences.
 inline int64_t g_ln_bwd_rows = 2;
+// convdr_set_option "train_bwd_stop_layer" (test aid, default -1 = off): with value l >= 0 the backward leaves its layer loop once
+// layer l's step is enqueued (layers below l and the embedding backward are skipped; l >= layers: no layer runs), so that the
+// buffers every layer rewrites (G0 / G1, dXb1, dXb2, dctx) still hold layer l's values (tests/train_stages.py).  Host code only.
+inline int64_t g_train_bwd_stop_layer = -1;
 struct TileCost { double step_us, epi_us; int per_cu; };
 inline double gemm_tile_cost(int64_t tiles, int nk, const TileCost& c) {
   const int64_t slots = (int64_t)device_cu_count() * c.per_cu;

@@ -460,6 +460,42 @@ extern "C" size_t convdr_encoder_train_workspace_bytes(const convdr_encoder_conf
   return P.b.total;
 }
 
+// Test aid: byte offsets of the train_plan regions inside the workspace (-1: the region does not exist in this configuration),
+// in the order documented in include/convdr_hip.h.  Returns the number of entries, -1 if out_len is too small.
+extern "C" int convdr_encoder_train_debug_layout(const convdr_encoder_config* cfg, int64_t rows, int B, int64_t* out, int out_len) {
+  CONVDR_REQUIRE(cfg->layers >= 1 && cfg->layers <= TRAIN_MAX_LAYERS, "convdr_encoder_train_debug_layout: %d layers", cfg->layers);
+  TrainPlan P;
+  train_plan(cfg, rows, B, nullptr, P);   // planned from a null base: every pointer IS its offset (status owns offset 0)
+  const TrainBufs& p = P.b;
+  int n = 0;
+  bool fits = true;
+  auto put = [&](const void* v) {
+    if (n < out_len) out[n] = v ? (int64_t)(uintptr_t)v : -1;
+    else fits = false;
+    ++n;
+  };
+  put(p.tok_id); put(p.tok_pos); put(p.order);
+  for (int l = 0; l < cfg->layers; ++l) {
+    const LayerSave& s = P.layers[l];
+    const void* v[10] = {s.Xin, s.QKV, s.ctx, s.LSE, s.Mbits, s.X1, s.Hpre, s.Hm, s.Y1, s.Y2};
+    for (int i = 0; i < 10; ++i) put(v[i]);
+  }
+  for (int l = 0; l < cfg->layers; ++l) {
+    const LayerBwd& g = P.bwd[l];
+    put(g.dYb); put(g.dHpre); put(g.dYb2); put(g.dQKV);
+  }
+  const void* v[28] = {p.Xout, p.cls_b, p.cls_y, p.cls_f, p.head_y, p.G0, p.G1, p.Drow, p.dcls_y, p.dcls_f, p.dhead_y, p.dhead_yb,
+                       p.dXb1, p.dXb2, p.dctx, p.c_ctx, p.c_xin, p.c_X1, p.c_Hpre, p.c_Hm, p.c_Y1, p.c_ctx32, p.c_dYb, p.c_dHpre,
+                       p.c_dYb2, p.c_dctx, p.c_dX1f, p.c_dY1};
+  for (int i = 0; i < 28; ++i) put(v[i]);
+  if (n < out_len) out[n] = p.ldt; else fits = false;
+  ++n;
+  if (n < out_len) out[n] = p.Tp; else fits = false;
+  ++n;
+  CONVDR_REQUIRE(fits, "convdr_encoder_train_debug_layout: %d entries, room for %d", n, out_len);
+  return n;
+}
+
 extern "C" int convdr_encoder_train_forward(const convdr_encoder_config* cfg, const convdr_encoder_weights* w,
                                             const void* input_ids, int ids_are_int32, const int64_t* attention_mask, int B,
                                             int L, const int32_t* cu_seqlens, const int32_t* seq_lens, int64_t rows,
@@ -682,7 +718,9 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
   const int chunks = colsum_chunks(rows);
   CONVDR_REQUIRE(I % 8 == 0 && H % 8 == 0, "train: hidden / intermediate %% 8 != 0");
   float* other = p.G1;
-  for (int l = NL - 1; l >= 0; --l) {
+  // "train_bwd_stop_layer" (test aid): layers below `stop` and the embedding backward are not enqueued
+  const int64_t stop = g_train_bwd_stop_layer;
+  for (int l = NL - 1; l >= 0 && l >= stop; --l) {
     const convdr_layer_weights* lw = &w->layers[l];
     const convdr_layer_weights_t* lt = &wt[l];
     const convdr_layer_grads* lg = &gr->layers[l];
@@ -848,8 +886,11 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
     if (int e = wf.layer_done(l)) return e;
   }
   wf.layers_recorded = NL;
-  // ---- embeddings ----
-  {
+  if (stop >= 0) {
+    // stopped: the events convdr_backward_wait_layer hands out for the skipped layers are recorded where the chains stand now
+    for (int l = (int)(stop < NL ? stop : NL) - 1; l >= 0; --l)
+      if (int e = wf.layer_done(l)) return e;
+  } else {   // ---- embeddings ----
     const int blocks = (int)(ceil_div64(rows, 4) < EMB_BWD_BLOCKS ? ceil_div64(rows, 4) : EMB_BWD_BLOCKS);
     ProfScope prof("embed_bwd", st);
     if (side_ok) CONVDR_CHECK_HIP(hipStreamWaitEvent(st, wf.head_fin, 0));   // p.part is rewritten here (long complete: first jobs of that stream)

@@ -606,13 +606,29 @@ int convdr_adamw_step_packed(float* p, const float* g, float* m, float* v, int64
  * "ffn2_splitk" = 1 / 0: the K = 3072 projection of at most 5,376 packed rows as 4 / 2 contraction slices + a finishing row
  * kernel / as whole-contraction tiles (default 1; fp32 summation order differs);
  * "ln_rows", "ln_bwd_rows" = straight-line LayerNorm forward (1 / 0) and backward (2 / 1 / 0) kernels for hidden size 768 against
- * the general ones (same formulas, rounding-level differences); "gemm_trace" / "gemm_trace_ln" = device buffer for the s_memtime phase stamps of a
+ * the general ones (same formulas, rounding-level differences); "train_bwd_stop_layer" = test aid, default -1 (off): with value
+ * l >= 0 convdr_encoder_backward[_fresh] enqueues the head and the layers down to and including l (data gradients, parameter
+ * gradients, the layer's events) and skips the layers below and the embedding backward (l >= layers: no layer at all), so the
+ * buffers every layer rewrites still hold layer l's values; the events of convdr_backward_wait_layer and the final join are
+ * recorded as usual; "gemm_trace" / "gemm_trace_ln" = device buffer for the s_memtime phase stamps of a
  * `make TRACE=1` build (tools/gemm_trace*.py; 0 = off). */
 int convdr_set_option(const char* name, int64_t value);
 
 /* Test aid: byte offsets of the activation buffers inside the encoder workspace, in the order tok_id, tok_pos, X, Q, K,
  * Vt, ctx, Hm, Y, cls_b, cls_y, cls_f, head_y; out[13] = leading dimension of Vt. */
 int convdr_encoder_debug_layout(const convdr_encoder_config* cfg, int64_t rows, int B, int64_t* out);
+
+/* Test aid: byte offsets of the regions of the TRAINING workspace (convdr_encoder_train_workspace_bytes), as the training
+ * forward and backward themselves plan them, -1 for a region this configuration does not have.  Order:
+ *   tok_id, tok_pos, order;
+ *   for each layer: Xin, QKV, ctx, LSE, Mbits, X1, Hpre, Hm, Y1, Y2   (X1 .. Y2 = -1 for the last layer under CLS pooling, whose
+ *                   tail lives in the compact c_* regions);
+ *   for each layer: dYb, dHpre, dYb2, dQKV;
+ *   Xout, cls_b, cls_y, cls_f, head_y, G0, G1, Drow, dcls_y, dcls_f, dhead_y, dhead_yb, dXb1, dXb2, dctx,
+ *   c_ctx, c_xin, c_X1, c_Hpre, c_Hm, c_Y1, c_ctx32, c_dYb, c_dHpre, c_dYb2, c_dctx, c_dX1f, c_dY1;
+ *   ldt (row stride of LSE / Mbits / Drow), Tp
+ * = 3 + 14 * layers + 30 entries.  Returns that count, or -1 (convdr_last_error) when out_len is smaller. */
+int convdr_encoder_train_debug_layout(const convdr_encoder_config* cfg, int64_t rows, int B, int64_t* out, int out_len);
 
 /* ------------------------------------------------------------------------------------------
  * Collectives of the N > 1 paths for hosts that are not Python: thin wrappers over RCCL (xGMI).
