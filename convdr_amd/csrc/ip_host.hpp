@@ -47,6 +47,7 @@ struct IpDepth { const char* entry; int min_cap, max_cap; bool top_k; };    // t
 constexpr IpDepth IP_SHALLOW = {"convdr_ip_search", 1024, 8192, true};              // lists and bands in LDS
 constexpr IpDepth IP_DEEP = {"convdr_ip_search_deep", 16384, 131072, true};         // lists in global memory (ip_deep.hpp)
 constexpr IpDepth IP_RANGE = {"convdr_ip_range_search", 1024, 131072, false};       // range search: no k (ip_range.hpp)
+constexpr IpDepth IP_RANK = {"convdr_ip_rank_rows", 1024, 131072, false};           // rank of given rows: no k (ip_rank.hpp)
 
 static int ip_check_sizes(const IpDepth& depth, int nq, int64_t n, int d, int k, int cap) {
   CONVDR_REQUIRE(nq > 0, "%s: bad sizes nq=%d", depth.entry, nq);
@@ -157,12 +158,13 @@ static IpPlan ip_plan(int nq, int64_t n, int d, int cap) {
 // ---- steps every pipeline runs -------------------------------------------------------------------------------------------
 // Queries -> 16-bit operands and norms (fp16: scaled row by row); the kernel also zeroes the padding rows and the hit
 // counters.  qlo: where the remainders go, NULL when the scan has no use for them.
+// counter_sets: how many [nq_pad x IP_COUNT_STRIDE] counter arrays follow each other at o_counts (the rank plan: hits, above).
 static int ip_prepare_queries(const IpBlock& b, const IpPlanHead& p, char* ws, const float* q_f32, int nq, bf16_t* qlo,
-                              hipStream_t st) {
+                              hipStream_t st, int counter_sets = 1) {
   bf16_t* qb = (bf16_t*)(ws + p.o_qb);
   float* qnorm = (float*)(ws + p.o_qnorm);
   uint32_t* counts = (uint32_t*)(ws + p.o_counts);
-  const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE;
+  const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE * counter_sets;
   if (b.kind() == IP_KIND_F16)
     hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, b.d,
                        (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);

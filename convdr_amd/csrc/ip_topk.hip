@@ -25,7 +25,7 @@
 
 namespace convdr {
 
-constexpr int IP_MODE_FULL = 0, IP_MODE_TOP2 = 1, IP_MODE_EMIT = 2;
+constexpr int IP_MODE_FULL = 0, IP_MODE_TOP2 = 1, IP_MODE_EMIT = 2, IP_MODE_BAND = 3;
 constexpr int IP_FULL_MAX_N = 32768;      // <= this many passages: "sample" = all scores, exact rank select
 constexpr int IP_SAMPLE_MIN = 32768;      // sampled passages (>= 1/32 of the block)
 constexpr int IP_SAMPLE_MAX = 262144;
@@ -278,6 +278,8 @@ struct ScanArgs {
   int two_pass;      // half store (fp16 only): S~ = P Qh + P Ql, the passage operand is exact and has no remainder copy
   const uint32_t* bits;  // row filter (FILT kernels only): row r is allowed iff bit r & 31 of word r >> 5 is set; padded with
                          // zero bits to whole TR-row tiles, word 0 = row 0 of P (a sub-block's pointer advances with its P)
+  const float* tau_hi;   // BAND: [nq_pad], tau <= tau_hi: rows with S~ >= tau_hi are counted, not listed (tau is the band's lower end)
+  uint32_t* above;       // BAND: [nq_pad * IP_COUNT_STRIDE], the count of query q at q * IP_COUNT_STRIDE, like counts
 };
 
 // The row filter in the scan epilogues.  A wave's accumulator tile mt covers the 32 rows (wr * MT + mt) * 32 .. + 31 of the
@@ -319,9 +321,77 @@ constexpr uint32_t IP_MASKED_SAMPLE = 0xff800000u;   // -inf
 
 template <int MODE, class T, bool FILT>
 __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc, const WavePos<T>& w, int ts, int64_t m0,
-                                              int64_t n0, const float (&tau_lane)[T::NT], const uint32_t (&fw)[T::MT]) {
-  if constexpr (FILT) filter_acc<T>(acc, fw, w, a.n - m0, MODE == IP_MODE_EMIT ? IP_MASKED_EMIT : IP_MASKED_SAMPLE);
-  if constexpr (MODE == IP_MODE_EMIT) {
+                                              int64_t n0, const float (&tau_lane)[T::NT], const uint32_t (&fw)[T::MT],
+                                              const float (&tau_hi_lane)[T::NT]) {   // (tau_hi_lane: BAND only)
+  constexpr bool LISTS = MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND;
+  if constexpr (FILT) filter_acc<T>(acc, fw, w, a.n - m0, LISTS ? IP_MASKED_EMIT : IP_MASKED_SAMPLE);
+  if constexpr (MODE == IP_MODE_BAND) {
+    // Two thresholds per query column, tau <= tau_hi.  S~ >= tau_hi: the row is COUNTED into the query's "above" counter and
+    // nothing else -- no slot, no id.  tau <= S~ < tau_hi: the row is listed exactly as EMIT lists it (one returning atomic per
+    // lane reserves the slots, the hits are written once it has retired, the hit counter counts past cap).  A masked score is
+    // NaN and fails both compares; the rows past n of the last tile score -inf, and tau is never below -FLT_MAX.
+    // How the above count leaves the registers: lanes l and l + 32 hold the same query column (the two halves of the 32 rows
+    // of an accumulator tile), so the pair is folded in registers first (a cross-lane move: no LDS is allocated, the R3 main
+    // loop owns all of it); then lanes 0..31 issue ONE non-returning 32-bit add per query tile into the query's counter, which
+    // has a 128-byte line of its own.  Integer sums do not depend on the order of arrival: the count is the same in every run.
+    const int rows_left = (int)(a.n - m0 < (int64_t)T::TR ? a.n - m0 : (int64_t)T::TR);
+    if (!FILT && rows_left < T::TR) {
+#pragma unroll
+      for (int nt = 0; nt < T::NT; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (w.r_index(mt, r) >= rows_left) acc.c[mt][nt][r] = -INFINITY;
+    }
+    uint32_t cnt[T::NT], slot[T::NT];
+#pragma unroll
+    for (int nt = 0; nt < T::NT; ++nt) {
+      uint32_t c = 0, ca = 0;
+#pragma unroll
+      for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          c += acc.c[mt][nt][r] >= tau_lane[nt] ? 1u : 0u;
+          ca += acc.c[mt][nt][r] >= tau_hi_lane[nt] ? 1u : 0u;
+        }
+      cnt[nt] = c - ca;          // (tau <= tau_hi: every row counted above also passed tau)
+      const uint32_t pair = ca + (uint32_t)__shfl_xor((int)ca, 32, 64);
+      const int q = (int)n0 + w.l_index(nt);
+      if (w.hi == 0 && pair) __hip_atomic_fetch_add(&a.above[(int64_t)q * IP_COUNT_STRIDE], pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int nt = 0; nt < T::NT; ++nt) {
+      const int q = (int)n0 + w.l_index(nt);
+      slot[nt] = cnt[nt] ? atomicAdd(&a.counts[(int64_t)q * IP_COUNT_STRIDE], cnt[nt]) : 0u;
+    }
+#pragma unroll
+    for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(slot[nt]));   // hipcc: the reservations retire HERE, once (see EMIT)
+#pragma unroll
+    for (int nt = 0; nt < T::NT; ++nt) {
+      if (cnt[nt] == 0) continue;
+      const int q = (int)n0 + w.l_index(nt);
+      const float tau = tau_lane[nt], tau_hi = tau_hi_lane[nt];
+      uint32_t* ids = a.cand_id + (int64_t)q * a.cap;
+      float* sc = a.cand_s + (int64_t)q * a.cap;
+      uint32_t sl = slot[nt];
+      const uint32_t row0 = (uint32_t)m0;
+#pragma unroll
+      for (int mt = 0; mt < T::MT; ++mt) {
+        const f32x16 v = acc.c[mt][nt];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          if (v[r] >= tau && !(v[r] >= tau_hi)) {
+            if (sl < (uint32_t)a.cap) {
+              ids[sl] = row0 + (uint32_t)w.r_index(mt, r);
+              sc[sl] = v[r];
+            }
+            ++sl;
+          }
+        }
+      }
+    }
+  } else if constexpr (MODE == IP_MODE_EMIT) {
     // A lane owns one query per 32-column tile and MT*16 of the tile's passages.  It counts its hits, reserves that
     // many slots of the query's candidate list with ONE atomic (a device-scope returning atomic is a ~1-2 us round
     // trip to the memory side; one per hit -- ~100 per tile, serialised by the branches around them -- was 30 % of
@@ -426,6 +496,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 // instruction for instruction the kernels they were before the filter existed.
 template <int MODE, class T, int PASSES, bool F16, bool FILT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
+  static_assert(MODE != IP_MODE_BAND, "the band-count scan is single pass: k_ip_scan_r3<..., IP_MODE_BAND>");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t ntiles = (uint32_t)a.nPt * (uint32_t)a.nQt;
   const uint32_t xcd = blockIdx.x & 7u, q8 = ntiles >> 3, r8 = ntiles & 7u;
@@ -512,7 +583,7 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));   // opaque: the epilogue's lane-dependent addresses stay out of the main loop's registers
     const WavePos<T> we(tid_e);
-    scan_epilogue<MODE, T, FILT>(a, acc, we, ts_cur, m0_cur, n0_cur, tau_lane, fw);
+    scan_epilogue<MODE, T, FILT>(a, acc, we, ts_cur, m0_cur, n0_cur, tau_lane, fw, tau_lane);
     if (!has_next) break;
     idx = next;
     buf = idle;
@@ -633,8 +704,13 @@ __device__ __forceinline__ void scan_emit_flush(const ScanArgs& a, const WavePos
 // The emitting scan of 256 x 256 tiles on the 3 R-slot / 2 L-slot main loop (gemm_nt_mainloop_r3); same persistent walk,
 // next-tile prologue under the epilogue and one-tile-ahead thresholds as k_ip_scan.  (The split-bf16 scan and the
 // sampling modes stay on the two-stage loop.)
-template <class T, bool F16, bool FILT>
+// MODE: IP_MODE_EMIT (the default: every caller before the band-count scan), or IP_MODE_BAND -- the same walk with
+// scan_epilogue<IP_MODE_BAND> in the place of capture / flush: the band's slots are reserved and waited for in the epilogue
+// (the list holds the few rows in doubt; the rows above are counted, not listed), and tau_hi travels with tau.
+template <class T, bool F16, bool FILT, int MODE = IP_MODE_EMIT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) {
+  static_assert(MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND, "the R3 scan lists: EMIT or BAND");
+  constexpr bool BAND = MODE == IP_MODE_BAND;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // the 256 x 128 tile serves scans with ONE query tile (at most 128 queries): every passage chunk is read exactly once,
   // so its DMA is non-temporal -- the block streams past L2 instead of through it
@@ -661,11 +737,13 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
   R3Slots slots{0, 0};
   gemm_r3_prologue<T, P_AUX>(src, a.d, smem, w, slots);
   float tau_next[T::NT];
+  float tau_hi_next[BAND ? T::NT : 1] = {};   // BAND: the upper thresholds, one tile ahead like tau
   auto load_tau = [&](int64_t n0_) {
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) {
       const int q = (int)n0_ + w.l_index(nt);
       tau_next[nt] = q < a.nq ? a.tau[q] : INFINITY;
+      if constexpr (BAND) tau_hi_next[nt] = q < a.nq ? a.tau_hi[q] : INFINITY;
     }
   };
   load_tau(n0);
@@ -679,19 +757,28 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
   };
   load_bits(m0);
   EmitPending<T> pend;
-  pend.clear();
+  if constexpr (!BAND) pend.clear();
   for (;;) {
     GemmAcc<T> acc;
     acc.zero();
     float tau_lane[T::NT];
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) tau_lane[nt] = tau_next[nt];
+    float tau_hi_lane[T::NT] = {};
+    if constexpr (BAND) {
+#pragma unroll
+      for (int nt = 0; nt < T::NT; ++nt) tau_hi_lane[nt] = tau_hi_next[nt];
+    }
     uint32_t fw[T::MT];
 #pragma unroll
     for (int mt = 0; mt < T::MT; ++mt) fw[mt] = fw_next[mt];
     slots = gemm_nt_mainloop_r3<T, F16, P_AUX>(src, a.d, smem, acc, w, slots, true, false, a.dbg_prelanded != 0);
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_lane[nt]));
+    if constexpr (BAND) {
+#pragma unroll
+      for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_hi_lane[nt]));
+    }
     if constexpr (FILT) {
 #pragma unroll
       for (int mt = 0; mt < T::MT; ++mt) asm volatile("" : "+v"(fw[mt]));
@@ -699,7 +786,7 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));
     const WavePos<T> we(tid_e);
-    scan_emit_flush<T>(a, we, pend);   // the previous tile's hits: their reservations came back under this main loop
+    if constexpr (!BAND) scan_emit_flush<T>(a, we, pend);   // the previous tile's hits: their reservations came back under this main loop
     const uint32_t next = idx + stride;
     const bool has_next = next < chunk_len;
     const int64_t m0_cur = m0, n0_cur = n0;
@@ -710,11 +797,12 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
       src = TileSrcAll<T>(a.P, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
       gemm_r3_prologue<T, P_AUX>(src, a.d, smem, w, slots);
     }
-    scan_emit_capture<T, FILT>(a, acc, we, m0_cur, n0_cur, tau_lane, pend, fw);
+    if constexpr (BAND) scan_epilogue<IP_MODE_BAND, T, FILT>(a, acc, we, 0, m0_cur, n0_cur, tau_lane, fw, tau_hi_lane);
+    else scan_emit_capture<T, FILT>(a, acc, we, m0_cur, n0_cur, tau_lane, pend, fw);
     if (!has_next) break;
     idx = next;
   }
-  scan_emit_flush<T>(a, w, pend);
+  if constexpr (!BAND) scan_emit_flush<T>(a, w, pend);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1218,6 +1306,32 @@ static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) { 
   return a.bits ? launch_scan_f<MODE, true>(a, tile, kind, st) : launch_scan_f<MODE, false>(a, tile, kind, st);
 }
 
+// The band-count scan (IP_MODE_BAND): the single-pass shapes of launch_scan<IP_MODE_EMIT> -- both tiles, both kinds (the half
+// store scans with the fp16 kernels), with and without the row filter -- on the R3 kernel.  There is no split BAND scan.
+template <class T, bool F16, bool FILT>
+static int launch_band_x(const ScanArgs& a, hipStream_t st) {
+  constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
+  static DeviceOnce attr3;
+  if (attr3.first())
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16, FILT, IP_MODE_BAND>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         R3_SMEM));
+  const unsigned tiles = (unsigned)a.nPt * (unsigned)a.nQt;
+  ProfScope prof("ip_scan_band", st);
+  hipLaunchKernelGGL((k_ip_scan_r3<T, F16, FILT, IP_MODE_BAND>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS),
+                     R3_SMEM, st, a);
+  CONVDR_CHECK_LAUNCH("k_ip_scan_r3<BAND>");
+  return 0;
+}
+template <bool F16, bool FILT>
+static int launch_band_k(const ScanArgs& a, int tile, hipStream_t st) {
+  return tile == IP_TILE_256 ? launch_band_x<Tile256, F16, FILT>(a, st) : launch_band_x<TileTall, F16, FILT>(a, st);
+}
+static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t st) {   // a.bits selects the filtered kernels
+  CONVDR_REQUIRE(!a.two_pass && !a.Plo && a.tau_hi && a.above, "band scan: one pass, tau_hi and above set");
+  if (kind == IP_KIND_F16) return a.bits ? launch_band_k<true, true>(a, tile, st) : launch_band_k<true, false>(a, tile, st);
+  return a.bits ? launch_band_k<false, true>(a, tile, st) : launch_band_k<false, false>(a, tile, st);
+}
+
 }  // namespace convdr
 
 // the host side: block descriptor, argument checks, plan head, shared steps and the shallow pipeline (k <= 4096)
@@ -1226,6 +1340,8 @@ static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) { 
 #include "ip_deep.hpp"
 // range search: every row scoring above a per-query radius (convdr_ip_range_*)
 #include "ip_range.hpp"
+// rank and score of given rows: the band-count scan (convdr_ip_score_rows, convdr_ip_rank_*)
+#include "ip_rank.hpp"
 
 using namespace convdr;
 

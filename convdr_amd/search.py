@@ -1190,6 +1190,172 @@ class FlatIPIndex:
             Dout[dest], Iout[dest] = D, I
         return lims, Dout, Iout
 
+    # -- score and rank of given rows: where does a known row stand, and what does it score? -------------------------
+    def score_rows(self, q, rows):
+        """Canonical score of given rows (FAISS ``compute_distance_subset``): rows int64 [nq] (one row per query) or [nq, m],
+        -1 = padding; float32 numpy of the same shape, the fp32 rounding of the canonical fp64 score that ``search`` ranks by
+        (``search(q, k)`` followed by ``score_rows(q, I)`` reproduces D bit for bit), padding -> -3.4028235e38.  numpy (or
+        host tensor) ids >= ntotal raise ValueError; ids in a device tensor are not read on the host: outside [0, ntotal)
+        they score as padding."""
+        return self.score_rows_tensors(q, rows)[0].cpu().numpy()
+
+    def score_rows_tensors(self, q, rows):
+        """``score_rows`` on the device: (D float32, X float64), both of the shape of `rows`; X is the canonical score itself."""
+        import torch
+        qt, rt, shape = self._rows_arg("score_rows", q, rows)
+        nq, m = int(rt.shape[0]), int(rt.shape[1])
+        D = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+        X = torch.empty((nq, m), dtype=torch.float64, device=self.device)
+        if nq and m:
+            store = 2 if self._half else (1 if self.kind == "f16" else 0)
+            n = self.ntotal
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().convdr_ip_score_rows(
+                    store, _lib.ptr(qt), nq, None if (self._half or not n) else _lib.ptr(self._rows), _lib.ptr(self._pbf) if n else None,
+                    float(self._scale) if store else 1.0, n, self.d, _lib.ptr(rt), m, m, _lib.ptr(X), _lib.ptr(D), _lib.stream_ptr()),
+                    "convdr_ip_score_rows")
+        return D.reshape(shape), X.reshape(shape)
+
+    def rank_rows(self, q, rows, allowed=None):
+        """Exact rank of given rows: rows int64 [nq] or [nq, m], -1 = padding; int64 numpy of the same shape: the number of rows
+        of the index (with ``allowed``: of the allowed rows) that precede the given row in the canonical order of ``search`` --
+        canonical fp64 score descending, row ascending --, 0-based, -1 for padding.  ``search(q, k)[1][j, rank] == row``
+        whenever rank < k.  The row itself need not be allowed: with the known positives masked out this is "the rank among
+        the rows that are not known positives".  Exact at any depth, whatever the store and the precision; exact ties (duplicate
+        rows) are ordered by row, as ``search`` orders them.  ids are checked as for ``score_rows``."""
+        return self.rank_rows_tensors(q, rows, allowed=allowed).cpu().numpy()
+
+    def rank_rows_tensors(self, q, rows, allowed=None):
+        """``rank_rows`` with the result left on the device (int64, the shape of `rows`).
+
+        Every (query, row) pair becomes one query of convdr_ip_rank_rows (include/convdr_hip.h, "Score and rank of given
+        rows"): one scan counts the rows that certainly precede the target and lists only those within the scan's error band
+        of its score, which are re-scored exactly.  The host loop reads ONE tensor per pass: the first pass runs at
+        ``self.cap``; a pair whose band overflowed is re-run once at the smallest power of two that holds the reported band
+        count, up to RANGE_MAX_CAP; CONVDR_IP_RANGE rebuilds the scan copy once (as search_finish).  A pair whose band holds
+        more than RANGE_MAX_CAP rows -- more duplicates or near-duplicates of the target than that -- takes the fallback: a
+        ``range_search`` just below the target's score (which has its own row-slice rung) and the canonical fp64 scores of
+        the rows it returns, compared on the device.  Correct, not fast.
+        ``stats``: rank_rounds (passes), rank_cap (the longest band list used), rank_band_rows (band entries re-scored, all
+        passes), rank_above (rows counted without a re-score, final passes), rank_fallback_pairs, rescaled."""
+        import torch
+        qt, rt, shape = self._rows_arg("rank_rows", q, rows)
+        f = self._filter(allowed)
+        nq, m = int(rt.shape[0]), int(rt.shape[1])
+        npairs = nq * m
+        self.stats = {"rank_rounds": 0, "rank_cap": 0, "rank_band_rows": 0, "rank_above": 0, "rank_fallback_pairs": 0, "rescaled": 0}
+        out = torch.full((npairs,), -1, dtype=torch.int64, device=self.device)
+        if not npairs or not self.ntotal:
+            return out.reshape(shape)
+        qp = qt if m == 1 else qt.repeat_interleave(m, dim=0)
+        tp = rt.reshape(-1).contiguous()
+        X = torch.empty(npairs, dtype=torch.float64, device=self.device)
+        cap_max = int(self.RANGE_MAX_CAP)
+        groups = [(np.arange(npairs), min(int(self.cap), cap_max))]
+        fallback = []
+        while groups:
+            idx, cap = groups.pop(0)
+            whole = len(idx) == npairs
+            sub = None if whole else torch.as_tensor(idx, device=self.device)
+            rank, cnt, above, st, Xs = self._rank_pass(qp if whole else qp[sub].contiguous(), tp if whole else tp[sub].contiguous(), cap, f)
+            self.stats["rank_rounds"] += 1
+            self.stats["rank_cap"] = max(self.stats["rank_cap"], cap)
+            if (st == STATUS_RANGE).any():
+                if self.kind != "f16" or self.stats["rescaled"]:
+                    raise _lib.ConvdrError("convdr_ip_rank_rows: CONVDR_IP_RANGE %s" % ("after the scan copy was rebuilt"
+                                           if self.stats["rescaled"] else "from a bf16 scan"))
+                self._rebuild_scaled()
+                self.stats["rescaled"] = 1
+                groups.insert(0, (idx, cap))
+                continue
+            ok, over = st == STATUS_OK, st == STATUS_OVERFLOW
+            if not (ok | over).all() or self.stats["rank_rounds"] > 64:
+                raise _lib.ConvdrError("convdr_ip_rank_rows: unexpected status %s" % (st,))
+            self.stats["rank_band_rows"] += int(np.minimum(cnt, cap).sum())
+            self.stats["rank_above"] += int(above[ok].sum())
+            if whole:
+                out, X = torch.as_tensor(rank, device=self.device), Xs
+            else:
+                out[sub], X[sub] = torch.as_tensor(rank, device=self.device), Xs
+            # the reported band count is exact and the thresholds do not change: the list that holds it cannot overflow
+            need = np.asarray([1 << int(c - 1).bit_length() for c in cnt[over]], dtype=np.int64)
+            fallback += list(idx[over][need > cap_max])
+            for c in sorted(set(need[need <= cap_max].tolist())):
+                groups.append((idx[over][need == c], int(c)))
+        if fallback:
+            stats = self.stats
+            stats["rank_fallback_pairs"] = len(fallback)
+            xs = X[torch.as_tensor(np.asarray(fallback, dtype=np.int64), device=self.device)].cpu().numpy()
+            for j, x in zip(fallback, xs):
+                t = tp[j]
+                r = np.float32(x)               # the largest fp32 strictly below the target's score: every row that ties
+                if not np.float64(r) < x:       # with it, or beats it, exceeds this radius
+                    r = np.nextafter(r, np.float32(-np.inf))
+                qj = qp[j:j + 1].contiguous()
+                _, _, I = self.range_search_tensors(qj, r, allowed=f)
+                Xr = self.score_rows_tensors(qj, I[None, :])[1][0]
+                out[j] = ((Xr > float(x)) | ((Xr == float(x)) & (I < t))).sum()
+            self.stats = stats
+        return out.reshape(shape)
+
+    def _rows_arg(self, who, q, rows):
+        """(queries device fp32 [nq, d], rows device int64 [nq, m], the shape of `rows`); the checks that need no device"""
+        import torch
+        qt = torch.as_tensor(q)
+        if qt.dtype != torch.float32:
+            qt = qt.float()
+        if qt.dim() != 2 or qt.shape[1] not in (self.d, self.d_in):
+            raise ValueError("%s: queries must be [nq, %d] (got shape %s)" % (who, self.d_in, tuple(qt.shape)))
+        nq = int(qt.shape[0])
+        rt = torch.as_tensor(rows)
+        if rt.dim() not in (1, 2) or int(rt.shape[0]) != nq:
+            raise ValueError("%s: rows must be [nq] or [nq, m] with nq = %d (got shape %s)" % (who, nq, tuple(rt.shape)))
+        if rt.is_floating_point() or rt.dtype == torch.bool:
+            raise ValueError("%s: rows must be integers (got %s)" % (who, rt.dtype))
+        shape = tuple(rt.shape)
+        if rt.device.type == "cpu" and rt.numel() and int(rt.max()) >= self.ntotal:
+            raise ValueError("%s: row id %d >= ntotal = %d" % (who, int(rt.max()), self.ntotal))
+        qt = (self._pad_columns(qt) if qt.shape[1] != self.d else qt.to(self.device)).contiguous()
+        rt = rt.to(torch.int64).to(self.device).reshape(nq, -1).contiguous()
+        return qt, rt, shape
+
+    def _rank_step(self, npairs, n, cap):
+        """pairs per call, so that one call's workspace stays under DEEP_WS_BYTES (as _range_step)"""
+        ws_bytes = _lib.lib().convdr_ip_rank_workspace_bytes
+        step = npairs
+        while step > 1 and ws_bytes(step, n, self.d, cap) > self.DEEP_WS_BYTES:
+            step = (step + 1) // 2
+        if not ws_bytes(step, n, self.d, cap):
+            raise _lib.ConvdrError("convdr_ip_rank_rows: sizes outside the contract (np=%d n=%d d=%d cap=%d)" % (npairs, n, self.d, cap))
+        return step
+
+    def _rank_pass(self, qp, tp, cap, allowed=None):
+        """One pass of convdr_ip_rank_rows over the resident block: (rank, band counts, above, status) numpy [np] and the
+        targets' fp64 scores (device).  One host read per call."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        npairs, n = int(qp.shape[0]), self.ntotal
+        store = 2 if self._half else (1 if self.kind == "f16" else 0)
+        step = self._rank_step(npairs, n, cap)
+        ws = self._workspace(L.convdr_ip_rank_workspace_bytes(step, n, self.d, cap))
+        bits = None if allowed is None else allowed.bits
+        X = torch.empty(npairs, dtype=torch.float64, device=self.device)
+        hosts = []
+        with torch.cuda.device(self.device):
+            for a in range(0, npairs, step):
+                b = min(npairs, a + step)
+                c = b - a
+                out = torch.empty(4 * c, dtype=torch.int64, device=self.device)      # rank | counts | above | status (int32)
+                _lib.check(L.convdr_ip_rank_rows(
+                    store, ptr(qp[a:b]), c, ptr(tp[a:b]), None if self._half else ptr(self._rows), ptr(self._pbf),
+                    float(self._scale) if store else 1.0, None if self._half else ptr(self._centre), n, self.d, ptr(self._max_norm),
+                    ptr(bits), 0 if bits is None else bits.numel(), 0 if allowed is None else allowed.n_allowed, cap, ptr(ws),
+                    ws.numel(), ptr(out[:c]), ptr(X[a:b]), ptr(out[c:2 * c]), ptr(out[2 * c:3 * c]), ptr(out[3 * c:]),
+                    _lib.stream_ptr()), "convdr_ip_rank_rows")
+                host = out.cpu().numpy()                                             # the pass's one host read
+                hosts.append((host[:c], host[c:2 * c], host[2 * c:3 * c], host[3 * c:].view(np.int32)[:c]))
+        return tuple(np.concatenate([h[i] for h in hosts]) for i in range(4)) + (X,)
+
 
 # Pinned staging buffers and the copy thread pool are process-wide: pinning 64 MB costs ~20 ms (hipHostMalloc), i.e. a
 # fresh set per index would cost as much as loading a 3 GB block through them.

@@ -250,6 +250,50 @@ int convdr_ip_range_search(int store, const float* q_f32, int nq, const float* p
 int convdr_ip_range_pack(const void* workspace, int nq, int64_t n, int d, int cap, const int64_t* lims, float* D, int64_t* I,
                          double* X, convdr_stream_t stream);
 
+/* Score and rank of given rows: where does a KNOWN row stand, and what does it score?  (FAISS: compute_distance_subset; the
+ * rank has no FAISS counterpart.)  X is the canonical fp64 score of the search entries throughout.
+ *
+ * convdr_ip_score_rows: X[q, j] = the canonical score of query q and row rows[q, j], j < m; rows, X and D share the pitch ld
+ * (>= m).  The fp32 block is re-scored for store 0 / 1 (p_half is not read), the stored halves for store 2 (p_f32 is not read;
+ * the sum over the resident 2^s v is multiplied by 2^-s once, exactly).  D is X rounded to fp32.  Either output may be NULL.
+ * An id outside [0, n) -- the -1 that pads a result list -- is never dereferenced and yields the score FAISS pads with,
+ * -3.4028235e38.  No workspace, no centre, no scan.  nq, m >= 0, 0 <= n < 2^31, d % 64 == 0, d <= 4096.
+ *
+ * convdr_ip_rank_rows: one target row per query row (the caller expands (query, target) pairs: np pairs, q_f32 [np, d]).
+ *   result       rank[p] = the number of rows r of the block (with a bitmap: of the ALLOWED rows) that precede the target t in
+ *                the canonical order of the search entries: X_r > X_t, or X_r == X_t and r < t.  0-based: when rank < k,
+ *                row rank of the top-k of the same query is t.  The target need not be allowed itself ("rank among the rows
+ *                that are not known positives").  X[p] = X_t.  A target outside [0, n): rank -1, X the padding score,
+ *                counts = above = 0, status OK, and no scan work for that column.
+ *   thresholds   from X_t, two per query: tau_lo with every rounding pushed DOWN, so that X_r >= X_t implies S~(r) >= tau_lo,
+ *                and tau_hi with every rounding pushed UP, so that S~(r) >= tau_hi implies X_r > X_t strictly (proofs beside
+ *                k_ip_band_tau; the error terms and eps are those of the range search).  One single-pass scan then COUNTS the
+ *                rows with S~ >= tau_hi (above[p]: they certainly precede t) and LISTS the rows with tau_lo <= S~ < tau_hi
+ *                (the band: at most 2 eps of scan score wide); only the band is re-scored canonically, and
+ *                rank = above + #{band rows that precede t}.  The cost follows the band, not the rank.
+ *   status       CONVDR_IP_OK: rank[p] is exact.  CONVDR_IP_OVERFLOW: the band holds more than cap rows; counts[p] = the
+ *                scan's exact band count: re-run with cap >= counts[p] -- the thresholds are the same, it cannot overflow
+ *                again.  CONVDR_IP_RANGE: as for range search, or an intermediate of the thresholds was not finite.  A pair
+ *                that is not OK has rank -1.  counts[p] is the band count and above[p] the counted rows for every status.
+ *   cap          a power of two in [1024, 131072]: entries of a pair's band list (global memory).
+ *   bitmap       row_bits / row_bits_words: the contract of convdr_ip_search_filtered (NULL, 0: no filter); n_allowed: set bits
+ *                among rows 0..n-1, read only with a bitmap -- 0 skips the scan (every rank is 0).
+ *   workspace    convdr_ip_rank_workspace_bytes(np, n, d, cap) bytes (0 outside the contract: convdr_last_error says why),
+ *                256-byte aligned regions in this order: query operands [nq_pad, d] x 2 | query norms [nq_pad] | tau_lo
+ *                [nq_pad] | tau_hi [nq_pad] | band hit counters [nq_pad x 32] | above counters [nq_pad x 32] | min(hits, cap)
+ *                [nq_pad] | threshold flags [nq_pad] | band ids [np, cap] u32 | band scan scores [np, cap] f32 | band
+ *                canonical scores [np, cap] f64 -- 16 bytes per list entry.  Nothing of it is read before this call wrote it.
+ * np > 0, 0 <= n < 2^31, d % 64 == 0, d <= 4096; store, p_scale and centre as for convdr_ip_range_search.  Every output (rank,
+ * X, counts, above int64 / fp64 [np], status int32 [np]) must be given.  Arguments are validated before anything touches a
+ * device; no allocation, no sync. */
+int convdr_ip_score_rows(int store, const float* q_f32, int nq, const float* p_f32, const void* p_half, float p_scale, int64_t n,
+                         int d, const int64_t* rows, int m, int64_t ld, double* X, float* D, convdr_stream_t stream);
+size_t convdr_ip_rank_workspace_bytes(int np, int64_t n, int d, int cap);
+int convdr_ip_rank_rows(int store, const float* q_f32, int np, const int64_t* target, const float* p_f32, const void* p_half,
+                        float p_scale, const float* centre, int64_t n, int d, const float* p_max_norm, const uint32_t* row_bits,
+                        int64_t row_bits_words, int64_t n_allowed, int cap, void* workspace, size_t workspace_bytes,
+                        int64_t* rank, double* X, int64_t* counts, int64_t* above, int32_t* status, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
