@@ -1342,6 +1342,8 @@ static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t s
 #include "ip_range.hpp"
 // rank and score of given rows: the band-count scan (convdr_ip_score_rows, convdr_ip_rank_*)
 #include "ip_rank.hpp"
+// removing rows: stable in-place compaction of the resident buffers (convdr_ip_compact_*)
+#include "ip_compact.hpp"
 
 using namespace convdr;
 

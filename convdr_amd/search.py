@@ -132,6 +132,9 @@ class FlatIPIndex:
         self.host_copy_threads = 16            # file reads / memcpy slices in flight while filling a staging buffer
         self.host_stage_buffers = 4            # pinned staging buffers (3 chunks being read while one crosses PCIe; 37-41 GB/s of a
                                                # 44 GB/s pinned-H2D ceiling on the r03 box, tools/dbg/block_load_sweep.py)
+        self.compact_window_rows = 65536       # rows per window of keep_rows / remove_rows (a multiple of 256): the bounce buffer
+                                               # holds one window of the widest buffer, 192 MB at d = 768; best of the sweep
+                                               # 1,024 .. 262,144 at 1 M rows (profiles/compact_rows_time.txt)
         self.stats = {}
         self._s32 = self._s16 = self._slo = None
         self.reset()
@@ -568,6 +571,128 @@ class FlatIPIndex:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._ws
+
+    # -- removing rows (FAISS remove_ids) and reading rows back (reconstruct) -------------------------------------------
+    def keep_rows(self, allowed):
+        """Compact the index to the allowed rows, IN PLACE: `allowed` is a RowFilter of this index or a bool / uint8 mask
+        [ntotal] (non-zero = keep; a stale filter raises ValueError, as in search).  Returns the number of rows removed.
+
+        The kept rows move to the front of every resident buffer (fp32 block, scan copy, remainder copy; the half store: its
+        one buffer) in their old order, bit for bit: row r becomes row #{kept rows before r}, so ``search`` afterwards equals
+        ``search(..., allowed=keep)`` before, with the ids renumbered by ``cumsum(keep) - 1``.  No buffer is copied: the device
+        works through windows of ``compact_window_rows`` rows (convdr_ip_compact_*, include/convdr_hip.h "Removing rows") and
+        the extra memory is one window of the widest buffer.  ntotal becomes the filter's ``n_allowed``, which is already on
+        the host: nothing is read back, the whole removal is enqueued.
+
+        What stays: the centre and the scale (any centre keeps the search exact, and the scale still fits); ``_max_norm``,
+        which remains an UPPER bound of the kept rows' norms -- all the certificate needs, so it is not recomputed; a
+        reservation and the backing storage, which is not shrunk: the next ``add`` fills rows [ntotal, ...).
+        What the caller does: filters built for the old ntotal are stale (unless nothing was removed); side tables
+        (offset2pid[embid], the keys of search_distinct) are cut with the same mask, ``keys[keep]``; a first block adopted from
+        the caller's device tensor is modified in place, as by update_rows; a search_begin handle is finished first.
+        ``stats``: removed, compact_windows (windows per buffer)."""
+        f = self._filter(allowed)
+        if f is None:
+            raise ValueError("keep_rows: a RowFilter or a mask of ntotal = %d entries is needed (got None)" % self.ntotal)
+        n, w = self.ntotal, int(self.compact_window_rows)
+        if w < ROW_FILTER_TILE or w % ROW_FILTER_TILE:
+            raise ValueError("keep_rows: compact_window_rows must be a positive multiple of %d (got %d)" % (ROW_FILTER_TILE, w))
+        removed = n - f.n_allowed
+        self.stats = {"removed": removed, "compact_windows": 0}
+        if removed:
+            self._compact(f, w)
+            self._n = f.n_allowed
+            self.stats["compact_windows"] = (n + w - 1) // w
+        return removed
+
+    def remove_rows(self, rows):
+        """FAISS ``remove_ids``: `rows` is an int64 id vector (numpy or torch, host or device; duplicates allowed) or a bool /
+        uint8 mask [ntotal] (non-zero = remove).  An id outside [0, ntotal) raises ValueError and leaves the index as it was.
+        The keep mask is built on the device and handed to ``keep_rows`` (one host read: the kept count and the range check
+        together).  Returns the number of rows removed."""
+        import torch
+        n = self.ntotal
+        t = torch.as_tensor(rows)
+        if t.dtype in (torch.bool, torch.uint8):
+            if t.dim() != 1 or int(t.numel()) != n:
+                raise ValueError("remove_rows: the mask must be a vector of ntotal = %d entries (got shape %s)" % (n, tuple(t.shape)))
+            return self.keep_rows(t.to(self.device) == 0)
+        if t.is_floating_point() or t.is_complex() or t.dim() != 1:
+            raise ValueError("remove_rows: rows must be an integer id vector or a bool / uint8 mask (got %s, shape %s)"
+                             % (t.dtype, tuple(t.shape)))
+        if not t.numel():
+            self.stats = {"removed": 0, "compact_windows": 0}
+            return 0
+        if t.device.type == "cpu" and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError("remove_rows: row ids %d..%d outside [0, ntotal = %d)" % (int(t.min()), int(t.max()), n))
+        if n == 0:
+            raise ValueError("remove_rows: the index is empty, no id is inside [0, ntotal = 0)")
+        t = t.to(torch.int64).to(self.device)
+        keep = torch.ones(n, dtype=torch.bool, device=self.device)
+        keep[t.clamp(0, n - 1)] = False                    # (a scratch mask: the index is untouched until the ids are known good)
+        counts = torch.stack([keep.sum(), ((t < 0) | (t >= n)).sum()]).cpu()
+        if int(counts[1]):
+            raise ValueError("remove_rows: %d row ids outside [0, ntotal = %d)" % (int(counts[1]), n))
+        return self.keep_rows(RowFilter(pack_row_mask(keep), n, int(counts[0])))
+
+    def _compact(self, f, window_rows):
+        """convdr_ip_compact_plan once, convdr_ip_compact_rows per resident buffer; no host read.  The plan's device scalar
+        stays in ``_n_kept`` (int64 [1])."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        # (a block shorter than the window is one window either way: the bounce buffer need not be larger than the block)
+        window_rows = min(int(window_rows), (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * ROW_FILTER_TILE)
+        bufs = [t for t in (self._s32, self._s16, self._slo) if t is not None]
+        widest = max(int(t.shape[1]) * t.element_size() for t in bufs)
+        need = L.convdr_ip_compact_workspace_bytes(n, widest, window_rows)
+        if not need:
+            raise _lib.ConvdrError("convdr_ip_compact_rows: sizes outside the contract: %s" % L.convdr_last_error().decode())
+        ws = self._workspace(need)
+        words = int(f.bits.numel())
+        with torch.cuda.device(self.device):
+            self._n_kept = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_ip_compact_plan(ptr(f.bits), words, n, ptr(ws), ws.numel(), ptr(self._n_kept), _lib.stream_ptr()),
+                       "convdr_ip_compact_plan")
+            for t in bufs:
+                _lib.check(L.convdr_ip_compact_rows(ptr(t), int(t.shape[1]) * t.element_size(), n, ptr(f.bits), words, window_rows,
+                                                    ptr(ws), ws.numel(), _lib.stream_ptr()), "convdr_ip_compact_rows")
+
+    def rows_tensors(self, ids):
+        """The corpus rows `ids` (integers, any shape [..]) as a device fp32 tensor [.., d_in]: the fp32 store returns the fp32
+        block's rows bit for bit, the half store its stored halves un-scaled and widened (exact); the zero columns of a
+        padded width are cut off.  An id outside [0, ntotal) raises IndexError (ids in a device tensor cost one host read)."""
+        import torch
+        t = torch.as_tensor(ids)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise IndexError("reconstruct: row ids must be integers (got %s)" % t.dtype)
+        t = t.to(torch.int64)
+        if t.numel():
+            lo, hi = (int(v) for v in torch.stack([t.min(), t.max()]).cpu())
+            if lo < 0 or hi >= self.ntotal:
+                raise IndexError("reconstruct: row ids %d..%d outside [0, ntotal = %d)" % (lo, hi, self.ntotal))
+        t = t.to(self.device)
+        if self._rows is None:
+            return torch.empty(tuple(t.shape) + (self.d_in,), dtype=torch.float32, device=self.device)
+        r = self._rows[t.reshape(-1)][:, :self.d_in]
+        if self._half:
+            r = r.float() * (1.0 / float(self._scale))     # (a power of two: exact)
+        return r.reshape(tuple(t.shape) + (self.d_in,)).contiguous()
+
+    def reconstruct(self, i):
+        """FAISS ``reconstruct``: row i as float32 numpy [d_in] (see rows_tensors)."""
+        return self.rows_tensors(int(i)).cpu().numpy()
+
+    def reconstruct_n(self, i0, ni):
+        """FAISS ``reconstruct_n``: rows [i0, i0 + ni) as float32 numpy [ni, d_in]."""
+        i0, ni = int(i0), int(ni)
+        if ni < 0 or i0 < 0 or i0 + ni > self.ntotal:
+            raise IndexError("reconstruct_n: rows [%d, %d) outside [0, ntotal = %d)" % (i0, i0 + ni, self.ntotal))
+        return self.rows_tensors(np.arange(i0, i0 + ni, dtype=np.int64)).cpu().numpy()
+
+    def reconstruct_batch(self, ids):
+        """FAISS ``reconstruct_batch``: the rows `ids` (int64 vector) as float32 numpy [len(ids), d_in]."""
+        return self.rows_tensors(ids).cpu().numpy()
 
     def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
                      deep=False, allowed=None):

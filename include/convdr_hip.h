@@ -294,6 +294,40 @@ int convdr_ip_rank_rows(int store, const float* q_f32, int np, const int64_t* ta
                         int64_t row_bits_words, int64_t n_allowed, int cap, void* workspace, size_t workspace_bytes,
                         int64_t* rank, double* X, int64_t* counts, int64_t* above, int32_t* status, convdr_stream_t stream);
 
+/* Removing rows: stable IN-PLACE compaction of a resident row buffer (FAISS: remove_ids).  The buffer is never copied; the
+ * extra memory is the workspace, bounded by one window of rows.
+ *   keep set     keep_bits / keep_bits_words: the bitmap contract of convdr_ip_search_filtered (16-byte aligned, bit (r & 31) of
+ *                word (r >> 5) set = row r is KEPT, whole 256-row tiles zero padded: keep_bits_words >= ceil(n / 256) * 8, bits
+ *                past n ignored).  NULL, 0: every row is kept.
+ *   result       a kept row r ends at row dest(r) = the number of kept rows before r: the order is preserved, dest(r) <= r,
+ *                rows [0, n_kept) of the buffer are the kept rows in order, bit for bit, and rows [n_kept, n) are unspecified.
+ *   two calls    convdr_ip_compact_plan, once: per-tile kept counts and their exclusive prefix, written to the workspace, and
+ *                the device scalar *n_kept (int64).  Then convdr_ip_compact_rows once per buffer that shares the row numbering
+ *                (the fp32 block, the scan copy, the remainder copy), with the same n, bitmap and workspace; the workspace is
+ *                sized for the widest row_bytes.  Everything is enqueued on `stream`; the calls between them need no host read.
+ *   windows      the buffer is processed in windows of window_rows consecutive source rows, one after the other in stream
+ *                order.  Window [a, b) with kept_w kept rows writes [dest(a), dest(a) + kept_w), which ends at or before b and
+ *                can overlap only the window's own sources and rows of earlier, finished windows.  Per window, decided on the
+ *                device: SKIP (dest(a) == a and kept_w == b - a: nothing removed so far), DIRECT (dest(a) + kept_w <= a: the
+ *                destination cannot touch the window's sources) or BOUNCE (one launch packs the kept rows into the bounce
+ *                buffer, the next copies them to the destination).  Two launches per window are always enqueued; the one with
+ *                nothing to do returns at once.  Ordering is stream order alone: no workgroup waits for another.
+ *                window_rows: a multiple of 256 in [256, 1048576].
+ *   row_bytes    a multiple of 16 in [16, 65536]; rows are moved as 16-byte pieces with streaming loads and stores.  The
+ *                buffer must be 16-byte aligned.
+ *   workspace    convdr_ip_compact_workspace_bytes(n, row_bytes, window_rows) bytes (0 outside the contract: convdr_last_error
+ *                says why), 256-byte aligned regions in this order: tile prefix u32 [ceil(n / 256) + 1] (the last entry is
+ *                n_kept) | chunk sums u32 [ceil((ceil(n / 256) + 1) / 8192)] | bounce buffer window_rows x row_bytes bytes.
+ *                convdr_ip_compact_plan writes the first two regions and needs no more than them; convdr_ip_compact_rows
+ *                reads the prefix and uses the bounce buffer.  Nothing of it is read before these calls wrote it.
+ * 0 <= n < 2^31.  n == 0, or a bitmap that keeps every row: nothing moves, *n_kept is still written.  Arguments are validated
+ * before anything touches a device; no allocation, no sync. */
+size_t convdr_ip_compact_workspace_bytes(int64_t n, int64_t row_bytes, int64_t window_rows);
+int convdr_ip_compact_plan(const uint32_t* keep_bits, int64_t keep_bits_words, int64_t n, void* workspace, size_t workspace_bytes,
+                           int64_t* n_kept, convdr_stream_t stream);
+int convdr_ip_compact_rows(void* rows, int64_t row_bytes, int64_t n, const uint32_t* keep_bits, int64_t keep_bits_words,
+                           int64_t window_rows, void* workspace, size_t workspace_bytes, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
