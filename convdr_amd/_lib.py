@@ -207,6 +207,10 @@ register("convdr_topk_distinct_deep", C.c_int, [_p, _p, C.c_int, C.c_int64, C.c_
 register("convdr_topk_merge_deep", C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, _p, _p, C.c_int64,
                                              _p])
 register("convdr_topk_merge_deep_packed", C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, C.c_int64, _p])
+register("convdr_run_label", C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _p, _p, _p, C.c_int64, _p, _p])
+register("convdr_run_measures", C.c_int, [_p, C.c_int, C.c_int, _p, _p, _p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, _p,
+                                          _p])
+register("convdr_run_negatives", C.c_int, [_p, _p, C.c_int, C.c_int64, C.c_int, _p, _p, _p, C.c_int64, C.c_int, _p, _p, _p, _p])
 register("convdr_pack_transposed", C.c_int, [_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int64), _p, _p])
 register("convdr_pack_transposed_bf16", C.c_int, [_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

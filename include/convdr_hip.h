@@ -408,6 +408,56 @@ int convdr_topk_merge_deep(const float* D, const int64_t* I, int nlists, int n, 
 int convdr_topk_merge_deep_packed(const void* lists, int nlists, int n, int nq, int n_out, float* Dout, int64_t* Iout,
                                   int64_t ldo, convdr_stream_t stream);
 
+/* Judging a run: join a ranked key list per query with that query's judged set (the qrels) on the device.  Replaces the
+ * per-entry dict lookup of the reference's drivers/run_convdr_inference.py:98-99, the trec_eval step that follows its .trec
+ * file, and the two walks over a text run file of its data/gen_ranking_data.py:539-567.
+ *   run          K int64 [nq, n], row pitch ld >= n: per query a ranked list of DISTINCT keys (what convdr_topk_distinct[_deep]
+ *                writes as Kout); a negative entry is padding wherever it stands.  0 <= n <= 65536, nq >= 0.
+ *   qrels        a CSR over the SAME query order: off int64 [nq + 1] (off[0] = 0, monotone, off[nq] = nnz), and per query q in
+ *                [off[q], off[q + 1]): key int64 strictly ascending, grade int32 (<= 0: judged non-relevant; the two sentinel
+ *                values below are not grades), ideal int32 = the segment's positive grades sorted descending, then zeros.
+ *                The library cannot check these on the device (convdr_amd/judge.py checks them when it packs); a segment is
+ *                clamped to [0, nnz] before use, so a wrong off gives wrong answers, never an access outside the arrays.
+ *   labels       int32 [nq, n] (dense): the grade of K[q, r] in q's segment, found by binary search on the full 64-bit key,
+ *                CONVDR_LABEL_UNJUDGED for a key that is not there, CONVDR_LABEL_PAD for padding.
+ *
+ * convdr_run_measures: out fp64 [nq, 4 + 3 nc].  An entry is RELEVANT iff label >= rel_level (>= 1); its GAIN is
+ * max(label, 0) whatever rel_level is; sentinels are neither.  Ranks r start at 1; c runs over the nc cutoffs (a HOST array,
+ * each >= 1, strictly ascending, nc <= 16).  Columns:
+ *   0            num_rel      qrels entries of the query with grade >= rel_level
+ *   1            num_rel_ret  relevant entries of the list
+ *   2            recip_rank   1 / r of the first relevant entry, else 0
+ *   3            map          (sum over relevant ranks r of #relevant in 1..r / r) / num_rel; 0 when num_rel = 0
+ *   4 + i        ndcg_cut_c   DCG_c / IDCG_c; DCG_c = sum over r <= min(c, n) of gain_r / log2(r + 1), IDCG_c the same sum over
+ *                             the first c values of ideal; 0 when IDCG_c = 0
+ *   4 + nc + i   recall_c     #relevant in 1..min(c, n) / num_rel; 0 when num_rel = 0
+ *   4 + 2nc + i  P_c          #relevant in 1..min(c, n) / c
+ * All in fp64; the counts and the single divisions are exact / correctly rounded, the two sums (map, DCG) are made in a fixed
+ * order that is not the ascending-rank order (at most 65,536 non-negative terms: relative error below 1e-11), and a call
+ * repeats bit for bit.  These are the usual trec_eval per-query definitions restated; agreement is claimed with THESE FORMULAS
+ * (tests/judge_cases.py), not with the trec_eval binary, which nothing here runs.  Averaging over queries is the caller's.
+ *
+ * convdr_run_negatives: the negative list of gen_ranking_data.py:539-567 for one ranked list per query.  out_keys (and out_rows,
+ * with I = the row ids of the same entries, pitch ld; both or neither) int64 [nq, W], W = max(n, fill_to), -1 padded; counts
+ * int32 [nq].  A query with no qrels entry of grade > 0 gets count 0 (the reference's `positive_ids != {}`).  Otherwise A then B:
+ *   A            every entry whose label is a judged grade <= 0, in list order, uncapped;
+ *   B            the first max(0, fill_to - |A|) entries, in list order, that are not positives (label <= 0 or not judged;
+ *                padding skipped).  B REPEATS members of A: the reference's second pass appends without looking at the first's.
+ * fill_to in [0, 65536] (the reference: 20).  Sampling num_negs of the list stays with the caller.
+ *
+ * Every array but cutoffs is a device pointer; key, grade, ideal may be NULL when nnz = 0, K / I / labels when n = 0.  nq = 0
+ * (and n = 0 for convdr_run_label): returns 0 without a launch.  Arguments are validated before anything touches a device; no
+ * allocation, no sync, no workspace.  One 1,024-thread workgroup per query walks the list 1,024 ranks at a time. */
+#define CONVDR_LABEL_PAD (-2147483647 - 1)  /* the entry is padding                       */
+#define CONVDR_LABEL_UNJUDGED (-2147483647) /* the key is not in the query's qrels segment */
+int convdr_run_label(const int64_t* K, int n, int64_t ld, int nq, const int64_t* off, const int64_t* key, const int32_t* grade,
+                     int64_t nnz, int32_t* labels, convdr_stream_t stream);
+int convdr_run_measures(const int32_t* labels, int n, int nq, const int64_t* off, const int32_t* grade, const int32_t* ideal,
+                        int64_t nnz, int rel_level, const int32_t* cutoffs, int n_cutoffs, double* out, convdr_stream_t stream);
+int convdr_run_negatives(const int64_t* K, const int64_t* I, int n, int64_t ld, int nq, const int32_t* labels, const int64_t* off,
+                         const int32_t* grade, int64_t nnz, int fill_to, int64_t* out_keys, int64_t* out_rows, int32_t* counts,
+                         convdr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Dual-encoder forward: replaces the HuggingFace RobertaModel / BertModel forward + pooling + head
  * behind  /root/reference/model/models.py:140-148 (RobertaDot_NLL_LN.query_emb / body_emb) and
