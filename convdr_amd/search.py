@@ -60,6 +60,17 @@ def pack_row_mask(mask):
     return by.contiguous().view(torch.int32)
 
 
+def split_under(ws_bytes, count, budget):
+    """(items per call, workspace bytes of one such call): the items of one request -- queries, (query, row) pairs -- are halved
+    until ws_bytes(items), the entry's own workspace function, fits `budget` (None: never split); the calls then run back to
+    back on the stream and share the buffer.  A single item is never split, and 0 bytes means sizes outside the entry's
+    contract: the caller raises, in its own words."""
+    step = count
+    while budget is not None and step > 1 and ws_bytes(step) > budget:
+        step = (step + 1) // 2
+    return step, ws_bytes(step)
+
+
 class RowFilter:
     """An allowed subset of an index's rows (FlatIPIndex.row_filter): `bits` the device bitmap (pack_row_mask), `n` the ntotal
     it was built for -- searching an index of another size with it raises ValueError --, `n_allowed` the number of allowed rows."""
@@ -203,6 +214,29 @@ class FlatIPIndex:
             r = self._pbf[sel].contiguous()
             return r, r
         return self._p32[sel].contiguous(), self._pbf[sel].contiguous()
+
+    def _operands(self, rows=None):
+        """What a block looks like to the C ABI: (store code 0 bf16 / 1 fp16 / 2 half store, fp32 rows or NULL, 16-bit operand,
+        scale of that operand, centre or NULL) of the resident block, or of `rows` = (re-score rows, scan copy) of a slice.  The
+        half store has no fp32 rows and no centre, the bf16 copy no scale."""
+        ptr = _lib.ptr
+        p32, p16 = (self._rows, self._pbf) if rows is None else rows
+        store = 2 if self._half else (1 if self.kind == "f16" else 0)
+        return (store, None if self._half else ptr(p32), ptr(p16), float(self._scale) if store else 1.0,
+                None if self._half else ptr(self._centre))
+
+    def _queries(self, q, padded_ok=False):
+        """The queries as every entry reads them: fp32 [nq, d] on the index's device, contiguous, the zero columns of a padded
+        width appended (padded_ok: a tensor that already has them is taken as it is)."""
+        import torch
+        qt = torch.as_tensor(q)
+        if qt.dtype != torch.float32:
+            qt = qt.float()
+        if self.d != self.d_in and not (padded_ok and qt.dim() == 2 and qt.shape[1] == self.d):
+            qt = self._pad_columns(qt)
+        qt = qt.to(self.device).contiguous()
+        assert qt.dim() == 2 and qt.shape[1] == self.d
+        return qt
 
     def reset(self):
         """faiss ``index.reset()``: forget the passages.  A reservation made with reserve() survives (its memory is reused
@@ -699,20 +733,16 @@ class FlatIPIndex:
         """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth; with a
         RowFilter, convdr_ip_search_filtered with the same operands."""
         ptr = _lib.ptr
+        store, r32, r16, scale, _ = self._operands((p32, p16))
+        rlo, split = None if self._half else ptr(plo), int(bool(split)) if self._half else 0
         if allowed is not None:
-            store = 2 if self._half else (1 if self.kind == "f16" else 0)
             _lib.check(_lib.lib().convdr_ip_search_filtered(
-                store, int(bool(deep)), ptr(q), nq, None if self._half else ptr(p32), ptr(p16), None if self._half else ptr(plo),
-                float(self._scale) if store else 1.0, int(bool(split)) if self._half else 0, n, self.d, k, ptr(self._max_norm),
+                store, int(bool(deep)), ptr(q), nq, r32, r16, rlo, scale, split, n, self.d, k, ptr(self._max_norm),
                 ptr(tau_in), cap, rank_target, ptr(ws), ws.numel(), ptr(allowed.bits), allowed.bits.numel(), allowed.n_allowed,
                 ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr()), "convdr_ip_search_filtered")
             return
-        if self._half:
-            name, rows = "_h16", (ptr(p16), float(self._scale), int(bool(split)))
-        elif self.kind == "f16":
-            name, rows = "_f16", (ptr(p32), ptr(p16), ptr(plo), float(self._scale))
-        else:
-            name, rows = "", (ptr(p32), ptr(p16), ptr(plo))
+        # the direct entry of the store code, each with the operands it declares
+        name, rows = (("", (r32, r16, rlo)), ("_f16", (r32, r16, rlo, scale)), ("_h16", (r16, scale, split)))[store]
         name = "convdr_ip_search" + ("_deep" if deep else "") + name
         _lib.check(getattr(_lib.lib(), name)(ptr(q), nq, *rows, n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target,
                                              ptr(ws), ws.numel(), ptr(D), ptr(I), ptr(status), ptr(tau_retry),
@@ -739,10 +769,7 @@ class FlatIPIndex:
         status = torch.empty(nq, dtype=torch.int32, device=self.device)
         tau_retry = torch.empty(nq, dtype=torch.float32, device=self.device)
         ws_bytes = L.convdr_ip_deep_workspace_bytes if deep else L.convdr_ip_workspace_bytes
-        step = nq
-        while deep and step > 1 and ws_bytes(step, n, self.d, k, cap) > self.DEEP_WS_BYTES:
-            step = (step + 1) // 2
-        need = ws_bytes(step, n, self.d, k, cap)
+        step, need = split_under(lambda c: ws_bytes(c, n, self.d, k, cap), nq, self.DEEP_WS_BYTES if deep else None)
         if deep and not need:
             raise _lib.ConvdrError("convdr_ip_search_deep: sizes outside the contract (nq=%d n=%d d=%d k=%d cap=%d)"
                                    % (nq, n, self.d, k, cap))
@@ -831,12 +858,7 @@ class FlatIPIndex:
         """First half of search_tensors: the first scan pass is ENQUEUED (no host round trip) and a handle returned;
         search_finish(handle) reads the certificates and walks the ladder for whatever the first pass left open.  Between the
         two the host is free -- search_one_by_one loads the next block file meanwhile."""
-        import torch
-        qt = torch.as_tensor(q)
-        if qt.dtype != torch.float32:
-            qt = qt.float()
-        qt = (self._pad_columns(qt) if self.d != self.d_in else qt.to(self.device)).contiguous()
-        assert qt.dim() == 2 and qt.shape[1] == self.d
+        qt = self._queries(q)
         k = int(k)
         f = self._filter(allowed)
         kw = {} if f is None else {"allowed": f}
@@ -1164,16 +1186,6 @@ class FlatIPIndex:
             raise ValueError("range_search: a radius is NaN")
         return r
 
-    def _range_step(self, nq, n, cap):
-        """queries per call, so that one call's workspace stays under DEEP_WS_BYTES (as _enqueue splits the deep search)"""
-        ws_bytes = _lib.lib().convdr_ip_range_workspace_bytes
-        step = nq
-        while step > 1 and ws_bytes(step, n, self.d, cap) > self.DEEP_WS_BYTES:
-            step = (step + 1) // 2
-        if not ws_bytes(step, n, self.d, cap):
-            raise _lib.ConvdrError("convdr_ip_range_search: sizes outside the contract (nq=%d n=%d d=%d cap=%d)" % (nq, n, self.d, cap))
-        return step
-
     def _range_pass(self, q, rad, cap, count_only, allowed=None, rows=None, want_x=False):
         """One pass of convdr_ip_range_search (+ convdr_ip_range_pack) over the resident block, or over `rows` = (re-score rows,
         scan copy) of a slice.  Returns (counts int64 numpy [nq], status numpy [nq], lims, D, I, X): the device result of the
@@ -1181,11 +1193,13 @@ class FlatIPIndex:
         One host read per call (status, counts and the total that sizes D and I)."""
         import torch
         L, ptr = _lib.lib(), _lib.ptr
-        p32, p16 = (self._rows, self._pbf) if rows is None else rows
-        nq, n = int(q.shape[0]), int(p16.shape[0])
-        store = 2 if self._half else (1 if self.kind == "f16" else 0)
-        step = self._range_step(nq, n, cap)
-        ws = self._workspace(L.convdr_ip_range_workspace_bytes(step, n, self.d, cap))
+        nq, n = int(q.shape[0]), self.ntotal if rows is None else int(rows[1].shape[0])
+        # queries per call, so that one call's workspace stays under DEEP_WS_BYTES (as _enqueue splits the deep search)
+        step, need = split_under(lambda c: L.convdr_ip_range_workspace_bytes(c, n, self.d, cap), nq, self.DEEP_WS_BYTES)
+        if not need:
+            raise _lib.ConvdrError("convdr_ip_range_search: sizes outside the contract (nq=%d n=%d d=%d cap=%d)" % (nq, n, self.d, cap))
+        ws = self._workspace(need)
+        store, r32, r16, scale, centre = self._operands(rows)
         bits = None if allowed is None else allowed.bits
         counts, status, parts = [], [], []
         with torch.cuda.device(self.device):
@@ -1194,8 +1208,7 @@ class FlatIPIndex:
                 out = torch.empty(3 * (b - a) + 1, dtype=torch.int64, device=self.device)     # counts | lims | status (int32)
                 cnt, lims, st = out[:b - a], out[b - a:2 * (b - a) + 1], out[2 * (b - a) + 1:].view(torch.int32)[:b - a]
                 _lib.check(L.convdr_ip_range_search(
-                    store, ptr(q[a:b]), b - a, None if self._half else ptr(p32), ptr(p16), float(self._scale) if store else 1.0,
-                    None if self._half else ptr(self._centre), n, self.d, ptr(self._max_norm), ptr(rad[a:b]), cap, int(count_only),
+                    store, ptr(q[a:b]), b - a, r32, r16, scale, centre, n, self.d, ptr(self._max_norm), ptr(rad[a:b]), cap, int(count_only),
                     ptr(bits), 0 if bits is None else bits.numel(), ptr(ws), ws.numel(), ptr(cnt), ptr(lims), ptr(st),
                     _lib.stream_ptr()), "convdr_ip_range_search")
                 host = out.cpu().numpy()                                                       # the pass's one host read
@@ -1247,56 +1260,73 @@ class FlatIPIndex:
         lims = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]), device=self.device)
         return counts, lims, X.to(torch.float32), I
 
-    def _range(self, q, radius, allowed, count_only):
+    def _count_ladder(self, who, n_items, one_pass, accept):
+        """The ladder of the entries that report an EXACT count (range search: hits per query; rank: band rows per pair).
+        A queue of (item numbers, cap) groups, one pass per group, starting with every item at min(self.cap, RANGE_MAX_CAP):
+        one_pass(idx, sub, cap) -> (status, counts, result) runs the items idx (numpy; `sub` the same as a device index
+        tensor, None for all items); accept(idx, sub, cap, ok, counts, result) keeps what a pass certified.  CONVDR_IP_RANGE
+        rebuilds the scan copy once (as search_finish) and the group runs again; an item that overflowed is re-run once, at the
+        smallest power of two that holds its count.  Returns (passes, the longest list used, the items whose count no list up
+        to RANGE_MAX_CAP holds: the caller's last rung)."""
         import torch
-        qt = torch.as_tensor(q)
-        if qt.dtype != torch.float32:
-            qt = qt.float()
-        qt = (self._pad_columns(qt) if self.d != self.d_in else qt.to(self.device)).contiguous()
-        assert qt.dim() == 2 and qt.shape[1] == self.d
-        nq = int(qt.shape[0])
-        rad = self._range_radius(radius, nq)
-        f = self._filter(allowed)
-        self.stats = {"range_results": 0, "range_rounds": 0, "range_cap": 0, "range_chunked_queries": 0, "rescaled": 0}
-        counts = np.zeros(nq, np.int64)
-        pieces = []                         # (query numbers, lims, D, I) of every pass that certified a query
         cap_max = int(self.RANGE_MAX_CAP)
-        groups = [(np.arange(nq), min(int(self.cap), cap_max))] if nq and self.ntotal and (f is None or f.n_allowed) else []
-        chunked = []
+        groups = [(np.arange(n_items), min(int(self.cap), cap_max))]
+        passes, longest, beyond = 0, 0, []
         while groups:
             idx, cap = groups.pop(0)
-            whole = len(idx) == nq
-            sub = None if whole else torch.as_tensor(idx, device=self.device)
-            cnt, st, lims, D, I, _ = self._range_pass(qt if whole else qt[sub].contiguous(), rad if whole else rad[sub].contiguous(),
-                                                      cap, count_only, allowed=f)
-            self.stats["range_rounds"] += 1
-            self.stats["range_cap"] = max(self.stats["range_cap"], cap)
+            sub = None if len(idx) == n_items else torch.as_tensor(idx, device=self.device)
+            st, cnt, result = one_pass(idx, sub, cap)
+            passes, longest = passes + 1, max(longest, cap)
             if (st == STATUS_RANGE).any():
                 if self.kind != "f16" or self.stats["rescaled"]:
-                    raise _lib.ConvdrError("convdr_ip_range_search: CONVDR_IP_RANGE %s" % ("after the scan copy was rebuilt"
+                    raise _lib.ConvdrError("%s: CONVDR_IP_RANGE %s" % (who, "after the scan copy was rebuilt"
                                            if self.stats["rescaled"] else "from a bf16 scan"))
                 self._rebuild_scaled()
                 self.stats["rescaled"] = 1
                 groups.insert(0, (idx, cap))
                 continue
             ok, over = st == STATUS_OK, st == STATUS_OVERFLOW
-            if not (ok | over).all() or self.stats["range_rounds"] > 64:
-                raise _lib.ConvdrError("convdr_ip_range_search: unexpected status %s" % (st,))
-            counts[idx[ok]] = cnt[ok]
-            if not count_only and ok.any():
-                pieces.append((idx, lims, D, I))
-            # the reported hit count is exact: the list that holds it cannot overflow -- one jump, no doubling
+            if not (ok | over).all() or passes > 64:
+                raise _lib.ConvdrError("%s: unexpected status %s" % (who, st))
+            accept(idx, sub, cap, ok, cnt, result)
+            # the reported count is exact and the thresholds do not change: the list that holds it cannot overflow -- one
+            # jump, no doubling
             need = np.asarray([1 << int(c - 1).bit_length() for c in cnt[over]], dtype=np.int64)
-            chunked += list(idx[over][need > cap_max])
+            beyond += list(idx[over][need > cap_max])
             for c in sorted(set(need[need <= cap_max].tolist())):
                 groups.append((idx[over][need == c], int(c)))
+        return passes, longest, beyond
+
+    def _range(self, q, radius, allowed, count_only):
+        import torch
+        qt = self._queries(q)
+        nq = int(qt.shape[0])
+        rad = self._range_radius(radius, nq)
+        f = self._filter(allowed)
+        self.stats = {"range_results": 0, "range_rounds": 0, "range_cap": 0, "range_chunked_queries": 0, "rescaled": 0}
+        counts = np.zeros(nq, np.int64)
+        pieces = []                         # (query numbers, lims, D, I) of every pass that certified a query
+
+        def one_pass(idx, sub, cap):
+            cnt, st, lims, D, I, _ = self._range_pass(qt if sub is None else qt[sub].contiguous(),
+                                                      rad if sub is None else rad[sub].contiguous(), cap, count_only, allowed=f)
+            return st, cnt, (lims, D, I)
+
+        def accept(idx, sub, cap, ok, cnt, result):
+            counts[idx[ok]] = cnt[ok]
+            if not count_only and ok.any():
+                pieces.append((idx,) + result)
+        chunked = []
+        if nq and self.ntotal and (f is None or f.n_allowed):
+            rounds, longest, chunked = self._count_ladder("convdr_ip_range_search", nq, one_pass, accept)
+            self.stats.update(range_rounds=rounds, range_cap=longest)
         if chunked:
             idx = np.asarray(sorted(chunked), dtype=np.int64)
             sub = torch.as_tensor(idx, device=self.device)
             cnt, lims, D, I = self._range_chunked(qt[sub].contiguous(), rad[sub].contiguous(), f, count_only)
             counts[idx] = cnt
             self.stats["range_chunked_queries"] = len(idx)
-            self.stats["range_cap"] = max(self.stats["range_cap"], cap_max)      # (every slice's list)
+            self.stats["range_cap"] = max(self.stats["range_cap"], int(self.RANGE_MAX_CAP))     # (every slice's list)
             if not count_only:
                 pieces.append((idx, lims, D, I))
         self.stats["range_results"] = int(counts.sum())
@@ -1332,13 +1362,11 @@ class FlatIPIndex:
         D = torch.empty((nq, m), dtype=torch.float32, device=self.device)
         X = torch.empty((nq, m), dtype=torch.float64, device=self.device)
         if nq and m:
-            store = 2 if self._half else (1 if self.kind == "f16" else 0)
             n = self.ntotal
+            store, r32, r16, scale, _ = self._operands(None if n else (None, None))     # (an empty index passes no rows)
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().convdr_ip_score_rows(
-                    store, _lib.ptr(qt), nq, None if (self._half or not n) else _lib.ptr(self._rows), _lib.ptr(self._pbf) if n else None,
-                    float(self._scale) if store else 1.0, n, self.d, _lib.ptr(rt), m, m, _lib.ptr(X), _lib.ptr(D), _lib.stream_ptr()),
-                    "convdr_ip_score_rows")
+                _lib.check(_lib.lib().convdr_ip_score_rows(store, _lib.ptr(qt), nq, r32, r16, scale, n, self.d, _lib.ptr(rt), m, m,
+                                                           _lib.ptr(X), _lib.ptr(D), _lib.stream_ptr()), "convdr_ip_score_rows")
         return D.reshape(shape), X.reshape(shape)
 
     def rank_rows(self, q, rows, allowed=None):
@@ -1375,38 +1403,23 @@ class FlatIPIndex:
         qp = qt if m == 1 else qt.repeat_interleave(m, dim=0)
         tp = rt.reshape(-1).contiguous()
         X = torch.empty(npairs, dtype=torch.float64, device=self.device)
-        cap_max = int(self.RANGE_MAX_CAP)
-        groups = [(np.arange(npairs), min(int(self.cap), cap_max))]
-        fallback = []
-        while groups:
-            idx, cap = groups.pop(0)
-            whole = len(idx) == npairs
-            sub = None if whole else torch.as_tensor(idx, device=self.device)
-            rank, cnt, above, st, Xs = self._rank_pass(qp if whole else qp[sub].contiguous(), tp if whole else tp[sub].contiguous(), cap, f)
-            self.stats["rank_rounds"] += 1
-            self.stats["rank_cap"] = max(self.stats["rank_cap"], cap)
-            if (st == STATUS_RANGE).any():
-                if self.kind != "f16" or self.stats["rescaled"]:
-                    raise _lib.ConvdrError("convdr_ip_rank_rows: CONVDR_IP_RANGE %s" % ("after the scan copy was rebuilt"
-                                           if self.stats["rescaled"] else "from a bf16 scan"))
-                self._rebuild_scaled()
-                self.stats["rescaled"] = 1
-                groups.insert(0, (idx, cap))
-                continue
-            ok, over = st == STATUS_OK, st == STATUS_OVERFLOW
-            if not (ok | over).all() or self.stats["rank_rounds"] > 64:
-                raise _lib.ConvdrError("convdr_ip_rank_rows: unexpected status %s" % (st,))
+
+        def one_pass(idx, sub, cap):
+            rank, cnt, above, st, Xs = self._rank_pass(qp if sub is None else qp[sub].contiguous(),
+                                                       tp if sub is None else tp[sub].contiguous(), cap, f)
+            return st, cnt, (rank, above, Xs)
+
+        def accept(idx, sub, cap, ok, cnt, result):
+            nonlocal out, X
+            rank, above, Xs = result
             self.stats["rank_band_rows"] += int(np.minimum(cnt, cap).sum())
             self.stats["rank_above"] += int(above[ok].sum())
-            if whole:
+            if sub is None:
                 out, X = torch.as_tensor(rank, device=self.device), Xs
             else:
                 out[sub], X[sub] = torch.as_tensor(rank, device=self.device), Xs
-            # the reported band count is exact and the thresholds do not change: the list that holds it cannot overflow
-            need = np.asarray([1 << int(c - 1).bit_length() for c in cnt[over]], dtype=np.int64)
-            fallback += list(idx[over][need > cap_max])
-            for c in sorted(set(need[need <= cap_max].tolist())):
-                groups.append((idx[over][need == c], int(c)))
+        rounds, longest, fallback = self._count_ladder("convdr_ip_rank_rows", npairs, one_pass, accept)
+        self.stats.update(rank_rounds=rounds, rank_cap=longest)
         if fallback:
             stats = self.stats
             stats["rank_fallback_pairs"] = len(fallback)
@@ -1427,8 +1440,6 @@ class FlatIPIndex:
         """(queries device fp32 [nq, d], rows device int64 [nq, m], the shape of `rows`); the checks that need no device"""
         import torch
         qt = torch.as_tensor(q)
-        if qt.dtype != torch.float32:
-            qt = qt.float()
         if qt.dim() != 2 or qt.shape[1] not in (self.d, self.d_in):
             raise ValueError("%s: queries must be [nq, %d] (got shape %s)" % (who, self.d_in, tuple(qt.shape)))
         nq = int(qt.shape[0])
@@ -1440,19 +1451,9 @@ class FlatIPIndex:
         shape = tuple(rt.shape)
         if rt.device.type == "cpu" and rt.numel() and int(rt.max()) >= self.ntotal:
             raise ValueError("%s: row id %d >= ntotal = %d" % (who, int(rt.max()), self.ntotal))
-        qt = (self._pad_columns(qt) if qt.shape[1] != self.d else qt.to(self.device)).contiguous()
+        qt = self._queries(qt, padded_ok=True)
         rt = rt.to(torch.int64).to(self.device).reshape(nq, -1).contiguous()
         return qt, rt, shape
-
-    def _rank_step(self, npairs, n, cap):
-        """pairs per call, so that one call's workspace stays under DEEP_WS_BYTES (as _range_step)"""
-        ws_bytes = _lib.lib().convdr_ip_rank_workspace_bytes
-        step = npairs
-        while step > 1 and ws_bytes(step, n, self.d, cap) > self.DEEP_WS_BYTES:
-            step = (step + 1) // 2
-        if not ws_bytes(step, n, self.d, cap):
-            raise _lib.ConvdrError("convdr_ip_rank_rows: sizes outside the contract (np=%d n=%d d=%d cap=%d)" % (npairs, n, self.d, cap))
-        return step
 
     def _rank_pass(self, qp, tp, cap, allowed=None):
         """One pass of convdr_ip_rank_rows over the resident block: (rank, band counts, above, status) numpy [np] and the
@@ -1460,9 +1461,12 @@ class FlatIPIndex:
         import torch
         L, ptr = _lib.lib(), _lib.ptr
         npairs, n = int(qp.shape[0]), self.ntotal
-        store = 2 if self._half else (1 if self.kind == "f16" else 0)
-        step = self._rank_step(npairs, n, cap)
-        ws = self._workspace(L.convdr_ip_rank_workspace_bytes(step, n, self.d, cap))
+        # pairs per call, so that one call's workspace stays under DEEP_WS_BYTES (as _range_pass)
+        step, need = split_under(lambda c: L.convdr_ip_rank_workspace_bytes(c, n, self.d, cap), npairs, self.DEEP_WS_BYTES)
+        if not need:
+            raise _lib.ConvdrError("convdr_ip_rank_rows: sizes outside the contract (np=%d n=%d d=%d cap=%d)" % (npairs, n, self.d, cap))
+        ws = self._workspace(need)
+        store, r32, r16, scale, centre = self._operands()
         bits = None if allowed is None else allowed.bits
         X = torch.empty(npairs, dtype=torch.float64, device=self.device)
         hosts = []
@@ -1472,10 +1476,8 @@ class FlatIPIndex:
                 c = b - a
                 out = torch.empty(4 * c, dtype=torch.int64, device=self.device)      # rank | counts | above | status (int32)
                 _lib.check(L.convdr_ip_rank_rows(
-                    store, ptr(qp[a:b]), c, ptr(tp[a:b]), None if self._half else ptr(self._rows), ptr(self._pbf),
-                    float(self._scale) if store else 1.0, None if self._half else ptr(self._centre), n, self.d, ptr(self._max_norm),
-                    ptr(bits), 0 if bits is None else bits.numel(), 0 if allowed is None else allowed.n_allowed, cap, ptr(ws),
-                    ws.numel(), ptr(out[:c]), ptr(X[a:b]), ptr(out[c:2 * c]), ptr(out[2 * c:3 * c]), ptr(out[3 * c:]),
+                    store, ptr(qp[a:b]), c, ptr(tp[a:b]), r32, r16, scale, centre, n, self.d, ptr(self._max_norm), ptr(bits),
+                    0 if bits is None else bits.numel(), 0 if allowed is None else allowed.n_allowed, cap, ptr(ws), ws.numel(), ptr(out[:c]), ptr(X[a:b]), ptr(out[c:2 * c]), ptr(out[2 * c:3 * c]), ptr(out[3 * c:]),
                     _lib.stream_ptr()), "convdr_ip_rank_rows")
                 host = out.cpu().numpy()                                             # the pass's one host read
                 hosts.append((host[:c], host[c:2 * c], host[2 * c:3 * c], host[3 * c:].view(np.int32)[:c]))
@@ -1704,10 +1706,7 @@ def distinct_topk_device(D, I, k, key_map=None):
                        "convdr_topk_distinct")
             return Do, Io, Ko, counts
         budget = FlatIPIndex.DEEP_WS_BYTES if DISTINCT_DEEP_WS_BYTES is None else int(DISTINCT_DEEP_WS_BYTES)
-        step = max(nq, 1)
-        while step > 1 and L.convdr_topk_distinct_deep_workspace_bytes(step, n) > budget:
-            step = (step + 1) // 2
-        need = L.convdr_topk_distinct_deep_workspace_bytes(step, n)
+        step, need = split_under(lambda c: L.convdr_topk_distinct_deep_workspace_bytes(c, n), max(nq, 1), budget)
         if n > FlatIPIndex.DEEP_MAX_K or k > FlatIPIndex.DEEP_MAX_K or not need:
             raise _lib.ConvdrError("convdr_topk_distinct_deep: sizes outside the contract (nq=%d n=%d n_out=%d)" % (nq, n, k))
         ws = torch.empty(need, dtype=torch.uint8, device=D.device)

@@ -247,20 +247,64 @@ def test_radius_forms_and_refusals():
     assert idx.trace == []
 
 
-def test_queries_are_split_under_the_workspace_limit():
-    """_range_step with the library's own workspace function: one call never asks for more than DEEP_WS_BYTES, and the split
+N_ROWS = 1000000
+# the four workspace planners behind split_under, as ws(L, items per call, size): the list capacity, or for the distinct cut the
+# length of the ranked lists; then a size where 1,000 items fit DEEP_WS_BYTES, the largest size, a count that does not fit at
+# that size, and a size outside the contract
+PLANNERS = {
+    "range": (lambda L, c, cap: L.convdr_ip_range_workspace_bytes(c, N_ROWS, 768, cap), 4096, 131072, 4000, 5000),
+    "rank": (lambda L, c, cap: L.convdr_ip_rank_workspace_bytes(c, N_ROWS, 768, cap), 4096, 131072, 4000, 5000),
+    "deep_topk": (lambda L, c, cap: L.convdr_ip_deep_workspace_bytes(c, N_ROWS, 768, 5000, cap), 16384, 131072, 4000, 5000),
+    "deep_distinct": (lambda L, c, n: L.convdr_topk_distinct_deep_workspace_bytes(c, n), 5000, 65536, 8000, 65537),
+}
+
+
+@pytest.mark.parametrize("planner", sorted(PLANNERS))
+def test_queries_are_split_under_the_workspace_limit(planner):
+    """split_under with the library's own workspace functions: one call never asks for more than DEEP_WS_BYTES, and the split
     is not finer than halving needs."""
-    ws = _lib.lib().convdr_ip_range_workspace_bytes
+    fn, small, large, many, bad = PLANNERS[planner]
+    L = _lib.lib()
+
+    def ws(c, size):
+        return fn(L, c, size)
+
+    def step(count, size, budget):
+        got, need = S.split_under(lambda c: ws(c, size), count, budget)
+        assert need == ws(got, size)
+        return got
+    budget = S.FlatIPIndex.DEEP_WS_BYTES
+    assert step(1000, small, budget) == 1000 and ws(1000, small) <= budget
+    got = step(many, large, budget)                   # range: 4000 x 131072 x 24 bytes = 12.6 GB in one call
+    assert 1 <= got < many and ws(got, large) <= budget < ws(min(many, 2 * got), large)
+    got = step(100, large, 64 << 20)
+    assert 1 <= got < 100 and ws(got, large) <= (64 << 20) < ws(2 * got, large)
+    assert step(100, small, 1) == 1                   # a single query is never split
+    assert step(many, large, None) == many            # no budget: never split
+    assert S.split_under(lambda c: ws(c, bad), 5, budget) == (5, 0)
+
+
+def test_every_pass_refuses_sizes_outside_the_contract_in_its_own_words():
+    """0 bytes from the workspace function: each user of split_under raises ConvdrError under its entry's name, before it
+    touches the device (the passes are the real ones, called on the stub)."""
     idx = RangeStub([0])
-    idx.d = 768
-    n = 1000000
-    assert idx._range_step(1000, n, 4096) == 1000 and ws(1000, n, 768, 4096) <= idx.DEEP_WS_BYTES
-    step = idx._range_step(4000, n, 131072)           # 4000 x 131072 x 24 bytes = 12.6 GB in one call
-    assert 1 <= step < 4000 and ws(step, n, 768, 131072) <= idx.DEEP_WS_BYTES < ws(min(4000, 2 * step), n, 768, 131072)
-    idx.DEEP_WS_BYTES = 64 << 20
-    step = idx._range_step(100, n, 131072)
-    assert 1 <= step < 100 and ws(step, n, 768, 131072) <= (64 << 20) < ws(2 * step, n, 768, 131072)
-    idx.DEEP_WS_BYTES = 1                              # a single query is never split
-    assert idx._range_step(100, n, 1024) == 1
-    with pytest.raises(_lib.ConvdrError):
-        idx._range_step(5, n, 5000)
+    q, z = _queries(5), torch.zeros((10, 64))
+    with pytest.raises(_lib.ConvdrError, match="convdr_ip_range_search: sizes outside the contract"):
+        S.FlatIPIndex._range_pass(idx, q, torch.zeros(5), 5000, False, rows=(z, z))
+    with pytest.raises(_lib.ConvdrError, match="convdr_ip_rank_rows: sizes outside the contract"):
+        S.FlatIPIndex._rank_pass(idx, q, torch.zeros(5, dtype=torch.int64), 5000)
+    with pytest.raises(_lib.ConvdrError, match="convdr_ip_search_deep: sizes outside the contract"):
+        idx._enqueue(q, 5000, None, 5000, False, deep=True, rows=(z, z))
+
+
+def test_a_status_that_is_neither_ok_nor_overflow_raises_after_one_pass():
+    """STATUS_TOO_FEW belongs to the top-k entries: from a range pass it is a broken contract, not a rung of the ladder."""
+    idx = RangeStub([10, 20])
+
+    def too_few(q, rad, cap, count_only, allowed=None, rows=None, want_x=False):
+        idx.trace.append(["pass", idx._ids(q).tolist(), int(cap), bool(count_only)])
+        return idx.hits, np.asarray([OK, S.STATUS_TOO_FEW], np.int32), None, None, None, None
+    idx._range_pass = too_few
+    with pytest.raises(_lib.ConvdrError, match="convdr_ip_range_search: unexpected status"):
+        idx.range_search_tensors(_queries(2), 0.0)
+    assert idx.trace == [["pass", [0, 1], 4096, False]]

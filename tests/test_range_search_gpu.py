@@ -13,52 +13,12 @@ import pytest
 from oracle import search as OS
 from tests.golden.make_golden import synth_corpus
 from tests.helpers import fill_bytes
+from tests.index_cases import CONFIGS, MASKS, SHAPES, torch_cuda      # noqa: F401 (torch_cuda: the fixture, by name)
+from tests.index_cases import corpus as _corpus, index as _index, mask as _mask, scores as _scores
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = [("fp32", "auto"), ("fp32", "bf16"), ("fp16", "auto")]
-# n, nq, d, clustered
-SHAPES = [
-    (300, 3, 64, False),          # ragged last tile, one K step
-    (257, 1, 100, False),         # padded width (d_in = 100), one query
-    (5000, 37, 768, False),
-    (33000, 130, 128, False),     # two query tiles: Tile256 and the r3 emit path
-    (5000, 37, 768, True),        # a common component of norm ~30 plus unit noise: q . centre matters
-]
-MASKS = ["half", "one", "last_tile", "word_edges", "none"]
-
-_CORPUS, _SCORES, _INDEX = {}, {}, {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _corpus(shape):
-    """(P = halves widened to fp32, Q); computed once, never written to afterwards"""
-    if shape not in _CORPUS:
-        n, nq, d, clustered = shape
-        P, Q = synth_corpus(100 + n % 97, n, d), synth_corpus(7, nq, d)
-        if clustered:
-            c = synth_corpus(9, 1, d)
-            c *= np.float32(30.0) / np.linalg.norm(c)
-            P, Q = P + c, Q + c
-        P = P.astype(np.float16).astype(np.float32)
-        P.setflags(write=False), Q.setflags(write=False)
-        _CORPUS[shape] = (P, Q)
-    return _CORPUS[shape]
-
-
-def _scores(shape):
-    if shape not in _SCORES:
-        P, Q = _corpus(shape)
-        S = OS.canonical_scores(Q, P)
-        S.setflags(write=False)
-        _SCORES[shape] = S
-    return _SCORES[shape]
+_MASKED_SCORES = {}       # (shape, mask name) -> the canonical scores over the allowed rows
 
 
 def _midpoint_radii(S, ms):
@@ -97,21 +57,6 @@ def _expected(S, rad32, rows=None):
         lims.append(lims[-1] + len(order))
     return (np.asarray(lims, np.int64), np.concatenate(Ds).astype(np.float32) if Ds else np.zeros(0, np.float32),
             np.concatenate(Is).astype(np.int64) if Is else np.zeros(0, np.int64))
-
-
-def _index(shape, storage, precision):
-    """one resident index per (shape, store, precision); one at a time"""
-    from convdr_amd.search import FlatIPIndex
-    key = (shape, storage, precision)
-    if key not in _INDEX:
-        _INDEX.clear()
-        P, _ = _corpus(shape)
-        idx = FlatIPIndex(shape[2], storage=storage, precision=precision, prepin=False)
-        idx.add(P.astype(np.float16) if storage == "fp16" else P)
-        _INDEX[key] = idx
-    idx = _INDEX[key]
-    idx.cap, idx.RANGE_MAX_CAP = 4096, 131072
-    return idx
 
 
 def _poison(idx, seed=1):
@@ -286,22 +231,6 @@ def test_last_rung_searches_row_slices(torch_cuda, storage, precision, filtered)
     np.testing.assert_array_equal(D2, want[1][want[0][1]:])
 
 
-def _mask(n, name):
-    m = np.zeros(n, bool)
-    if name == "half":
-        m = np.random.RandomState(11 + n).rand(n) < 0.5
-    elif name == "one":
-        m[n // 3] = True
-    elif name == "last_tile":
-        assert n % 256
-        m[n // 256 * 256:] = True
-    elif name == "word_edges":
-        m[[31, 32, 63, 64, 255, 256]] = True
-    else:
-        assert name == "none"
-    return m
-
-
 @pytest.mark.parametrize("name", MASKS)
 @pytest.mark.parametrize("storage,precision", CONFIGS)
 @pytest.mark.parametrize("n,nq,d", [(5000, 37, 768), (300, 3, 64)])
@@ -311,9 +240,9 @@ def test_row_filter(torch_cuda, n, nq, d, storage, precision, name):
     mask = _mask(n, name)
     rows = np.flatnonzero(mask)
     key = (shape, name)
-    if key not in _SCORES:
-        _SCORES[key] = OS.canonical_scores(Q, np.ascontiguousarray(P[rows])) if len(rows) else np.zeros((nq, 0))
-    Sr = _SCORES[key]
+    if key not in _MASKED_SCORES:
+        _MASKED_SCORES[key] = OS.canonical_scores(Q, np.ascontiguousarray(P[rows])) if len(rows) else np.zeros((nq, 0))
+    Sr = _MASKED_SCORES[key]
     rad = _midpoint_radii(Sr, _cycle(nq, len(rows)))
     want = _expected(Sr, rad, rows)
     if name == "none":

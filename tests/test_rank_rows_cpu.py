@@ -202,3 +202,52 @@ def test_ladder_rebuilds_once_on_range():
         RankStub(np.zeros(1000, np.int64), range_first=2).rank_rows(_queries(1), np.array([5]))
     with pytest.raises(_lib.ConvdrError):
         RankStub(np.zeros(1000, np.int64), kind="bf16", range_first=1).rank_rows(_queries(1), np.array([5]))
+
+
+def test_a_status_that_is_neither_ok_nor_overflow_raises_after_one_pass():
+    idx = RankStub(np.zeros(1000, np.int64))
+
+    def too_few(qp, tp, cap, allowed=None):
+        idx.trace.append(["pass", tp.tolist(), int(cap)])
+        z = np.zeros(len(tp), np.int64)
+        return z - 1, z, z, np.asarray([OK, S.STATUS_TOO_FEW], np.int32), torch.zeros(len(tp), dtype=torch.float64)
+    idx._rank_pass = too_few
+    with pytest.raises(_lib.ConvdrError, match="convdr_ip_rank_rows: unexpected status"):
+        idx.rank_rows(_queries(2), np.array([5, 150]))
+    assert idx.trace == [["pass", [5, 150], 4096]]
+
+
+@pytest.mark.parametrize("x", [0.1, 0.7, 0.0, -3.0])       # float32(x) above x, below x, and equal to x twice
+def test_a_band_beyond_range_max_cap_is_handed_to_the_fallback(x):
+    """One target whose band holds 131,073 rows: no list holds it, so the pair goes to range_search_tensors just below the
+    target's score and the rows that come back are compared by their canonical scores.  Both are recorders here."""
+    t = 50
+    band = np.zeros(1000, np.int64)
+    band[t] = 131073
+    idx = RankStub(band)
+    ranked = idx._rank_pass
+    calls = []
+
+    def rank_pass(qp, tp, cap, allowed=None):
+        return ranked(qp, tp, cap, allowed)[:4] + (torch.full((len(tp),), x, dtype=torch.float64),)
+
+    def range_search_tensors(q, radius, allowed=None):
+        calls.append(["range", q[:, 0].tolist(), radius, allowed])
+        idx.stats = {"range_results": 4, "range_rounds": 1, "range_cap": 4096, "range_chunked_queries": 0, "rescaled": 0}
+        return torch.tensor([0, 4]), torch.zeros(4), torch.tensor([3, t, 70, 900])
+
+    def score_rows_tensors(q, rows):
+        calls.append(["score", q[:, 0].tolist(), rows.tolist()])
+        X = torch.tensor([[x, x, x, x + 1.0]], dtype=torch.float64)     # row 3 ties below the target, 70 above it; 900 beats it
+        return X.float(), X
+    idx._rank_pass, idx.range_search_tensors, idx.score_rows_tensors = rank_pass, range_search_tensors, score_rows_tensors
+    got = idx.rank_rows_tensors(_queries(1), np.array([t]))
+    assert got.tolist() == [2]
+    assert idx.trace == [["pass", [t], 4096]]
+    assert [c[0] for c in calls] == ["range", "score"] and calls[1] == ["score", [0.0], [[3, t, 70, 900]]]
+    _, qs, r, allowed = calls[0]
+    assert qs == [0.0] and allowed is None
+    assert isinstance(r, np.float32) and np.float64(r) < x <= np.float64(np.nextafter(r, np.float32(np.inf)))
+    assert idx.stats == {"rank_rounds": 1, "rank_cap": 4096, "rank_band_rows": 4096, "rank_above": 0, "rank_fallback_pairs": 1,
+                         "rescaled": 0}
+    assert not [k for k in idx.stats if k.startswith("range_")]

@@ -11,53 +11,14 @@ import pytest
 from oracle import search as OS
 from tests.golden.make_golden import synth_corpus
 from tests.helpers import fill_bytes
+from tests.index_cases import CONFIGS, MASKS, SHAPES, torch_cuda      # noqa: F401 (torch_cuda: the fixture, by name)
+from tests.index_cases import corpus as _corpus, index as _index, mask as _mask, scores as _scores
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = [("fp32", "auto"), ("fp32", "bf16"), ("fp16", "auto")]
-# n, nq, d, clustered
-SHAPES = [
-    (300, 3, 64, False),          # ragged last tile, one K step
-    (257, 1, 100, False),         # padded width (d_in = 100), one query
-    (5000, 37, 768, False),
-    (33000, 130, 128, False),     # more than 128 pairs: Tile256
-    (5000, 37, 768, True),        # a common component of norm ~30 plus unit noise: q . centre matters
-]
-MASKS = ["half", "one", "last_tile", "word_edges", "none"]
 PAD = np.float32(-3.4028234663852886e38)
 
-_CORPUS, _SCORES, _ORDER, _INDEX = {}, {}, {}, {}
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
-
-
-def _corpus(shape):
-    """(P = halves widened to fp32, Q); computed once, never written to afterwards"""
-    if shape not in _CORPUS:
-        n, nq, d, clustered = shape
-        P, Q = synth_corpus(100 + n % 97, n, d), synth_corpus(7, nq, d)
-        if clustered:
-            c = synth_corpus(9, 1, d)
-            c *= np.float32(30.0) / np.linalg.norm(c)
-            P, Q = P + c, Q + c
-        P = P.astype(np.float16).astype(np.float32)
-        P.setflags(write=False), Q.setflags(write=False)
-        _CORPUS[shape] = (P, Q)
-    return _CORPUS[shape]
-
-
-def _scores(shape):
-    if shape not in _SCORES:
-        P, Q = _corpus(shape)
-        S = OS.canonical_scores(Q, P)
-        S.setflags(write=False)
-        _SCORES[shape] = S
-    return _SCORES[shape]
+_ORDER = {}
 
 
 def _order(shape):
@@ -82,21 +43,6 @@ def _oracle_rank(s, t, mask=None):
 def _oracle_ranks(S, rows, mask=None):
     rows2 = rows.reshape(S.shape[0], -1)
     return np.asarray([[_oracle_rank(S[j], int(t), mask) for t in rows2[j]] for j in range(S.shape[0])], np.int64).reshape(rows.shape)
-
-
-def _index(shape, storage, precision):
-    """one resident index per (shape, store, precision); one at a time"""
-    from convdr_amd.search import FlatIPIndex
-    key = (shape, storage, precision)
-    if key not in _INDEX:
-        _INDEX.clear()
-        P, _ = _corpus(shape)
-        idx = FlatIPIndex(shape[2], storage=storage, precision=precision, prepin=False)
-        idx.add(P.astype(np.float16) if storage == "fp16" else P)
-        _INDEX[key] = idx
-    idx = _INDEX[key]
-    idx.cap, idx.RANGE_MAX_CAP = 4096, 131072
-    return idx
 
 
 def _rank(idx, Q, rows, allowed=None):
@@ -259,22 +205,6 @@ def test_all_zero_query_every_score_ties(torch_cuda, storage, precision):
     before = np.concatenate([[0], np.cumsum(mask)])
     np.testing.assert_array_equal(got, np.where(rows >= 0, before[np.maximum(rows, 0)], -1))
     assert mask[rows[rows >= 0]].any() and not mask[rows[rows >= 0]].all()
-
-
-def _mask(n, name):
-    m = np.zeros(n, bool)
-    if name == "half":
-        m = np.random.RandomState(11 + n).rand(n) < 0.5
-    elif name == "one":
-        m[n // 3] = True
-    elif name == "last_tile":
-        assert n % 256
-        m[n // 256 * 256:] = True
-    elif name == "word_edges":
-        m[[31, 32, 63, 64, 255, 256]] = True
-    else:
-        assert name == "none"
-    return m
 
 
 @pytest.mark.parametrize("name", MASKS)

@@ -11,17 +11,11 @@ import pytest
 from oracle import search as OS
 from tests.golden.make_golden import synth_corpus
 from tests.helpers import fill_bytes
+from tests.index_cases import mask as _recipe, torch_cuda      # noqa: F401 (torch_cuda: the fixture, by name)
 
 pytestmark = pytest.mark.gpu
 
 PAD_D, PAD_I = np.float32(-3.4028234663852886e38), -1
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch
 
 
 # n, nq, k, d: the smallest shapes that reach each plan
@@ -65,27 +59,11 @@ def _filtered_oracle(Q, P, k, mask):
 
 def _mask(shape, name):
     n, nq, k, d = shape
-    m = np.zeros(n, bool)
-    if name == "all":
-        m[:] = True
-    elif name == "no_topk":                  # the whole unfiltered top-k of every query removed
-        m[:] = True
+    if name not in ("all", "no_topk"):
+        return _recipe(n, name)
+    m = np.ones(n, bool)
+    if name == "no_topk":                    # the whole unfiltered top-k of every query removed
         m[np.unique(_expected(shape, "all")[1])] = False
-    elif name == "half":
-        m = np.random.RandomState(11 + n).rand(n) < 0.5
-    elif name == "most":
-        m = np.random.RandomState(12 + n).rand(n) < 0.9
-    elif name == "percent":
-        m = np.random.RandomState(13 + n).rand(n) < 0.01
-    elif name == "one":
-        m[n // 3] = True
-    elif name == "last_tile":                # only rows of the last, partial 256-row tile
-        assert n % 256
-        m[n // 256 * 256:] = True
-    elif name == "word_edges":
-        m[[31, 32, 63, 64, 255, 256]] = True
-    else:
-        assert name == "none"
     return m
 
 
