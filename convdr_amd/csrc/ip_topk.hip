@@ -1344,6 +1344,8 @@ static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t s
 #include "ip_rank.hpp"
 // removing rows: stable in-place compaction of the resident buffers (convdr_ip_compact_*)
 #include "ip_compact.hpp"
+// row ids: a hash set of the listed keys, probed by every row of the id column (convdr_keyset_*, convdr_keys_*)
+#include "ip_keys.hpp"
 // judging a run against the qrels: labels, rank measures, negatives (convdr_run_*)
 #include "run_judge.hpp"
 

@@ -42,6 +42,8 @@ _Depth = collections.namedtuple("_Depth", "enqueue max_cap shortcut last_rung la
 # allowed = the RowFilter of a restricted search or None
 _Pending = collections.namedtuple("_Pending", "qt k depth x3 cap first allowed", defaults=(None,))
 
+RESERVED_ID = -(1 << 63)    # INT64_MIN: the free-slot marker of the key set (csrc/ip_keys.hpp), no legal row id
+KEY_ST_LIST, KEY_ST_PROBE, KEY_ST_COLUMN, KEY_ST_NOSET = 1, 2, 4, 8      # status bits of convdr_keyset_build / the row passes
 ROW_FILTER_TILE = 256       # the bitmap covers whole scan tiles of this many rows (csrc/ip_topk.hip: Tile256::TR)
 
 
@@ -245,6 +247,8 @@ class FlatIPIndex:
         self._n = 0
         if not getattr(self, "_reserved", False):
             self._s32 = self._s16 = self._slo = None
+        self._sid = self._sid_spare = None      # the id column and its ping-pong partner (keep_rows): an index has ids or not,
+                                                # from its first add on; a reset forgets that too
         self._centre = None
         self._scale = 1.0                       # power of two applied to the fp16 scan copy (1 for bf16)
         self._max_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -264,7 +268,7 @@ class FlatIPIndex:
 
     def reserve(self, n, lo=None):
         """Backing storage for n passages (fp32 block + 16-bit scan copy, + the remainder copy of the split scan when
-        `lo`, default: only if the precision pins it).  Existing rows are kept."""
+        `lo`, default: only if the precision pins it; + the id column of an index that carries ids).  Existing rows are kept."""
         import torch
         held = {"_s16": self._half_dtype}          # the buffers this index holds: a half store keeps its 16-bit rows and nothing else
         if not self._half:
@@ -280,7 +284,20 @@ class FlatIPIndex:
                     if old is not None and self._n:
                         t[:self._n].copy_(old[:self._n])
                     setattr(self, name, t)
+            if getattr(self, "_sid", None) is not None:
+                self._reserve_ids(rows)
         self._reserved = True
+
+    def _reserve_ids(self, rows, keep=None):
+        """the id column for `rows` rows (the first `keep` entries kept, default ntotal); its ping-pong partner is re-made on
+        its next use"""
+        import torch
+        keep = self._n if keep is None else keep
+        if self._sid is None or self._sid.shape[0] < rows:
+            t = torch.empty(int(rows), dtype=torch.int64, device=self.device)
+            if self._sid is not None and keep:
+                t[:keep].copy_(self._sid[:keep])
+            self._sid, self._sid_spare = t, None
 
     def _prepare_into(self, src32, dst16, dstlo):
         """scan copy (and remainder copy) of the fp32 rows `src32`; folds their norms into the block's max norm"""
@@ -367,13 +384,55 @@ class FlatIPIndex:
         assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
         return t, None
 
-    def add(self, x, chunk_bytes=None):
+    def add(self, x, chunk_bytes=None, ids=None):
         """x: numpy / torch [n, d] float32 (host or device).  Appends to the index.
         A HOST array -- typically the memory-mapped payload of a block file (blocks.BlockView) -- is streamed: chunks of
         ~chunk_bytes (default 64 MB) go through pinned staging buffers, the H2D copy of chunk i + 1 (copy stream) runs under the
         centring / rounding / norm pass of chunk i (convdr_ip_prepare_block*), and the host fills one staging buffer
         (page faults on the mmap = the disk read) while the others are in flight.  The reference does pickle.load (a full
-        host copy of the 14.6 GB block) and a pageable copy (run_convdr_inference.py:164-180)."""
+        host copy of the 14.6 GB block) and a pageable copy (run_convdr_inference.py:164-180).
+
+        ids (FAISS ``add_with_ids``): an int64 vector [n], numpy or torch, host or device -- the rows' ids (``passage_embedding2id``,
+        ``offset2pid``), kept in a device column beside the rows (``idx.ids``) and carried through keep_rows / remove_rows.  Ids
+        need not be distinct: the chunk rows of one document share theirs.  Every add of an index carries ids or none does;
+        a mixed add, a vector of another length or dtype, or the reserved id INT64_MIN raises ValueError and leaves the index
+        as it was (ids on the device cost one host read for that check), and an add the index refuses leaves the column as it
+        was, too."""
+        if ids is None:
+            if self._n and getattr(self, "_sid", None) is not None:
+                raise ValueError("FlatIPIndex.add: this index carries row ids (%d rows), an add without ids= would leave rows "
+                                 "without one; the index is unchanged" % self._n)
+            return self._add_rows(x, chunk_bytes)
+        if self._n and getattr(self, "_sid", None) is None:
+            raise ValueError("FlatIPIndex.add: this index holds %d rows without ids, ids= cannot start now; the index is unchanged"
+                             % self._n)
+        rows = x.array if hasattr(x, "array") else x
+        m = int(rows.shape[0]) if hasattr(rows, "shape") else len(rows)
+        t = self._id_list("add", ids, length=m)
+        n0 = self._n
+        self._add_rows(x, chunk_bytes)                  # (raises: nothing below has touched the column)
+        if m:
+            self._reserve_ids(max(n0 + m, 0 if self._s16 is None else self._s16.shape[0]), keep=n0)
+            self._sid[n0:n0 + m].copy_(t)
+
+    def _id_list(self, who, ids, length=None):
+        """ids of a caller -> device int64 vector, contiguous.  ValueError: not an int64 vector, not `length` entries, or the
+        reserved id INT64_MIN (looked for here only where that costs no more than it does for add: `length` given, or the
+        ids are on the host; the kernels flag it for the others)."""
+        import torch
+        if isinstance(ids, np.ndarray) and not ids.flags.writeable:
+            ids = np.array(ids)                     # (a read-only array -- a memory-mapped id table: as in _source)
+        t = torch.as_tensor(ids)
+        if t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError("%s: ids must be an int64 vector (got %s, shape %s)" % (who, t.dtype, tuple(t.shape)))
+        if length is not None and int(t.numel()) != length:
+            raise ValueError("%s: %d ids for %d rows" % (who, int(t.numel()), length))
+        if (length is not None or t.device.type == "cpu") and t.numel() and bool((t == RESERVED_ID).any()):
+            raise ValueError("%s: the id %d (INT64_MIN) is reserved" % (who, RESERVED_ID))
+        return t.to(self.device).contiguous()
+
+    def _add_rows(self, x, chunk_bytes=None):
+        """add() without the id column"""
         import time
         import torch
         chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
@@ -621,8 +680,10 @@ class FlatIPIndex:
         What stays: the centre and the scale (any centre keeps the search exact, and the scale still fits); ``_max_norm``,
         which remains an UPPER bound of the kept rows' norms -- all the certificate needs, so it is not recomputed; a
         reservation and the backing storage, which is not shrunk: the next ``add`` fills rows [ntotal, ...).
-        What the caller does: filters built for the old ntotal are stale (unless nothing was removed); side tables
-        (offset2pid[embid], the keys of search_distinct) are cut with the same mask, ``keys[keep]``; a first block adopted from
+        The id column of an index that carries ids (add(ids=)) is compacted with the same bitmap and plan: ``idx.ids`` stays in
+        step, nothing is cut by hand.
+        What the caller does: filters built for the old ntotal are stale (unless nothing was removed); side tables the index
+        does not hold (the keys of search_distinct) are cut with the same mask, ``keys[keep]``; a first block adopted from
         the caller's device tensor is modified in place, as by update_rows; a search_begin handle is finished first.
         ``stats``: removed, compact_windows (windows per buffer)."""
         f = self._filter(allowed)
@@ -691,6 +752,190 @@ class FlatIPIndex:
             for t in bufs:
                 _lib.check(L.convdr_ip_compact_rows(ptr(t), int(t.shape[1]) * t.element_size(), n, ptr(f.bits), words, window_rows,
                                                     ptr(ws), ws.numel(), _lib.stream_ptr()), "convdr_ip_compact_rows")
+            if getattr(self, "_sid", None) is not None:
+                # the id column: 8-byte rows, out of place into its partner by the same plan; the two then change roles
+                if self._sid_spare is None or self._sid_spare.shape[0] != self._sid.shape[0]:
+                    self._sid_spare = torch.empty_like(self._sid)
+                _lib.check(L.convdr_ip_compact_ids(ptr(self._sid), ptr(self._sid_spare), n, ptr(f.bits), words, ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr()), "convdr_ip_compact_ids")
+                self._sid, self._sid_spare = self._sid_spare, self._sid
+
+    # -- row ids (FAISS IndexIDMap2): the column add(ids=) fills, and the operations that speak in ids ---------------------
+    # No key -> row table is kept: every call builds a hash set of ITS list on the device (convdr_keyset_build) and all rows
+    # probe it in one pass over the column (convdr_keys_member / convdr_keys_locate; include/convdr_hip.h "Row ids").
+    @property
+    def ids(self):
+        """The rows' ids: device int64 [ntotal], a view of the column; None for an index that never got ids."""
+        sid = getattr(self, "_sid", None)
+        return None if sid is None else sid[:self._n]
+
+    def _need_ids(self, who):
+        if self.ids is None:
+            raise ValueError("%s: this index carries no row ids (give them to add: add(x, ids=...))" % who)
+
+    def _keyset(self, who, t):
+        """convdr_keyset_build of the device int64 list `t` -> (workspace, status int32 [1]); enqueued, no host read"""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        m = int(t.numel())
+        need = int(L.convdr_keyset_workspace_bytes(m))
+        if not need:
+            raise ValueError("%s: %s" % (who, L.convdr_last_error().decode()))
+        ws = getattr(self, "_key_ws", None)
+        if ws is None or ws.numel() < need:
+            self._key_ws = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(L.convdr_keyset_build(ptr(t), m, ptr(ws), ws.numel(), ptr(status), _lib.stream_ptr()), "convdr_keyset_build")
+        return ws, status
+
+    @staticmethod
+    def _key_codes(ws, status):
+        """the two status words (the build's, the row pass's) as device int64 [2], to ride along with the caller's host read"""
+        import torch
+        return torch.cat([status, ws[:4].view(torch.int32)]).to(torch.int64)
+
+    @staticmethod
+    def _key_status(who, code):
+        if code & (KEY_ST_LIST | KEY_ST_COLUMN):
+            raise ValueError("%s: the id %d (INT64_MIN) is reserved; %s holds it" %
+                             (who, RESERVED_ID, "the list" if code & KEY_ST_LIST else "the index's id column"))
+        if code:
+            raise _lib.ConvdrError("%s: the key set reported status %d (2: a probe hit its bound, 8: no set in the workspace)" % (who, code))
+
+    def _member(self, who, ids, invert):
+        """(bitmap of the rows whose id is / is not in `ids`, bits set, distinct listed ids on no row): ONE host read"""
+        import torch
+        self._need_ids(who)
+        t = self._id_list(who, ids)
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        words = (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * 8
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t)
+            bits = torch.empty(words, dtype=torch.int32, device=self.device)
+            counts = torch.empty(2, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_member(ptr(self.ids), n, ptr(ws), ws.numel(), int(bool(invert)), ptr(bits), words, ptr(counts),
+                                            _lib.stream_ptr()), "convdr_keys_member")
+            got = [int(v) for v in torch.cat([counts, self._key_codes(ws, status)]).cpu()]
+        self._key_status(who, got[2] | got[3])
+        return bits, got[0], got[1]
+
+    def remove_ids(self, ids):
+        """FAISS ``IndexIDMap2.remove_ids``: every row whose id is in `ids` (int64 vector, numpy or torch, host or device;
+        repeats allowed) goes -- all chunk rows of a repeated id included --, ids that are on no row are ignored.  Returns the
+        number of rows removed.  The keep bitmap is built on the device and handed to ``keep_rows``, which compacts the rows
+        and the id column; one host read (the kept count, the missing count and the status words together).
+        ``stats``: removed, compact_windows, ids_missing (distinct listed ids found on no row)."""
+        n = self.ntotal
+        bits, kept, missing = self._member("remove_ids", ids, True)
+        removed = self.keep_rows(RowFilter(bits, n, kept))
+        self.stats["ids_missing"] = missing
+        return removed
+
+    def id_filter(self, ids, invert=False):
+        """A RowFilter of the rows whose id is in `ids` (invert: is NOT in it) -- a sub-collection, the judged pool of a topic
+        set -- for ``allowed=`` of the searches and for keep_rows.  Built on the device straight into the bitmap layout of
+        pack_row_mask; one host read (the allowed count), as for row_filter, and the same staleness rule: valid while ntotal
+        stays what it was."""
+        bits, n_allowed, _ = self._member("id_filter", ids, invert)
+        return RowFilter(bits, self.ntotal, n_allowed)
+
+    def _locate(self, who, ids, want_dup=False):
+        import torch
+        self._need_ids(who)
+        t = self._id_list(who, ids)
+        L, ptr = _lib.lib(), _lib.ptr
+        m = int(t.numel())
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t)
+            first = torch.empty(m, dtype=torch.int64, device=self.device)
+            count = torch.empty(m, dtype=torch.int32, device=self.device)
+            dup = torch.empty(m, dtype=torch.int32, device=self.device) if want_dup else None
+            _lib.check(L.convdr_keys_locate(ptr(self.ids), self.ntotal, ptr(ws), ws.numel(), ptr(t), m, ptr(first), ptr(count), ptr(dup),
+                                            _lib.stream_ptr()), "convdr_keys_locate")
+        return t, first, count, dup, ws, status
+
+    def rows_of(self, ids):
+        """Where the ids are: device (first_row int64 [m], count int32 [m]) -- the smallest row holding ids[j] or -1, and the
+        number of rows holding it.  Enqueued, no sync (so a reserved id in a device list is not an error here: it is on no
+        row, -1 and 0)."""
+        _, first, count, _, _, _ = self._locate("rows_of", ids)
+        return first, count
+
+    def reconstruct_ids(self, ids):
+        """FAISS ``IndexIDMap2.reconstruct`` for a list: float32 numpy [m, d_in], the first row of every id (rows_tensors of
+        rows_of).  An id that is on no row raises IndexError."""
+        first, _ = self.rows_of(ids)
+        if first.numel():
+            absent = int((first < 0).sum().item())
+            if absent:
+                raise IndexError("reconstruct_ids: %d of the %d ids are on no row" % (absent, int(first.numel())))
+        return self.rows_tensors(first).cpu().numpy()
+
+    def upsert(self, ids, emb):
+        """Re-encoded passages: `emb` (device fp32 [m, d_in]) replaces the rows of `ids` (int64 [m]).  An id that is on exactly
+        one row gets that row overwritten in place (the scan copies and the max norm refreshed as by update_rows; the half
+        store's update_flags() rule applies); an id on no row is appended, in list order, with its id.  Returns
+        (n_updated, n_added).  A list that repeats an id, or an id that sits on more than one row (chunk rows: which one?),
+        raises ValueError BEFORE anything is written -- one host read, the one that also splits the list."""
+        import torch
+        t, first, count, dup, ws, status = self._locate("upsert", ids, want_dup=True)
+        m = int(t.numel())
+        if not (isinstance(emb, torch.Tensor) and emb.dtype == torch.float32 and emb.device == self.device
+                and tuple(emb.shape) == (m, self.d_in)):
+            raise ValueError("upsert: emb must be a float32 tensor [%d, %d] on %s" % (m, self.d_in, self.device))
+        got = torch.cat([first, count.to(torch.int64), dup.to(torch.int64), self._key_codes(ws, status)]).cpu().numpy()
+        self._key_status("upsert", int(got[3 * m] | got[3 * m + 1]))
+        fr, cnt, dp = got[:m], got[m:2 * m], got[2 * m:3 * m]
+        rep = np.nonzero(dp != np.arange(m))[0]
+        if rep.size:
+            raise ValueError("upsert: the list repeats an id (position %d repeats position %d); nothing was written"
+                             % (int(rep[0]), int(dp[rep[0]])))
+        many = np.nonzero(cnt > 1)[0]
+        if many.size:
+            raise ValueError("upsert: the id at position %d sits on %d rows; nothing was written" % (int(many[0]), int(cnt[many[0]])))
+        upd, new = np.nonzero(cnt == 1)[0], np.nonzero(cnt == 0)[0]
+        emb = emb.contiguous()
+        with torch.cuda.device(self.device):
+            if upd.size:
+                sel = torch.as_tensor(upd, device=self.device)
+                self._overwrite_rows(torch.as_tensor(fr[upd], device=self.device), emb if upd.size == m else emb[sel])
+            if new.size:
+                sel = torch.as_tensor(new, device=self.device)
+                self.add(emb[sel], ids=t[sel])
+        return int(upd.size), int(new.size)
+
+    def _overwrite_rows(self, rows, emb):
+        """update_rows for scattered rows: the scan copies of `emb` are made by the same pass on a contiguous temporary (norms
+        folded into the max norm, the half store's flags into the update word), then every resident buffer takes its rows."""
+        import torch
+        m = int(emb.shape[0])
+        src = (emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))).contiguous()
+        t16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
+        if self._half:
+            self._store_rows(src, t16, self._scale, flags=self._uflags)
+            self._s16.index_copy_(0, rows, t16)
+            return
+        tlo = None if self._slo is None else torch.empty_like(t16)
+        self._prepare_into(src, t16, tlo)
+        self._s32.index_copy_(0, rows, src)
+        self._s16.index_copy_(0, rows, t16)
+        if tlo is not None:
+            self._slo.index_copy_(0, rows, tlo)
+
+    def search_ids(self, q, k, allowed=None):
+        """``search`` with ids for row numbers: numpy (D, ids [nq, k]); FAISS padding stays -1."""
+        D, I = self.search_ids_tensors(q, k, allowed=allowed)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_ids_tensors(self, q, k, allowed=None):
+        """``search_tensors`` with I mapped through the id column on the device (-1 stays -1)."""
+        import torch
+        self._need_ids("search_ids")
+        D, I = self.search_tensors(q, k, allowed=allowed)
+        if not self.ntotal:
+            return D, I
+        return D, torch.where(I >= 0, self.ids[I.clamp(min=0)], torch.full_like(I, -1))
 
     def rows_tensors(self, ids):
         """The corpus rows `ids` (integers, any shape [..]) as a device fp32 tensor [.., d_in]: the fp32 store returns the fp32

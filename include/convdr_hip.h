@@ -328,6 +328,53 @@ int convdr_ip_compact_plan(const uint32_t* keep_bits, int64_t keep_bits_words, i
 int convdr_ip_compact_rows(void* rows, int64_t row_bytes, int64_t n, const uint32_t* keep_bits, int64_t keep_bits_words,
                            int64_t window_rows, void* workspace, size_t workspace_bytes, convdr_stream_t stream);
 
+/* Row ids: which rows of an int64 key column hold a key of a given list, and where (FAISS: IndexIDMap2 -- remove_ids by id, an
+ * IDSelector of ids, reconstruct by id).  No table is kept between calls: convdr_keyset_build makes a hash set of the m listed
+ * keys in the workspace, and a row pass streams the n row keys (8 bytes per row) and probes it.
+ *   the set      open addressing with linear probing; S = the smallest power of two >= max(64, 2 m) slots (load factor <= 1/2);
+ *                home slot of key x = mix(x) & (S - 1) with, on uint64,
+ *                  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31.
+ *                Repeats within the list collapse into one slot, which remembers the smallest list position of its key.
+ *   reserved     INT64_MIN marks a free slot and is no legal key: a list that holds it sets bit 0 of *status, a column that
+ *                holds it bit 2 of the head's status word; such a list entry is in no slot and such a row never hits.
+ *   bounded      every probe loop runs at most S steps; one that ends there sets bit 1 (of *status in the build, of the
+ *                head's status word in a row pass) and leaves.  With at most S / 2 slots taken this cannot happen; the bound
+ *                is what makes a defect a status bit and not a workgroup that spins.
+ *   workspace    convdr_keyset_workspace_bytes(m) bytes (0 outside the contract), 256-byte aligned regions in this order:
+ *                head 256 bytes (u32 word 0: status of the last row pass -- bit 1 probe bound, bit 2 reserved key in the
+ *                column, bit 3 the workspace holds no set that fits workspace_bytes; u32 word 1: log2 S) | slot keys int64 [S] |
+ *                smallest list position u32 [S] | smallest row u32 [S] | row count u32 [S]: 256 + 20 S bytes.
+ *                convdr_keyset_build writes all of it; the row passes reset what they accumulate (the last two regions and
+ *                word 0) themselves, so one build serves any number of them.  They take S from word 1 and refuse (bit 3; the
+ *                outputs are then an all-zero bitmap / (-1, 0, j)) a value whose layout does not fit workspace_bytes.
+ *                Nothing of the workspace is read before these calls wrote it.
+ * convdr_keyset_build   *status (device int32) = 0 | bit 0 | bit 1.  Two launches (one when m == 0).
+ * convdr_keys_member    bits = the row bitmap of convdr_ip_search_filtered / convdr_ip_compact_*: bit (r & 31) of word (r >> 5)
+ *                set iff r < n and ((row_keys[r] is in the set) != (invert != 0)); exactly ceil(n / 256) * 8 words are written,
+ *                whole 256-row tiles, zero past n (invert applies to rows < n only), with plain stores: every wave ballots its
+ *                64 rows into two words.  bits 16-byte aligned, bits_words >= ceil(n / 256) * 8.  counts int64 [2] = (bits
+ *                set, distinct list keys found on no row); integer sums, the same in every run.  Three launches.
+ * convdr_keys_locate    per list position j < m: first_row[j] (int64) = the smallest row holding keys[j] or -1, count[j]
+ *                (int32) = the rows holding it, dup_of[j] (int32, nullable) = the smallest list position with the same key
+ *                (j itself for a key that is not repeated, and for INT64_MIN).  keys / m: the list the set was built from.
+ *                Three launches: reset, rows (atomicMin / atomicAdd per hit), answers.
+ * convdr_ip_compact_ids the id column's share of a removal (convdr_ip_compact_rows moves rows of 16 bytes and more): dst[dest(r)]
+ *                = src[r] for every kept row, stable, OUT OF PLACE (src != dst, dst holds n entries), 8 bytes per row.  Reads
+ *                the tile prefix convdr_ip_compact_plan wrote to plan_workspace for the same n and bitmap; workspace_bytes
+ *                covers the plan's regions.  keep_bits NULL, 0: every row kept (a copy).
+ * 0 <= n < 2^31, 0 <= m <= 2^27; n == 0 and m == 0 are legal and write their outputs (row_keys / keys / bits / the per-position
+ * outputs may then be NULL).  Arguments are validated before anything touches a device: a refusal is a negative code and a
+ * convdr_last_error message; no allocation, no sync. */
+size_t convdr_keyset_workspace_bytes(int64_t m);
+int convdr_keyset_build(const int64_t* keys, int64_t m, void* workspace, size_t workspace_bytes, int32_t* status,
+                        convdr_stream_t stream);
+int convdr_keys_member(const int64_t* row_keys, int64_t n, void* workspace, size_t workspace_bytes, int invert, uint32_t* bits,
+                       int64_t bits_words, int64_t* counts, convdr_stream_t stream);
+int convdr_keys_locate(const int64_t* row_keys, int64_t n, void* workspace, size_t workspace_bytes, const int64_t* keys, int64_t m,
+                       int64_t* first_row, int32_t* count, int32_t* dup_of, convdr_stream_t stream);
+int convdr_ip_compact_ids(const int64_t* src, int64_t* dst, int64_t n, const uint32_t* keep_bits, int64_t keep_bits_words,
+                          const void* plan_workspace, size_t workspace_bytes, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
