@@ -54,6 +54,11 @@ _SIGNATURES = {
     "convdr_keys_member": (C.c_int, [_p, C.c_int64, _p, C.c_size_t, C.c_int, _p, C.c_int64, _p, _p]),
     "convdr_keys_locate": (C.c_int, [_p, C.c_int64, _p, C.c_size_t, _p, C.c_int64, _p, _p, _p, _p]),
     "convdr_ip_compact_ids": (C.c_int, [_p, _p, C.c_int64, _p, C.c_int64, _p, C.c_size_t, _p]),
+    "convdr_keys_rows_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "convdr_keys_rows_count": (C.c_int, [_p, C.c_int64, _p, C.c_size_t, _p, C.c_int64, _p, _p, _p, _p, _p]),
+    "convdr_keys_rows_fill": (C.c_int, [_p, C.c_int64, _p, C.c_size_t, C.c_int64, _p, C.c_int64, _p]),
+    "convdr_ip_score_docs": (C.c_int, [C.c_int, _p, C.c_int, _p, _p, C.c_float, C.c_int64, C.c_int, _p, C.c_int64, _p, _p, C.c_int,
+                                       C.c_int64, _p, _p, _p, _p]),
     "convdr_ip_debug_counts":(_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "convdr_ip_debug_band": (_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
 }

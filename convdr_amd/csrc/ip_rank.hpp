@@ -21,9 +21,29 @@ namespace convdr {
 
 constexpr int IP_RANK_THREADS = 1024;
 
+// The canonical fp64 score of one (query, row) pair, computed by one whole wave and returned on every lane of it: the lane /
+// (j, c) / butterfly order of k_ip_rescore, and its one multiplication by `unscale` for the half store -- the same value bit
+// for bit.  Shared by k_ip_score_rows and k_ip_score_docs (ip_docs.hpp).  The call is wave-uniform.
+template <class PT>
+__device__ __forceinline__ double ip_row_score(const float* __restrict__ qv, const PT* __restrict__ pv, int d, int lane,
+                                               double unscale) {
+  double acc = 0.0;
+  for (int e = lane * 4; e < d; e += 256) {
+    const float4 x = *(const float4*)(qv + e);
+    const f64x4 y = ip_load4_f64<PT>(pv + e);
+    acc = fma((double)x.x, y.x, acc);
+    acc = fma((double)x.y, y.y, acc);
+    acc = fma((double)x.z, y.z, acc);
+    acc = fma((double)x.w, y.w, acc);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if constexpr (sizeof(PT) == 2) acc *= unscale;
+  return acc;
+}
+
 // One wave per (query, row) pair; grid (nq, chunks).  rows / X / D share the pitch ld; the query of pair (q, j) is row q of Q.
-// The lane / (j, c) / butterfly order of k_ip_rescore, and its one multiplication by `unscale` for the half store: the same
-// value bit for bit.  An id outside [0, n) yields the score FAISS pads with and P is not touched for it.
+// An id outside [0, n) yields the score FAISS pads with and P is not touched for it.
 template <class PT>
 __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__ Q, const PT* __restrict__ P, int64_t n, int d,
                                                        const int64_t* __restrict__ rows, int m, int64_t ld,
@@ -33,21 +53,7 @@ __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__
   for (int j = blockIdx.y * 4 + wave; j < m; j += gridDim.y * 4) {
     const int64_t id = rows[(int64_t)q * ld + j];
     double acc = -(double)FLT_MAX;
-    if (id >= 0 && id < n) {        // (wave-uniform)
-      const PT* pv = P + id * d;
-      acc = 0.0;
-      for (int e = lane * 4; e < d; e += 256) {
-        const float4 x = *(const float4*)(qv + e);
-        const f64x4 y = ip_load4_f64<PT>(pv + e);
-        acc = fma((double)x.x, y.x, acc);
-        acc = fma((double)x.y, y.y, acc);
-        acc = fma((double)x.z, y.z, acc);
-        acc = fma((double)x.w, y.w, acc);
-      }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-      if constexpr (sizeof(PT) == 2) acc *= unscale;
-    }
+    if (id >= 0 && id < n) acc = ip_row_score<PT>(qv, P + id * d, d, lane, unscale);        // (wave-uniform)
     if (lane == 0) {
       if (X) X[(int64_t)q * ld + j] = acc;
       if (D) D[(int64_t)q * ld + j] = (float)acc;

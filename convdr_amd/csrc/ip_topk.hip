@@ -1346,6 +1346,8 @@ static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t s
 #include "ip_compact.hpp"
 // row ids: a hash set of the listed keys, probed by every row of the id column (convdr_keyset_*, convdr_keys_*)
 #include "ip_keys.hpp"
+// documents by id: all rows of the listed keys as a CSR, the MaxP score of (query, document) pairs (convdr_keys_rows_*, convdr_ip_score_docs)
+#include "ip_docs.hpp"
 // judging a run against the qrels: labels, rank measures, negatives (convdr_run_*)
 #include "run_judge.hpp"
 

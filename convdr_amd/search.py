@@ -408,8 +408,11 @@ class FlatIPIndex:
                              % self._n)
         rows = x.array if hasattr(x, "array") else x
         m = int(rows.shape[0]) if hasattr(rows, "shape") else len(rows)
-        t = self._id_list("add", ids, length=m)
-        n0 = self._n
+        self._add_keyed(x, chunk_bytes, self._id_list("add", ids, length=m))
+
+    def _add_keyed(self, x, chunk_bytes, t):
+        """the rows `x` and their checked ids `t` (device int64, one per row) behind the resident rows and the column"""
+        n0, m = self._n, int(t.numel())
         self._add_rows(x, chunk_bytes)                  # (raises: nothing below has touched the column)
         if m:
             self._reserve_ids(max(n0 + m, 0 if self._s16 is None else self._s16.shape[0]), keep=n0)
@@ -773,12 +776,13 @@ class FlatIPIndex:
         if self.ids is None:
             raise ValueError("%s: this index carries no row ids (give them to add: add(x, ids=...))" % who)
 
-    def _keyset(self, who, t):
-        """convdr_keyset_build of the device int64 list `t` -> (workspace, status int32 [1]); enqueued, no host read"""
+    def _keyset(self, who, t, need=None):
+        """convdr_keyset_build of the device int64 list `t` -> (workspace, status int32 [1]); enqueued, no host read.
+        need: bytes of a workspace that keeps more behind the set (0: sizes outside that entry's contract)"""
         import torch
         L, ptr = _lib.lib(), _lib.ptr
         m = int(t.numel())
-        need = int(L.convdr_keyset_workspace_bytes(m))
+        need = int(L.convdr_keyset_workspace_bytes(m)) if need is None else need
         if not need:
             raise ValueError("%s: %s" % (who, L.convdr_last_error().decode()))
         ws = getattr(self, "_key_ws", None)
@@ -922,6 +926,168 @@ class FlatIPIndex:
         self._s16.index_copy_(0, rows, t16)
         if tlo is not None:
             self._slo.index_copy_(0, rows, tlo)
+
+    # -- documents by id: a document is EVERY row that carries one id (the chunk rows of a MaxP block share theirs) ----------
+    # Two device primitives (include/convdr_hip.h, "Documents by id"): all rows of the listed ids as a CSR
+    # (convdr_keys_rows_count / convdr_keys_rows_fill) and the MaxP score of (query, document) pairs (convdr_ip_score_docs).
+    def _rows_csr(self, who, t, reserved_ok=False, host=False):
+        """The CSR of the device id list `t` (int64 [m]): (start int64 [m], count int32 [m], rows int64 [total], host) --
+        convdr_keyset_build, convdr_keys_rows_count, ONE host read (total and the status words; with `host` also start, count
+        and dup_of, returned as numpy int64 [3, m]), convdr_keys_rows_fill into a list of exactly `total` entries.
+        reserved_ok: INT64_MIN in the list is padding (on no row), not an error."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        m, n = int(t.numel()), self.ntotal
+        need0 = int(L.convdr_keys_rows_workspace_bytes(m, 0))
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t, need0)
+            start = torch.empty(m, dtype=torch.int64, device=self.device)
+            count = torch.empty(m, dtype=torch.int32, device=self.device)
+            dup = torch.empty(m, dtype=torch.int32, device=self.device) if host else None
+            total = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_rows_count(ptr(self.ids), n, ptr(ws), ws.numel(), ptr(t), m, ptr(start), ptr(count), ptr(dup),
+                                                ptr(total), _lib.stream_ptr()), "convdr_keys_rows_count")
+            parts = [total, self._key_codes(ws, status)]
+            if host:
+                parts += [start, count.to(torch.int64), dup.to(torch.int64)]
+            got = torch.cat(parts).cpu().numpy()
+            code = int(got[1] | got[2])
+            self._key_status(who, code & ~KEY_ST_LIST if reserved_ok else code)
+            tot = int(got[0])
+            need = int(L.convdr_keys_rows_workspace_bytes(m, tot))
+            if ws.numel() < need:
+                # the two lists of the fill lie behind what the count wrote: a larger buffer takes that part over
+                grown = torch.empty(need, dtype=torch.uint8, device=self.device)
+                grown[:need0].copy_(ws[:need0])
+                self._key_ws = ws = grown
+            rows = torch.empty(tot, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_rows_fill(ptr(self.ids), n, ptr(ws), ws.numel(), m, ptr(rows), tot, _lib.stream_ptr()),
+                       "convdr_keys_rows_fill")
+        return start, count, rows, (got[3:].reshape(3, m) if host else None)
+
+    def rows_all(self, ids):
+        """ALL rows of the listed ids (int64 vector, numpy or torch, host or device; repeats allowed): device (start int64 [m],
+        count int32 [m], rows int64 [total]).  The rows that carry ids[j] are rows[start[j] : start[j] + count[j]], ascending;
+        an id on no row has count 0; a repeated id shares the segment of its first occurrence, so total = the rows of the
+        DISTINCT listed ids.  The same bits in every run.  One host read (total, to size `rows`, and the status words; a
+        device list that holds the reserved id INT64_MIN raises ValueError there, as for remove_ids)."""
+        self._need_ids("rows_all")
+        start, count, rows, _ = self._rows_csr("rows_all", self._id_list("rows_all", ids))
+        return start, count, rows
+
+    def score_ids(self, q, ids):
+        """``score_ids_tensors`` as numpy: (D float32, R int64), the shape of `ids`."""
+        D, R = self.score_ids_tensors(q, ids)
+        return D.cpu().numpy(), R.cpu().numpy()
+
+    def score_ids_tensors(self, q, ids):
+        """MaxP score of given documents: ids int64 [nq] (one document per query) or [nq, m], numpy or torch, host or device.
+        Returns device (D float32, R int64) of the shape of `ids`: D = the largest canonical score among the rows that carry
+        the id -- the fp32 rounding of the fp64 score ``search`` ranks by, what ``score_rows`` gives for that row -- and R the
+        row that attains it, the lowest on equal scores.  An id on no row gives the padding pair (-3.4028235e38, -1): that
+        includes INT64_MIN, the natural padding of a device list, and the -1 ``search_ids`` pads with whenever no document has
+        the id -1.  Re-ranking a list of documents (BM25 candidates, a known positive) needs no id -> row map on the host:
+        one key set and one CSR over the flattened list, one score launch, one host read (the CSR's size)."""
+        import torch
+        self._need_ids("score_ids")
+        if isinstance(ids, np.ndarray) and not ids.flags.writeable:
+            ids = np.array(ids)
+        qt, it = torch.as_tensor(q), torch.as_tensor(ids)
+        if qt.dim() != 2 or qt.shape[1] not in (self.d, self.d_in):
+            raise ValueError("score_ids: queries must be [nq, %d] (got shape %s)" % (self.d_in, tuple(qt.shape)))
+        nq = int(qt.shape[0])
+        if it.dtype != torch.int64 or it.dim() not in (1, 2) or int(it.shape[0]) != nq:
+            raise ValueError("score_ids: ids must be int64 [nq] or [nq, m] with nq = %d (got %s, shape %s)"
+                             % (nq, it.dtype, tuple(it.shape)))
+        shape = tuple(it.shape)
+        m = int(it.shape[1]) if it.dim() == 2 else 1
+        qt = self._queries(qt, padded_ok=True)
+        D = torch.empty((nq, m), dtype=torch.float32, device=self.device)
+        R = torch.empty((nq, m), dtype=torch.int64, device=self.device)
+        if nq and m:
+            n = self.ntotal
+            start, count, rows, _ = self._rows_csr("score_ids", it.to(self.device).reshape(-1).contiguous(), reserved_ok=True)
+            store, r32, r16, scale, _ = self._operands(None if n else (None, None))     # (an empty index passes no rows)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().convdr_ip_score_docs(store, _lib.ptr(qt), nq, r32, r16, scale, n, self.d, _lib.ptr(rows),
+                                                           int(rows.numel()), _lib.ptr(start), _lib.ptr(count), m, m, None,
+                                                           _lib.ptr(D), _lib.ptr(R), _lib.stream_ptr()), "convdr_ip_score_docs")
+        return D.reshape(shape), R.reshape(shape)
+
+    def search_docs(self, q, k, allowed=None, depth=None, strict=True, max_depth=None):
+        """Exact top-k DOCUMENTS: ``search_distinct`` with the index's own id column for keys -- no side table to keep in
+        step.  Returns device (D fp32 [nq, k], ids int64 [nq, k], rows int64 [nq, k] = each document's best row, counts int32
+        [nq, 2]); padding (-3.4028235e38, -1, -1).  ``score_ids_tensors(q, ids)`` reproduces D and rows.  allowed: as for
+        ``search``; a filter may drop some chunk rows of a document (its best ALLOWED row then stands for it) or all of them."""
+        self._need_ids("search_docs")
+        D, I, K, counts = self._search_distinct(q, k, self.ids, depth, strict, max_depth, allowed)
+        return D, K, I, counts
+
+    def reconstruct_docs(self, ids):
+        """All chunk rows of the listed documents: numpy (start int64 [m], count int32 [m], emb float32 [total, d_in]) --
+        ``rows_all`` followed by ``rows_tensors``; the rows of ids[j] are emb[start[j] : start[j] + count[j]], in ascending row
+        order.  An id on no row has count 0 (``reconstruct_ids`` raises for it)."""
+        start, count, rows = self.rows_all(ids)
+        return start.cpu().numpy(), count.cpu().numpy(), self.rows_tensors(rows).cpu().numpy()
+
+    def upsert_docs(self, ids, counts, emb):
+        """Re-encoded documents: document ids[j] (int64 [m]) now has counts[j] >= 1 chunk rows (host integers [m]), given in
+        list order in `emb` (device fp32 [sum(counts), d_in]).
+          * a document on no row is appended with its id repeated;
+          * a document that sits on counts[j] rows has them overwritten in place, in ascending row order (``_overwrite_rows``:
+            the scan copies and the max norm refreshed, the half store's update_flags() rule applies);
+          * a document on another number of rows has ALL its old rows removed -- one ``keep_rows`` for all such documents --
+            and its new rows appended, in list order among the appended documents.
+        Returns (n_in_place, n_replaced, n_added) in documents.  A list that repeats an id, or counts / emb of another shape,
+        dtype or device, raises ValueError BEFORE anything is written; one host read (total, status, and what splits the list).
+        Consequences: replaced documents move to the END of the index; and whenever a document was replaced, rows were
+        removed and others added, so a RowFilter built before the call must not be reused even where ntotal happens to come
+        out equal -- the staleness check compares ntotal only.  Side tables in row order are cut as for keep_rows."""
+        import torch
+        self._need_ids("upsert_docs")
+        t = self._id_list("upsert_docs", ids)
+        m = int(t.numel())
+        if isinstance(counts, torch.Tensor):
+            if counts.device.type != "cpu":
+                raise ValueError("upsert_docs: counts must be host integers (got a tensor on %s)" % (counts.device,))
+            counts = counts.numpy()
+        cn = np.asarray(counts)
+        if cn.ndim != 1 or cn.shape[0] != m or cn.dtype.kind not in "iu" or (m and int(cn.min()) < 1):
+            raise ValueError("upsert_docs: counts must be an integer vector [%d] with every entry >= 1 (got %s, shape %s)"
+                             % (m, cn.dtype, tuple(cn.shape)))
+        cn = cn.astype(np.int64)
+        if not (isinstance(emb, torch.Tensor) and emb.dtype == torch.float32 and emb.device == self.device
+                and tuple(emb.shape) == (int(cn.sum()), self.d_in)):
+            raise ValueError("upsert_docs: emb must be a float32 tensor [%d, %d] on %s" % (int(cn.sum()), self.d_in, self.device))
+        if not m:
+            return 0, 0, 0
+        _, _, rows, (st, cur, dp) = self._rows_csr("upsert_docs", t, host=True)
+        rep = np.nonzero(dp != np.arange(m))[0]
+        if rep.size:
+            raise ValueError("upsert_docs: the list repeats an id (position %d repeats position %d); nothing was written"
+                             % (int(rep[0]), int(dp[rep[0]])))
+
+        def spans(first, length):
+            """the concatenation of arange(first[j], first[j] + length[j]), on the device"""
+            begin = np.cumsum(length) - length
+            at = np.repeat(first, length) + (np.arange(int(length.sum()), dtype=np.int64) - np.repeat(begin, length))
+            return torch.as_tensor(at, device=self.device)
+        off = np.cumsum(cn) - cn                                   # first row of document j in emb
+        same, new = cur == cn, cur == 0
+        repl = ~same & ~new
+        emb, n = emb.contiguous(), self.ntotal
+        with torch.cuda.device(self.device):
+            if same.any():
+                self._overwrite_rows(rows[spans(st[same], cn[same])], emb if same.all() else emb[spans(off[same], cn[same])])
+            if repl.any():
+                keep = torch.ones(n, dtype=torch.bool, device=self.device)
+                keep[rows[spans(st[repl], cur[repl])]] = False
+                self.keep_rows(RowFilter(pack_row_mask(keep), n, n - int(cur[repl].sum())))
+            if not same.all():
+                app = ~same
+                who = torch.as_tensor(np.repeat(np.nonzero(app)[0], cn[app]), device=self.device)
+                self._add_keyed(emb[spans(off[app], cn[app])], None, t[who])       # (the list's ids are known clean)
+        return int(same.sum()), int(repl.sum()), int(new.sum())
 
     def search_ids(self, q, k, allowed=None):
         """``search`` with ids for row numbers: numpy (D, ids [nq, k]); FAISS padding stays -1."""
@@ -1204,6 +1370,13 @@ class FlatIPIndex:
         and of the doubling: beyond 4,096 rows the row search is the deep one and the cut convdr_topk_distinct_deep.
         Returns device tensors (D fp32 [nq, k], I int64 [nq, k] rows, K int64 [nq, k] keys, counts int32 [nq, 2] =
         (n_distinct, n_valid) of the pass that produced the row); slots past a query's last key hold (-3.4028235e38, -1, -1)."""
+        return self._search_distinct(q, k, keys, depth, strict, max_depth, None)
+
+    def _search_distinct(self, q, k, keys, depth, strict, max_depth, allowed):
+        """``search_distinct`` with a row filter (``search_docs``).  allowed: a RowFilter or a mask as for ``search``, packed
+        once for all passes, or None.  With a filter the result is the walk over the ALLOWED rows, the filter's ``n_allowed``
+        takes ntotal's place in the depth defaults, and a query is certified iff it found k keys, or the list ran out of rows,
+        or m >= n_allowed.  None: search_distinct as it was."""
         import torch
         qt = torch.as_tensor(q)
         k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
@@ -1213,8 +1386,11 @@ class FlatIPIndex:
         if keys.dtype != torch.int64 or keys.dim() != 1 or keys.device != self.device:
             raise ValueError("search_distinct: keys must be an int64 vector on %s" % (self.device,))
         keys = keys.contiguous()
-        limit = min(max_depth, nt)
-        m = int(depth) if depth else min(max_depth, 2 * k, nt)
+        f = self._filter(allowed)
+        kw = {} if f is None else {"allowed": f}
+        rows = nt if f is None else f.n_allowed          # the rows the search can return
+        limit = min(max_depth, rows)
+        m = int(depth) if depth else min(max_depth, 2 * k, rows)
         m = max(1, min(m, max_depth))
         D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
@@ -1227,7 +1403,7 @@ class FlatIPIndex:
         self.distinct_stats = {"depths": [], "searched": []}
         while True:
             qs = qt if todo is None else qt[todo].contiguous()
-            Dm, Im = self.search_tensors(qs, m)
+            Dm, Im = self.search_tensors(qs, m, **kw)
             Dd, Id, Kd, cd = distinct_topk_device(Dm, Im, k, keys)
             self.distinct_stats["depths"].append(m)
             self.distinct_stats["searched"].append(int(qs.shape[0]))
@@ -1238,7 +1414,7 @@ class FlatIPIndex:
             c = cd.cpu().numpy()                        # the one host round trip of a pass: the certificate
             if (c[:, 0] < 0).any():
                 raise _lib.ConvdrError("search_distinct: keys has %d entries, the block %d rows" % (keys.numel(), nt))
-            open_ = np.nonzero(~((c[:, 0] >= k) | (c[:, 1] < m) | (m >= nt)))[0]
+            open_ = np.nonzero(~((c[:, 0] >= k) | (c[:, 1] < m) | (m >= rows)))[0]
             if not len(open_):
                 return D, I, K, counts
             if m >= limit:

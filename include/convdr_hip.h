@@ -375,6 +375,59 @@ int convdr_keys_locate(const int64_t* row_keys, int64_t n, void* workspace, size
 int convdr_ip_compact_ids(const int64_t* src, int64_t* dst, int64_t n, const uint32_t* keep_bits, int64_t keep_bits_words,
                           const void* plan_workspace, size_t workspace_bytes, convdr_stream_t stream);
 
+/* Documents by id: a DOCUMENT is the set of rows that carry one key (the chunk rows of a MaxP block share theirs).  Two
+ * primitives: every row of every listed key as a CSR, and the MaxP score -- the best row -- of (query, document) pairs.
+ *   the set      convdr_keyset_build of keys[m], into the FRONT of the workspace described below (it needs no more than its
+ *                own convdr_keyset_workspace_bytes(m) and may be given the whole size).  The calls below take m again and
+ *                refuse on the device (bit 3 of the head's status word; start = count = total = 0, rows[] not written) a set
+ *                whose slot count is not the one of m.  Reserved key, probe bound, status words: as under "Row ids".
+ * convdr_keys_rows_count   per list position j < m: start[j] (int64), count[j] (int32), dup_of[j] (int32, nullable); *total
+ *                (device int64).  The rows that hold keys[j] are rows[start[j] : start[j] + count[j]] of the list the fill
+ *                writes.  Segments follow the LIST: the segment of the first occurrence of a key begins where the segments of
+ *                the earlier distinct keys end (an exclusive scan over the owning positions), a repeated key shares the
+ *                segment of its first occurrence, dup_of[j], and *total counts every distinct key's rows once (total <= n).
+ *                A key on no row has count 0 (and the start its segment would have); INT64_MIN has (0, 0, j).
+ *                Six launches: reset, rows (convdr_keys_locate's row pass: atomicAdd per hit), block sums, scan of the block
+ *                sums (one workgroup), starts, answers.  m == 0: *total = 0.
+ * convdr_keys_rows_fill    rows[0 : total] (int64), every segment in ASCENDING row order -- the same bits in every run.  After a
+ *                count with the same workspace, m, column and n.  total > rows_cap: NOTHING is written to rows[] and bit 4 of
+ *                the head's status word is set; re-run with rows_cap >= total (the count need not be repeated).  A second
+ *                pass over the column: every row that hits draws a place in its segment from a per-slot cursor (atomicAdd;
+ *                the order inside a segment is then the order of arrival), into a list of (slot, row) entries; the lists are
+ *                then ordered: every 256-entry chunk of a segment by rank (at most 256 steps per entry), then runs of width
+ *                256, 512, ... merged by binary search in the sibling run (at most 32 steps per entry and pass), one launch
+ *                per width below min(n, rows_cap): a segment of any length comes out sorted, n log^2 n work at worst, every
+ *                loop bounded, no workgroup waits for another.  3 + ceil(log2(min(n, rows_cap) / 256)) launches (one when
+ *                n == 0 or rows_cap == 0); plain vector stores.  For a column other than the count's the result is
+ *                unspecified but every access stays inside the workspace and rows[0 : rows_cap].
+ *   workspace    convdr_keys_rows_workspace_bytes(m, rows_cap) bytes (0 outside the contract: convdr_last_error says why),
+ *                256-byte aligned regions in this order: the key set's regions (256 + 20 S bytes, "Row ids") | head 256 bytes
+ *                (u32 word 0: total) | segment start u32 [S] | cursor u32 [S] | block sums u32 [ceil(m / 256)] | list A
+ *                u64 [rows_cap] | list B u64 [rows_cap] (entry = slot << 32 | row).  The count needs the size for
+ *                rows_cap = 0 and writes head, starts (of the slots in use) and block sums; the fill zeroes the cursors and
+ *                writes the lists.  Nothing is read before these calls wrote it.  convdr_keyset_workspace_bytes is unchanged.
+ * convdr_ip_score_docs     (query q, segment (start[q, j], count[q, j])) for j < m; start (int64), count (int32), X, D and R share
+ *                the pitch ld (>= m).  X[q, j] (fp64, nullable) = the maximum over the segment's rows r = rows[start + i] of the
+ *                canonical score of (q, r): for every row the value convdr_ip_score_rows gives, bit for bit (one device
+ *                function serves both); D[q, j] (fp32, nullable) = (float)X; R[q, j] (int64, nullable) = the row that attains
+ *                it, the LOWEST such row on equal fp64 scores, whatever the order of the list.  The maximum starts below
+ *                every score (the first row is taken unconditionally): all-negative scores are ordinary.  An empty segment,
+ *                one that does not lie inside rows[0 : rows_len], or one whose entries are all outside [0, n) gives
+ *                (-3.4028235e38, -1); an entry outside [0, n) is skipped and never dereferenced.  One wave per pair walks its
+ *                segment; one launch, no workspace.  store / p_f32 / p_half / p_scale as for convdr_ip_score_rows.
+ *                nq, m >= 0, rows_len >= 0, 0 <= n < 2^31, d % 64 == 0, d <= 4096.
+ * 0 <= n < 2^31, 0 <= m <= 2^27, 0 <= rows_cap < 2^31; n == 0 and m == 0 are legal and write their outputs (row_keys / keys /
+ * rows / the per-position outputs may then be NULL).  Arguments are validated before anything touches a device: a refusal is a
+ * negative code and a convdr_last_error message; no allocation, no sync. */
+size_t convdr_keys_rows_workspace_bytes(int64_t m, int64_t rows_cap);
+int convdr_keys_rows_count(const int64_t* row_keys, int64_t n, void* workspace, size_t workspace_bytes, const int64_t* keys, int64_t m,
+                           int64_t* start, int32_t* count, int32_t* dup_of, int64_t* total, convdr_stream_t stream);
+int convdr_keys_rows_fill(const int64_t* row_keys, int64_t n, void* workspace, size_t workspace_bytes, int64_t m, int64_t* rows,
+                          int64_t rows_cap, convdr_stream_t stream);
+int convdr_ip_score_docs(int store, const float* q_f32, int nq, const float* p_f32, const void* p_half, float p_scale, int64_t n,
+                         int d, const int64_t* rows, int64_t rows_len, const int64_t* start, const int32_t* count, int m, int64_t ld,
+                         double* X, float* D, int64_t* R, convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
