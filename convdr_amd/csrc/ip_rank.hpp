@@ -15,6 +15,7 @@
 // a row only needs counting) and S~ < tau_lo PROVES X_r < X_t (such a row is nothing).  Only the rows between the two are
 // listed and re-scored, so the cost follows the width of the error band, not the rank.  A query fails only by OVERFLOW of the
 // band list (re-run with a list as long as the reported band count: same thresholds, cannot overflow again) or by RANGE.
+// convdr_ip_rank_docs (ip_docrank.hpp) runs the same pipeline with the marking scan and its own finish: ip_rank_rows below.
 #pragma once
 
 namespace convdr {
@@ -254,12 +255,40 @@ static int ip_score_rows_launch(const IpBlock& b, const float* q_f32, int nq, co
   return 0;
 }
 
-// The pipeline behind convdr_ip_rank_rows: every check of its arguments, then the launches.  b.store is in range.
-static int ip_rank_rows(const IpBlock& b, const float* q_f32, int np, const int64_t* target, const float* centre, int cap,
-                        void* workspace, size_t workspace_bytes, int64_t* rank, double* X, int64_t* counts, int64_t* above,
-                        int32_t* status, hipStream_t st) {
-  const char* name = "convdr_ip_rank_rows";
-  if (int e = ip_check_sizes(IP_RANK, np, b.n, b.d, 0, cap)) return e;
+// Document rank (ip_docrank.hpp, convdr_ip_rank_docs): the same pipeline with the marking scan and its own finish.
+struct RankDocs {
+  const uint32_t* ord;       // [n] the rows' document ordinals (convdr_doc_ordinals)
+  int64_t ndocs;
+};
+constexpr IpDepth IP_RANK_DOCS = {"convdr_ip_rank_docs", 1024, 131072, false};
+static inline int64_t docrank_mark_words(int64_t ndocs) { return ceil_div64(ndocs, 32 * 32) * 32; }   // whole 128-byte lines
+static inline size_t docrank_mark_bytes(int np, int64_t ndocs) { return align_up((size_t)np * docrank_mark_words(ndocs) * 4, 256); }
+struct DocRankFinish {       // what the two finishing launches read and write (ip_docrank.hpp)
+  int np, cap;
+  int64_t n;
+  const uint32_t *hits, *above_u, *bad, *list_id;
+  const double* list_x;
+  const int64_t* target;
+  const double* xt;
+  const float *qnorm, *p_max_norm;
+  float p_scale, norm_limit;
+  const uint32_t* ord;
+  int64_t ndocs, mark_words;
+  uint32_t* marks;
+  int64_t *rank, *counts, *above;
+  int32_t* status;
+};
+static int ip_docrank_finish(const DocRankFinish& f, hipStream_t st);
+
+// The pipeline behind convdr_ip_rank_rows (depth = IP_RANK, docs = NULL) and convdr_ip_rank_docs (IP_RANK_DOCS, the ordinals):
+// every check of its arguments, then the launches.  b.store is in range.
+static int ip_rank_rows(const IpDepth& depth, const IpBlock& b, const float* q_f32, int np, const int64_t* target, const float* centre,
+                        int cap, void* workspace, size_t workspace_bytes, int64_t* rank, double* X, int64_t* counts, int64_t* above,
+                        int32_t* status, const RankDocs* docs, hipStream_t st) {
+  const char* name = depth.entry;
+  if (int e = ip_check_sizes(depth, np, b.n, b.d, 0, cap)) return e;
+  CONVDR_REQUIRE(!docs || (docs->ndocs >= 0 && docs->ndocs <= b.n), "%s: ndocs=%lld outside [0, n=%lld]", name,
+                 docs ? (long long)docs->ndocs : 0ll, (long long)b.n);
   CONVDR_REQUIRE(!b.rows_f16() || centre == nullptr, "%s: the half store has no centre", name);
   CONVDR_REQUIRE(b.row_bits != nullptr || b.row_bits_words == 0, "%s: row_bits is NULL but row_bits_words=%lld", name,
                  (long long)b.row_bits_words);
@@ -267,9 +296,11 @@ static int ip_rank_rows(const IpBlock& b, const float* q_f32, int np, const int6
                  (long long)b.n_allowed, (long long)b.n);
   if (int e = ip_check_block(name, b)) return e;
   const IpRankPlan p = ip_rank_plan(np, b.n, b.d, cap);
-  if (int e = ip_check_workspace(name, workspace_bytes, p.total)) return e;
+  const size_t mark_bytes = docs ? docrank_mark_bytes(np, docs->ndocs) : 0;       // the bitmap follows the rank plan's regions
+  if (int e = ip_check_workspace(name, workspace_bytes, p.total + mark_bytes)) return e;
   CONVDR_REQUIRE(q_f32 && target && workspace && rank && X && counts && above && status,
                  "%s: a NULL argument (q_f32, target, workspace, rank, X, counts, above, status)", name);
+  CONVDR_REQUIRE(!docs || docs->ord || b.n == 0, "%s: ord is NULL (the rows' document ordinals: convdr_doc_ordinals)", name);
   CONVDR_REQUIRE(b.n == 0 || (b.p_half && b.p_max_norm && (b.rows_f16() || b.p_f32)),
                  "%s: a NULL block pointer (p_half, p_max_norm; p_f32 unless store = 2)", name);
   char* ws = (char*)workspace;
@@ -292,11 +323,19 @@ static int ip_rank_rows(const IpBlock& b, const float* q_f32, int np, const int6
                      b.scan_scale(), b.eps_coef(), b.eps_abs(), b.kind() == IP_KIND_F16 ? 1 : 0, tau_lo, tau_hi, bad);
   CONVDR_CHECK_LAUNCH("k_ip_band_tau");
   const bool scan = b.n > 0 && !(b.row_bits && b.n_allowed == 0);     // (no allowed row: nothing precedes any target)
+  uint32_t* marks = (uint32_t*)(ws + p.total);
+  const int64_t mark_words = docs ? docrank_mark_words(docs->ndocs) : 0;
+  if (mark_bytes) CONVDR_CHECK_HIP(hipMemsetAsync(marks, 0, mark_bytes, st));       // zeroed in the call, on the stream
   if (scan) {
     ScanArgs a = ip_scan_args(b, p, ws, np, cap, nullptr, nullptr);
     a.tau_hi = tau_hi;
     a.above = above_u;
-    if (int e = launch_scan_band(a, p.big, b.kind(), st)) return e;
+    if (docs) {
+      a.ord = docs->ord;  a.ndocs = docs->ndocs;  a.marks = marks;  a.mark_words = mark_words;
+      if (int e = launch_scan_mark(a, p.big, b.kind(), st)) return e;
+    } else {
+      if (int e = launch_scan_band(a, p.big, b.kind(), st)) return e;
+    }
   }
   hipLaunchKernelGGL(k_ip_range_clamp, dim3((np + 255) / 256), dim3(256), 0, st, hits, np, cap, m);
   CONVDR_CHECK_LAUNCH("k_ip_range_clamp");
@@ -304,7 +343,12 @@ static int ip_rank_rows(const IpBlock& b, const float* q_f32, int np, const int6
     ProfScope prof("ip_rank_rescore", st);
     if (int e = ip_rescore(b, q_f32, np, np < 64 ? 128 : 16, cap, m, list_id, list_x, st)) return e;
   }
-  {
+  if (docs) {
+    ProfScope prof("ip_docrank_finish", st);
+    const DocRankFinish f = {np, cap, b.n, hits, above_u, bad, list_id, list_x, target, X, qnorm, b.p_max_norm, b.scan_scale(),
+                             b.norm_limit(), docs->ord, docs->ndocs, mark_words, marks, rank, counts, above, status};
+    if (int e = ip_docrank_finish(f, st)) return e;
+  } else {
     ProfScope prof("ip_rank_finish", st);
     hipLaunchKernelGGL(k_ip_rank_finish, dim3(np), dim3(IP_RANK_THREADS), 0, st, cap, b.n, hits, above_u, bad, list_id, list_x, target,
                        X, qnorm, b.p_max_norm, b.scan_scale(), b.norm_limit(), rank, counts, above, status);
@@ -351,6 +395,6 @@ extern "C" int convdr_ip_rank_rows(int store, const float* q_f32, int np, const 
   // (one pass: no remainder copy)
   const IpBlock b = {store, p_f32, p_half, nullptr, store == 0 ? 1.f : p_scale, false, n, d, p_max_norm, row_bits, row_bits_words,
                      row_bits ? n_allowed : n};
-  return ip_rank_rows(b, q_f32, np, target, centre, cap, workspace, workspace_bytes, rank, X, counts, above, status,
+  return ip_rank_rows(IP_RANK, b, q_f32, np, target, centre, cap, workspace, workspace_bytes, rank, X, counts, above, status, nullptr,
                       (hipStream_t)stream);
 }

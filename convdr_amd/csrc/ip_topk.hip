@@ -25,7 +25,7 @@
 
 namespace convdr {
 
-constexpr int IP_MODE_FULL = 0, IP_MODE_TOP2 = 1, IP_MODE_EMIT = 2, IP_MODE_BAND = 3;
+constexpr int IP_MODE_FULL = 0, IP_MODE_TOP2 = 1, IP_MODE_EMIT = 2, IP_MODE_BAND = 3, IP_MODE_MARK = 4;
 constexpr int IP_FULL_MAX_N = 32768;      // <= this many passages: "sample" = all scores, exact rank select
 constexpr int IP_SAMPLE_MIN = 32768;      // sampled passages (>= 1/32 of the block)
 constexpr int IP_SAMPLE_MAX = 262144;
@@ -280,6 +280,10 @@ struct ScanArgs {
                          // zero bits to whole TR-row tiles, word 0 = row 0 of P (a sub-block's pointer advances with its P)
   const float* tau_hi;   // BAND: [nq_pad], tau <= tau_hi: rows with S~ >= tau_hi are counted, not listed (tau is the band's lower end)
   uint32_t* above;       // BAND: [nq_pad * IP_COUNT_STRIDE], the count of query q at q * IP_COUNT_STRIDE, like counts
+  const uint32_t* ord;   // MARK: [n], the dense document number of every row (convdr_doc_ordinals); >= ndocs: no document
+  uint32_t* marks;       // MARK: [nq, mark_words], one bit per document and query: some row of it scored S~ >= tau_hi
+  int64_t mark_words;    // MARK: words of one query's bitmap (>= ceil(ndocs / 32))
+  int64_t ndocs;
 };
 
 // The row filter in the scan epilogues.  A wave's accumulator tile mt covers the 32 rows (wr * MT + mt) * 32 .. + 31 of the
@@ -323,9 +327,10 @@ template <int MODE, class T, bool FILT>
 __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc, const WavePos<T>& w, int ts, int64_t m0,
                                               int64_t n0, const float (&tau_lane)[T::NT], const uint32_t (&fw)[T::MT],
                                               const float (&tau_hi_lane)[T::NT]) {   // (tau_hi_lane: BAND only)
-  constexpr bool LISTS = MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND;
+  constexpr bool MARK = MODE == IP_MODE_MARK;     // BAND plus one bit per document with a row above tau_hi (ip_docrank.hpp)
+  constexpr bool LISTS = MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND || MARK;
   if constexpr (FILT) filter_acc<T>(acc, fw, w, a.n - m0, LISTS ? IP_MASKED_EMIT : IP_MASKED_SAMPLE);
-  if constexpr (MODE == IP_MODE_BAND) {
+  if constexpr (MODE == IP_MODE_BAND || MARK) {
     // Two thresholds per query column, tau <= tau_hi.  S~ >= tau_hi: the row is COUNTED into the query's "above" counter and
     // nothing else -- no slot, no id.  tau <= S~ < tau_hi: the row is listed exactly as EMIT lists it (one returning atomic per
     // lane reserves the slots, the hits are written once it has retired, the hit counter counts past cap).  A masked score is
@@ -345,6 +350,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
             if (w.r_index(mt, r) >= rows_left) acc.c[mt][nt][r] = -INFINITY;
     }
     uint32_t cnt[T::NT], slot[T::NT];
+    uint32_t mine_above[MARK ? T::NT : 1] = {};      // MARK: this lane's own share of the above count, per query column
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) {
       uint32_t c = 0, ca = 0;
@@ -356,6 +362,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
           ca += acc.c[mt][nt][r] >= tau_hi_lane[nt] ? 1u : 0u;
         }
       cnt[nt] = c - ca;          // (tau <= tau_hi: every row counted above also passed tau)
+      if constexpr (MARK) mine_above[nt] = ca;
       const uint32_t pair = ca + (uint32_t)__shfl_xor((int)ca, 32, 64);
       const int q = (int)n0 + w.l_index(nt);
       if (w.hi == 0 && pair) __hip_atomic_fetch_add(&a.above[(int64_t)q * IP_COUNT_STRIDE], pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -387,6 +394,36 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
               sc[sl] = v[r];
             }
             ++sl;
+          }
+        }
+      }
+    }
+    if constexpr (MARK) {
+      // The rows above tau_hi precede the target for certain: each ORs the bit of its DOCUMENT into the query's bitmap -- no
+      // slot, no id, no re-score.  One dependent load (the row's ordinal) and one non-returning atomic per such row; lanes
+      // that counted none skip the walk.  Nothing is stored for a row past the block's end, an ordinal that names no
+      // document or a padding query column, whatever the thresholds are.  An OR is idempotent and commutative: the bitmap
+      // is the same in every run.  No LDS (the R3 main loop owns all of it).
+#pragma unroll
+      for (int nt = 0; nt < T::NT; ++nt) {
+        if (mine_above[nt] == 0) continue;
+        const int q = (int)n0 + w.l_index(nt);
+        if (q >= a.nq) continue;
+        const float tau_hi = tau_hi_lane[nt];
+        uint32_t* mk = a.marks + (int64_t)q * a.mark_words;
+#pragma unroll
+        for (int mt = 0; mt < T::MT; ++mt) {
+          const f32x16 v = acc.c[mt][nt];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            if (v[r] >= tau_hi) {
+              const int64_t row = m0 + w.r_index(mt, r);
+              if (row < a.n) {
+                const uint32_t o = a.ord[row];
+                if ((int64_t)o < a.ndocs && (int64_t)(o >> 5) < a.mark_words)
+                  __hip_atomic_fetch_or(&mk[o >> 5], 1u << (o & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              }
+            }
           }
         }
       }
@@ -496,7 +533,7 @@ __device__ __forceinline__ void scan_epilogue(const ScanArgs& a, GemmAcc<T>& acc
 // instruction for instruction the kernels they were before the filter existed.
 template <int MODE, class T, int PASSES, bool F16, bool FILT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan(const ScanArgs a) {
-  static_assert(MODE != IP_MODE_BAND, "the band-count scan is single pass: k_ip_scan_r3<..., IP_MODE_BAND>");
+  static_assert(MODE != IP_MODE_BAND && MODE != IP_MODE_MARK, "the band-count scan is single pass: k_ip_scan_r3<..., IP_MODE_BAND>");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t ntiles = (uint32_t)a.nPt * (uint32_t)a.nQt;
   const uint32_t xcd = blockIdx.x & 7u, q8 = ntiles >> 3, r8 = ntiles & 7u;
@@ -706,11 +743,12 @@ __device__ __forceinline__ void scan_emit_flush(const ScanArgs& a, const WavePos
 // sampling modes stay on the two-stage loop.)
 // MODE: IP_MODE_EMIT (the default: every caller before the band-count scan), or IP_MODE_BAND -- the same walk with
 // scan_epilogue<IP_MODE_BAND> in the place of capture / flush: the band's slots are reserved and waited for in the epilogue
-// (the list holds the few rows in doubt; the rows above are counted, not listed), and tau_hi travels with tau.
+// (the list holds the few rows in doubt; the rows above are counted, not listed), and tau_hi travels with tau.  IP_MODE_MARK
+// is BAND with scan_epilogue<IP_MODE_MARK>: the rows above also mark their document (document rank, ip_docrank.hpp).
 template <class T, bool F16, bool FILT, int MODE = IP_MODE_EMIT>
 __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) {
-  static_assert(MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND, "the R3 scan lists: EMIT or BAND");
-  constexpr bool BAND = MODE == IP_MODE_BAND;
+  static_assert(MODE == IP_MODE_EMIT || MODE == IP_MODE_BAND || MODE == IP_MODE_MARK, "the R3 scan lists: EMIT, BAND or MARK");
+  constexpr bool BAND = MODE == IP_MODE_BAND || MODE == IP_MODE_MARK;      // two thresholds, the epilogue of the band
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // the 256 x 128 tile serves scans with ONE query tile (at most 128 queries): every passage chunk is read exactly once,
   // so its DMA is non-temporal -- the block streams past L2 instead of through it
@@ -797,7 +835,7 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
       src = TileSrcAll<T>(a.P, a.d, a.n, a.Qb, a.d, a.nq_pad, m0, n0, w);
       gemm_r3_prologue<T, P_AUX>(src, a.d, smem, w, slots);
     }
-    if constexpr (BAND) scan_epilogue<IP_MODE_BAND, T, FILT>(a, acc, we, 0, m0_cur, n0_cur, tau_lane, fw, tau_hi_lane);
+    if constexpr (BAND) scan_epilogue<MODE, T, FILT>(a, acc, we, 0, m0_cur, n0_cur, tau_lane, fw, tau_hi_lane);
     else scan_emit_capture<T, FILT>(a, acc, we, m0_cur, n0_cur, tau_lane, pend, fw);
     if (!has_next) break;
     idx = next;
@@ -1308,28 +1346,41 @@ static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) { 
 
 // The band-count scan (IP_MODE_BAND): the single-pass shapes of launch_scan<IP_MODE_EMIT> -- both tiles, both kinds (the half
 // store scans with the fp16 kernels), with and without the row filter -- on the R3 kernel.  There is no split BAND scan.
-template <class T, bool F16, bool FILT>
+// MODE: IP_MODE_BAND, or IP_MODE_MARK -- the same eight shapes with the marking epilogue (launch_scan_mark).
+template <class T, bool F16, bool FILT, int MODE>
 static int launch_band_x(const ScanArgs& a, hipStream_t st) {
   constexpr int R3_SMEM = 3 * T::R_BYTES + 2 * T::L_BYTES;
   static DeviceOnce attr3;
   if (attr3.first())
-    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16, FILT, IP_MODE_BAND>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_scan_r3<T, F16, FILT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          R3_SMEM));
   const unsigned tiles = (unsigned)a.nPt * (unsigned)a.nQt;
-  ProfScope prof("ip_scan_band", st);
-  hipLaunchKernelGGL((k_ip_scan_r3<T, F16, FILT, IP_MODE_BAND>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS),
+  ProfScope prof(MODE == IP_MODE_MARK ? "ip_scan_mark" : "ip_scan_band", st);
+  hipLaunchKernelGGL((k_ip_scan_r3<T, F16, FILT, MODE>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS),
                      R3_SMEM, st, a);
-  CONVDR_CHECK_LAUNCH("k_ip_scan_r3<BAND>");
+  if constexpr (MODE == IP_MODE_MARK) CONVDR_CHECK_LAUNCH("k_ip_scan_r3<MARK>");
+  else CONVDR_CHECK_LAUNCH("k_ip_scan_r3<BAND>");
   return 0;
 }
-template <bool F16, bool FILT>
+template <bool F16, bool FILT, int MODE>
 static int launch_band_k(const ScanArgs& a, int tile, hipStream_t st) {
-  return tile == IP_TILE_256 ? launch_band_x<Tile256, F16, FILT>(a, st) : launch_band_x<TileTall, F16, FILT>(a, st);
+  return tile == IP_TILE_256 ? launch_band_x<Tile256, F16, FILT, MODE>(a, st) : launch_band_x<TileTall, F16, FILT, MODE>(a, st);
 }
-static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t st) {   // a.bits selects the filtered kernels
+template <int MODE>
+static int launch_band_m(const ScanArgs& a, int tile, int kind, hipStream_t st) {   // a.bits selects the filtered kernels
+  if (kind == IP_KIND_F16) return a.bits ? launch_band_k<true, true, MODE>(a, tile, st) : launch_band_k<true, false, MODE>(a, tile, st);
+  return a.bits ? launch_band_k<false, true, MODE>(a, tile, st) : launch_band_k<false, false, MODE>(a, tile, st);
+}
+static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t st) {
   CONVDR_REQUIRE(!a.two_pass && !a.Plo && a.tau_hi && a.above, "band scan: one pass, tau_hi and above set");
-  if (kind == IP_KIND_F16) return a.bits ? launch_band_k<true, true>(a, tile, st) : launch_band_k<true, false>(a, tile, st);
-  return a.bits ? launch_band_k<false, true>(a, tile, st) : launch_band_k<false, false>(a, tile, st);
+  return launch_band_m<IP_MODE_BAND>(a, tile, kind, st);
+}
+// The marking scan (IP_MODE_MARK): the band scan whose rows above tau_hi also OR their document's bit into a.marks.
+static int launch_scan_mark(const ScanArgs& a, int tile, int kind, hipStream_t st) {
+  CONVDR_REQUIRE(!a.two_pass && !a.Plo && a.tau_hi && a.above, "mark scan: one pass, tau_hi and above set");
+  CONVDR_REQUIRE(a.ord && a.ndocs >= 0 && a.ndocs <= a.n && a.mark_words * 32 >= a.ndocs && (a.marks || a.ndocs == 0),
+                 "mark scan: ord, marks and mark_words must cover ndocs=%lld documents", (long long)a.ndocs);
+  return launch_band_m<IP_MODE_MARK>(a, tile, kind, st);
 }
 
 }  // namespace convdr
@@ -1348,6 +1399,8 @@ static int launch_scan_band(const ScanArgs& a, int tile, int kind, hipStream_t s
 #include "ip_keys.hpp"
 // documents by id: all rows of the listed keys as a CSR, the MaxP score of (query, document) pairs (convdr_keys_rows_*, convdr_ip_score_docs)
 #include "ip_docs.hpp"
+// document rank: dense document numbers of the id column, the marking band scan's finish (convdr_doc_ordinals, convdr_ip_rank_docs)
+#include "ip_docrank.hpp"
 // judging a run against the qrels: labels, rank measures, negatives (convdr_run_*)
 #include "run_judge.hpp"
 

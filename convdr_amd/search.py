@@ -92,6 +92,16 @@ class RowFilter:
         return self._rows
 
 
+class DocOrdinals:
+    """Dense document numbers of an index's id column (FlatIPIndex.doc_ordinals): `ord` the device vector [ntotal] (int32
+    words, the bytes of uint32: ord[r] = the number of distinct ids whose first row lies below the first row of ids[r]),
+    `ndocs` the distinct ids, `n` the ntotal it was built for -- ranking with it on an index of another size raises ValueError.
+    Query independent: build once, pass as ``ordinals=`` to rank_ids / rank_ids_tensors."""
+
+    def __init__(self, ord, ndocs, n):
+        self.ord, self.ndocs, self.n = ord, int(ndocs), int(n)
+
+
 class FlatIPIndex:
     """Exact inner-product index resident in HBM.  ``add`` keeps the fp32 block and builds its 16-bit scan copy;
     ``search`` returns FAISS-shaped ``(D float32 [nq,k], I int64 [nq,k])`` and is certified exact
@@ -975,6 +985,21 @@ class FlatIPIndex:
         start, count, rows, _ = self._rows_csr("rows_all", self._id_list("rows_all", ids))
         return start, count, rows
 
+    def _ids_arg(self, who, q, ids):
+        """(queries as a tensor, ids as a tensor, the shape of `ids`) of a (queries, document ids) call; the checks that need
+        no device"""
+        import torch
+        if isinstance(ids, np.ndarray) and not ids.flags.writeable:
+            ids = np.array(ids)
+        qt, it = torch.as_tensor(q), torch.as_tensor(ids)
+        if qt.dim() != 2 or qt.shape[1] not in (self.d, self.d_in):
+            raise ValueError("%s: queries must be [nq, %d] (got shape %s)" % (who, self.d_in, tuple(qt.shape)))
+        nq = int(qt.shape[0])
+        if it.dtype != torch.int64 or it.dim() not in (1, 2) or int(it.shape[0]) != nq:
+            raise ValueError("%s: ids must be int64 [nq] or [nq, m] with nq = %d (got %s, shape %s)"
+                             % (who, nq, it.dtype, tuple(it.shape)))
+        return qt, it, tuple(it.shape)
+
     def score_ids(self, q, ids):
         """``score_ids_tensors`` as numpy: (D float32, R int64), the shape of `ids`."""
         D, R = self.score_ids_tensors(q, ids)
@@ -990,17 +1015,8 @@ class FlatIPIndex:
         one key set and one CSR over the flattened list, one score launch, one host read (the CSR's size)."""
         import torch
         self._need_ids("score_ids")
-        if isinstance(ids, np.ndarray) and not ids.flags.writeable:
-            ids = np.array(ids)
-        qt, it = torch.as_tensor(q), torch.as_tensor(ids)
-        if qt.dim() != 2 or qt.shape[1] not in (self.d, self.d_in):
-            raise ValueError("score_ids: queries must be [nq, %d] (got shape %s)" % (self.d_in, tuple(qt.shape)))
-        nq = int(qt.shape[0])
-        if it.dtype != torch.int64 or it.dim() not in (1, 2) or int(it.shape[0]) != nq:
-            raise ValueError("score_ids: ids must be int64 [nq] or [nq, m] with nq = %d (got %s, shape %s)"
-                             % (nq, it.dtype, tuple(it.shape)))
-        shape = tuple(it.shape)
-        m = int(it.shape[1]) if it.dim() == 2 else 1
+        qt, it, shape = self._ids_arg("score_ids", q, ids)
+        nq, m = int(qt.shape[0]), (shape[1] if len(shape) == 2 else 1)
         qt = self._queries(qt, padded_ok=True)
         D = torch.empty((nq, m), dtype=torch.float32, device=self.device)
         R = torch.empty((nq, m), dtype=torch.int64, device=self.device)
@@ -1013,6 +1029,43 @@ class FlatIPIndex:
                                                            int(rows.numel()), _lib.ptr(start), _lib.ptr(count), m, m, None,
                                                            _lib.ptr(D), _lib.ptr(R), _lib.stream_ptr()), "convdr_ip_score_docs")
         return D.reshape(shape), R.reshape(shape)
+
+    def doc_ordinals(self):
+        """The DocOrdinals of this index: every row's dense document number (convdr_doc_ordinals; include/convdr_hip.h,
+        "Document rank"), 0 .. ndocs - 1 in the order of the documents' first rows -- what numpy gives as
+        ``argsort(argsort(first))[inv]`` of ``np.unique(ids, return_index=True, return_inverse=True)``, the same bits in every
+        run.  Query independent: one pass over the id column, ONE host read (ndocs together with the status words).  Valid while
+        the column stays as it was; ntotal is what is checked (a stale one raises ValueError in rank_ids).  As for a RowFilter,
+        ``upsert_docs`` of documents whose chunk count changed moves rows without changing ntotal: rebuild after it."""
+        import torch
+        self._need_ids("doc_ordinals")
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        need = int(L.convdr_doc_ordinals_workspace_bytes(n))
+        if not need:
+            raise ValueError("doc_ordinals: %s" % L.convdr_last_error().decode())
+        with torch.cuda.device(self.device):
+            ws = getattr(self, "_key_ws", None)
+            if ws is None or ws.numel() < need:
+                self._key_ws = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ord_ = torch.empty(n, dtype=torch.int32, device=self.device)
+            nd = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_doc_ordinals(ptr(self.ids), n, ptr(ws), ws.numel(), ptr(ord_), ptr(nd), _lib.stream_ptr()),
+                       "convdr_doc_ordinals")
+            got = [int(v) for v in torch.cat([nd, ws[:4].view(torch.int32).to(torch.int64)]).cpu()]     # the one host read
+        self._key_status("doc_ordinals", got[1])
+        return DocOrdinals(ord_, got[0], n)
+
+    def _ordinals(self, ordinals):
+        """ordinals= of a rank_ids call -> None or a DocOrdinals that fits this index"""
+        if ordinals is None:
+            return None
+        if not isinstance(ordinals, DocOrdinals):
+            raise ValueError("ordinals must be a DocOrdinals of this index (FlatIPIndex.doc_ordinals)")
+        if ordinals.n != self.ntotal or ordinals.ord.device != self.device:
+            raise ValueError("stale DocOrdinals: built for ntotal = %d on %s, the index holds %d rows on %s"
+                             % (ordinals.n, ordinals.ord.device, self.ntotal, self.device))
+        return ordinals
 
     def search_docs(self, q, k, allowed=None, depth=None, strict=True, max_depth=None):
         """Exact top-k DOCUMENTS: ``search_distinct`` with the index's own id column for keys -- no side table to keep in
@@ -1879,13 +1932,26 @@ class FlatIPIndex:
     def _rank_pass(self, qp, tp, cap, allowed=None):
         """One pass of convdr_ip_rank_rows over the resident block: (rank, band counts, above, status) numpy [np] and the
         targets' fp64 scores (device).  One host read per call."""
+        return self._rank_entry_pass(qp, tp, cap, allowed, None)
+
+    def _rank_docs_pass(self, qp, tp, cap, ordinals, allowed=None):
+        """One pass of convdr_ip_rank_docs: as _rank_pass, `rank` counting documents and `above` the rows the scan marked."""
+        return self._rank_entry_pass(qp, tp, cap, allowed, ordinals)
+
+    def _rank_entry_pass(self, qp, tp, cap, allowed, ordinals):
+        """convdr_ip_rank_rows (ordinals None) or convdr_ip_rank_docs over the resident block"""
         import torch
         L, ptr = _lib.lib(), _lib.ptr
         npairs, n = int(qp.shape[0]), self.ntotal
+        who = "convdr_ip_rank_rows" if ordinals is None else "convdr_ip_rank_docs"
+        if ordinals is None:
+            ws_bytes = lambda c: L.convdr_ip_rank_workspace_bytes(c, n, self.d, cap)
+        else:
+            ws_bytes = lambda c: L.convdr_ip_rank_docs_workspace_bytes(c, n, self.d, cap, ordinals.ndocs)
         # pairs per call, so that one call's workspace stays under DEEP_WS_BYTES (as _range_pass)
-        step, need = split_under(lambda c: L.convdr_ip_rank_workspace_bytes(c, n, self.d, cap), npairs, self.DEEP_WS_BYTES)
+        step, need = split_under(ws_bytes, npairs, self.DEEP_WS_BYTES)
         if not need:
-            raise _lib.ConvdrError("convdr_ip_rank_rows: sizes outside the contract (np=%d n=%d d=%d cap=%d)" % (npairs, n, self.d, cap))
+            raise _lib.ConvdrError("%s: sizes outside the contract (np=%d n=%d d=%d cap=%d)" % (who, npairs, n, self.d, cap))
         ws = self._workspace(need)
         store, r32, r16, scale, centre = self._operands()
         bits = None if allowed is None else allowed.bits
@@ -1896,13 +1962,99 @@ class FlatIPIndex:
                 b = min(npairs, a + step)
                 c = b - a
                 out = torch.empty(4 * c, dtype=torch.int64, device=self.device)      # rank | counts | above | status (int32)
-                _lib.check(L.convdr_ip_rank_rows(
-                    store, ptr(qp[a:b]), c, ptr(tp[a:b]), r32, r16, scale, centre, n, self.d, ptr(self._max_norm), ptr(bits),
-                    0 if bits is None else bits.numel(), 0 if allowed is None else allowed.n_allowed, cap, ptr(ws), ws.numel(), ptr(out[:c]), ptr(X[a:b]), ptr(out[c:2 * c]), ptr(out[2 * c:3 * c]), ptr(out[3 * c:]),
-                    _lib.stream_ptr()), "convdr_ip_rank_rows")
+                block = (store, ptr(qp[a:b]), c, ptr(tp[a:b]), r32, r16, scale, centre, n, self.d, ptr(self._max_norm), ptr(bits),
+                         0 if bits is None else bits.numel(), 0 if allowed is None else allowed.n_allowed)
+                outs = (cap, ptr(ws), ws.numel(), ptr(out[:c]), ptr(X[a:b]), ptr(out[c:2 * c]), ptr(out[2 * c:3 * c]), ptr(out[3 * c:]),
+                        _lib.stream_ptr())
+                if ordinals is None:
+                    _lib.check(L.convdr_ip_rank_rows(*block, *outs), who)
+                else:
+                    _lib.check(L.convdr_ip_rank_docs(*block, ptr(ordinals.ord), ordinals.ndocs, *outs), who)
                 host = out.cpu().numpy()                                             # the pass's one host read
                 hosts.append((host[:c], host[c:2 * c], host[2 * c:3 * c], host[3 * c:].view(np.int32)[:c]))
         return tuple(np.concatenate([h[i] for h in hosts]) for i in range(4)) + (X,)
+
+    # -- document rank: where does a known DOCUMENT stand among the documents? ----------------------------------------------
+    def rank_ids(self, q, ids, allowed=None, ordinals=None):
+        """Exact rank of given documents: ids int64 [nq] (one document per query) or [nq, m], numpy or torch, host or device;
+        int64 numpy of the same shape: the number of documents that precede the document ids[j, c] in the order of
+        ``search_docs`` -- a document stands where its best row stands: canonical fp64 score descending, row ascending --,
+        0-based; -1 for an id on no row (INT64_MIN included).  ``search_docs(q, k)[1][j, rank] == id`` whenever 0 <= rank < k;
+        on an index whose ids are all distinct, ``rank_ids(q, ids) == rank_rows(q, rows_of(ids))``.  Exact at any depth,
+        whatever the store and the precision.
+        allowed (as for ``rank_rows``): the document's best row is taken over ALL its rows, as ``score_ids`` does -- it need
+        not be allowed --, and the competitors are counted among the allowed rows only: "the rank among the documents that
+        are not known positives".  Consequently ``search_docs(q, k, allowed=f)`` places the document at `rank` whenever its
+        best row is allowed.  ordinals: a DocOrdinals of this index (``doc_ordinals()``), built here when not given."""
+        return self.rank_ids_tensors(q, ids, allowed=allowed, ordinals=ordinals)[0].cpu().numpy()
+
+    def rank_ids_tensors(self, q, ids, allowed=None, ordinals=None):
+        """``rank_ids`` on the device: (rank int64, D float32, R int64), all of the shape of `ids`; (D, R) is the MaxP pair of
+        ``score_ids_tensors``: the document's score and its best row.
+
+        ``score_ids_tensors`` finds every document's best row; every (query, best row) pair becomes one query of
+        convdr_ip_rank_docs (include/convdr_hip.h, "Document rank"): the band-count scan of ``rank_rows`` whose rows above
+        the band mark their document in a bitmap of ndocs bits per pair instead of being counted only, the re-scored band
+        rows that precede the target mark theirs afterwards, and the rank is the bitmap's population with the target's own
+        document left out.  The host ladder is that of ``rank_rows_tensors`` (one tensor read per pass, one jump to the
+        reported band count, one rebuild on CONVDR_IP_RANGE).  A pair whose band holds more than RANGE_MAX_CAP rows takes the
+        fallback: ``range_search`` just below the target's score, the canonical scores of the rows it returns, the ids of
+        those that precede the target, the target's own id dropped, a distinct count.  Correct, not fast.
+        ``stats``: rank_rounds, rank_cap, rank_band_rows (band entries re-scored, all passes), rank_above (ROWS marked without
+        a re-score, final passes), rank_fallback_pairs, rescaled, ndocs."""
+        import torch
+        self._need_ids("rank_ids")
+        qt, it, shape = self._ids_arg("rank_ids", q, ids)
+        f = self._filter(allowed)
+        o = self._ordinals(ordinals)
+        D, R = self.score_ids_tensors(qt, it)
+        if o is None:
+            o = self.doc_ordinals()
+        nq, m = int(qt.shape[0]), (shape[1] if len(shape) == 2 else 1)
+        npairs = nq * m
+        self.stats = {"rank_rounds": 0, "rank_cap": 0, "rank_band_rows": 0, "rank_above": 0, "rank_fallback_pairs": 0, "rescaled": 0,
+                      "ndocs": o.ndocs}
+        out = torch.full((npairs,), -1, dtype=torch.int64, device=self.device)
+        if not npairs or not self.ntotal:
+            return out.reshape(shape), D, R
+        qt = self._queries(qt, padded_ok=True)
+        qp = qt if m == 1 else qt.repeat_interleave(m, dim=0)
+        tp = R.reshape(-1).contiguous()                     # (an id on no row has best row -1: the entry's padding, rank -1)
+        X = torch.empty(npairs, dtype=torch.float64, device=self.device)
+
+        def one_pass(idx, sub, cap):
+            rank, cnt, above, st, Xs = self._rank_docs_pass(qp if sub is None else qp[sub].contiguous(),
+                                                            tp if sub is None else tp[sub].contiguous(), cap, o, f)
+            return st, cnt, (rank, above, Xs)
+
+        def accept(idx, sub, cap, ok, cnt, result):
+            nonlocal out, X
+            rank, above, Xs = result
+            self.stats["rank_band_rows"] += int(np.minimum(cnt, cap).sum())
+            self.stats["rank_above"] += int(above[ok].sum())
+            if sub is None:
+                out, X = torch.as_tensor(rank, device=self.device), Xs
+            else:
+                out[sub], X[sub] = torch.as_tensor(rank, device=self.device), Xs
+        rounds, longest, fallback = self._count_ladder("convdr_ip_rank_docs", npairs, one_pass, accept)
+        self.stats.update(rank_rounds=rounds, rank_cap=longest)
+        if fallback:
+            stats = self.stats
+            stats["rank_fallback_pairs"] = len(fallback)
+            xs = X[torch.as_tensor(np.asarray(fallback, dtype=np.int64), device=self.device)].cpu().numpy()
+            col = self.ids
+            for j, x in zip(fallback, xs):
+                t = tp[j]
+                r = np.float32(x)               # the largest fp32 strictly below the target's score (as rank_rows_tensors)
+                if not np.float64(r) < x:
+                    r = np.nextafter(r, np.float32(-np.inf))
+                qj = qp[j:j + 1].contiguous()
+                _, _, I = self.range_search_tensors(qj, r, allowed=f)
+                Xr = self.score_rows_tensors(qj, I[None, :])[1][0]
+                ahead = col[I[(Xr > float(x)) | ((Xr == float(x)) & (I < t))]]
+                out[j] = torch.unique(ahead[ahead != col[t]]).numel()
+            self.stats = stats
+        return out.reshape(shape), D, R
 
 
 # Pinned staging buffers and the copy thread pool are process-wide: pinning 64 MB costs ~20 ms (hipHostMalloc), i.e. a

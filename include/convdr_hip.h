@@ -428,6 +428,50 @@ int convdr_ip_score_docs(int store, const float* q_f32, int nq, const float* p_f
                          int d, const int64_t* rows, int64_t rows_len, const int64_t* start, const int32_t* count, int m, int64_t ld,
                          double* X, float* D, int64_t* R, convdr_stream_t stream);
 
+/* Document rank: how many DOCUMENTS precede a known row?  A document is the set of rows that carry one key ("Documents by id")
+ * and stands where its best row stands -- largest canonical score, lowest row on equal scores --, so document D precedes a
+ * target row t iff at least one (allowed) row of D precedes t in the canonical row order, and
+ *     doc_rank(q, t) = #{ distinct keys among the allowed rows r that precede t (X_r > X_t, or X_r == X_t and r < t),
+ *                         other than the key of row t }.
+ * With t the best row of a document this is that document's 0-based position among the documents of the same query.
+ * convdr_doc_ordinals   query independent, one pass over the key column: ord[r] (u32 [n]) = the number of distinct keys whose
+ *                first row lies below the first row of row_keys[r] -- the documents numbered 0 .. ndocs - 1 in the order of first
+ *                appearance --, *ndocs (device int64) = the distinct keys.  The same bits in every run.  A row that holds
+ *                INT64_MIN is in no document: ord = 0xffffffff, and bit 2 of the head's status word is set (bit 1: a probe hit
+ *                its bound; bit 3: no set -- as under "Row ids").  The key set of "Row ids" is built over the column itself (its
+ *                smallest list position is the first row), the rows that own their key are scanned exclusively (block sums, one
+ *                workgroup over the block sums, the scan inside each block), a last pass writes ord.  Six launches (two when
+ *                n == 0); plain vector stores, the only atomics are the key set's and the status bits.  0 <= n <= 2^27.
+ *   workspace    convdr_doc_ordinals_workspace_bytes(n) bytes (0 outside the contract), 256-byte aligned regions in this order:
+ *                the key set's regions for a list of n keys (256 + 20 S bytes, S = the smallest power of two >= max(64, 2 n)) |
+ *                head 256 bytes (u32 word 0: ndocs, word 1: the build's status) | document number per slot u32 [S] | block sums
+ *                u32 [ceil(n / 256)].  Nothing of it is read before this call wrote it.
+ * convdr_ip_rank_docs   the arguments of convdr_ip_rank_rows plus ord [n] and ndocs (of the SAME column and n).  target names
+ *                rows.  Thresholds, certificate, statuses, cap, bitmap and n_allowed: "Score and rank of given rows", unchanged.
+ *                A row with S~ >= tau_hi precedes t for certain: it is counted (above) and ORs its document's bit into the
+ *                pair's bitmap -- no slot, no id, no re-score; the band [tau_lo, tau_hi) is listed and re-scored as there, and
+ *                the entries that precede t OR their bit afterwards; a last launch counts the set bits with the bit of ord[t]
+ *                cleared.  A row whose ordinal is >= ndocs marks nothing.
+ *   outputs      rank[p] = doc_rank (-1 unless status is OK; a target outside [0, n): -1, status OK, counts = above = 0);
+ *                X[p] = X_t; counts[p] = the band's exact row count (re-run with cap >= counts[p] on CONVDR_IP_OVERFLOW);
+ *                above[p] = the ROWS the scan marked without a re-score (above <= the row rank of t); status as there.
+ *   workspace    convdr_ip_rank_docs_workspace_bytes(np, n, d, cap, ndocs) bytes (0 outside the contract): the regions of
+ *                convdr_ip_rank_workspace_bytes(np, n, d, cap) in their order, then the bitmap u32 [np, mark_words],
+ *                mark_words = ceil(ndocs / 32) rounded up to a multiple of 32 (np x ndocs / 8 bytes, whole 128-byte lines per
+ *                pair).  The bitmap is zeroed on the stream inside the call; nothing is read before this call wrote it.
+ * np > 0, 0 <= n < 2^31, 0 <= ndocs <= n, ord not NULL unless n == 0; everything else as for convdr_ip_rank_rows.  Arguments are
+ * validated before anything touches a device: a refusal is a negative code and a convdr_last_error message that names the
+ * entry; no allocation, no sync. */
+size_t convdr_doc_ordinals_workspace_bytes(int64_t n);
+int convdr_doc_ordinals(const int64_t* row_keys, int64_t n, void* workspace, size_t workspace_bytes, uint32_t* ord, int64_t* ndocs,
+                        convdr_stream_t stream);
+size_t convdr_ip_rank_docs_workspace_bytes(int np, int64_t n, int d, int cap, int64_t ndocs);
+int convdr_ip_rank_docs(int store, const float* q_f32, int np, const int64_t* target, const float* p_f32, const void* p_half,
+                        float p_scale, const float* centre, int64_t n, int d, const float* p_max_norm, const uint32_t* row_bits,
+                        int64_t row_bits_words, int64_t n_allowed, const uint32_t* ord, int64_t ndocs, int cap, void* workspace,
+                        size_t workspace_bytes, int64_t* rank, double* X, int64_t* counts, int64_t* above, int32_t* status,
+                        convdr_stream_t stream);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
