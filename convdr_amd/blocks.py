@@ -247,7 +247,7 @@ class BlockView:
 
 def key_row_stats(ann_data_dir, max_blocks=8, key_map=None):
     """(most rows any key owns, rows in all) over the block files under `ann_data_dir`, from the small id files alone
-    (``passage__embid_p__data_obj_{b}.pb``).  Blocks are found as the search finds them (search._search_block_list): ids
+    (``passage__embid_p__data_obj_{b}.pb``).  Blocks are found as the search finds them (block_search._search_block_list): ids
     0 .. max_blocks - 1 in order, the first one whose embedding file is missing or whose id file cannot be read ends the
     list.  key = key_map[record offset] (e.g. offset2pid) or the record offset itself."""
     ids = []

@@ -15,7 +15,7 @@ What changed for MI355X (results are identical, embeddings do not depend on batc
   * no per-batch device sync: ids go up and embeddings come back through pinned buffers asynchronously.
 
 A MaxP model (``base_len``: rdot_nll_multi_chunk) encodes documents as one row per live 512-token chunk with the record
-offset repeated (_encode_shard_chunks; the reference: gen_passage_embeddings.py:116-120); search.search_distinct_one_by_one
+offset repeated (_encode_shard_chunks; the reference: gen_passage_embeddings.py:116-120); block_search.search_distinct_one_by_one
 ranks such a block by document.
 """
 import os

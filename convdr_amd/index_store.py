@@ -1,0 +1,1053 @@
+"""The rows a FlatIPIndex holds: the resident buffers (fp32 block, scan copy, remainder copy, id column) and everything that writes
+them or speaks only about rows and ids -- add / update / remove, row filters, the id operations, reading rows back.  The questions
+asked of the rows (search, range, score, rank) are ``search.FlatIPIndex(_IndexStore)``; nothing here calls into it."""
+import os
+
+import numpy as np
+
+from . import _lib
+from .staging import _STAGING, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _staging, _staging_key
+
+_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16"}
+_HALF_PRECISIONS = ("auto", "fp16", "fp16x2")    # the rungs of a half store (storage="fp16")
+HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM_LIMIT
+
+RESERVED_ID = -(1 << 63)    # INT64_MIN: the free-slot marker of the key set (csrc/ip_keys.hpp), no legal row id
+KEY_ST_LIST, KEY_ST_PROBE, KEY_ST_COLUMN, KEY_ST_NOSET = 1, 2, 4, 8      # status bits of convdr_keyset_build / the row passes
+ROW_FILTER_TILE = 256       # the bitmap covers whole scan tiles of this many rows (csrc/ip_topk.hip: Tile256::TR)
+
+
+def pack_row_mask(mask):
+    """bool / uint8 vector [n] (a torch tensor, on any device) -> the bitmap of convdr_ip_search_filtered: int32 words (the bytes
+    of uint32), row r allowed iff bit r & 31 of word r >> 5 is set, zero padded to whole 256-row tiles (ceil(n / 256) * 8 words).
+    Torch ops on the mask's device: eight rows make a byte (least significant bit first), four bytes a little-endian word."""
+    import torch
+    m = mask.reshape(-1) != 0
+    n = int(m.numel())
+    padded = (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * ROW_FILTER_TILE
+    if padded != n:
+        m = torch.cat([m, torch.zeros(padded - n, dtype=torch.bool, device=m.device)])
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=m.device)
+    by = (m.view(-1, 8).to(torch.int32) * weights).sum(1).to(torch.uint8)         # (at most 255)
+    return by.contiguous().view(torch.int32)
+
+
+class RowFilter:
+    """An allowed subset of an index's rows (FlatIPIndex.row_filter): `bits` the device bitmap (pack_row_mask), `n` the ntotal
+    it was built for -- searching an index of another size with it raises ValueError --, `n_allowed` the number of allowed rows."""
+
+    def __init__(self, bits, n, n_allowed):
+        self.bits, self.n, self.n_allowed = bits, int(n), int(n_allowed)
+        self._rows = None
+
+    def rows(self):
+        """ascending ids of the allowed rows (device int64 [n_allowed]), unpacked from the bitmap on first use: the last rungs
+        of the ladder rank explicit row lists"""
+        import torch
+        if self._rows is None:
+            by = self.bits.view(torch.uint8).to(torch.int32)
+            shifts = torch.arange(8, dtype=torch.int32, device=by.device)
+            self._rows = torch.nonzero(((by[:, None] >> shifts) & 1).reshape(-1)[:self.n]).flatten()
+        return self._rows
+
+
+class DocOrdinals:
+    """Dense document numbers of an index's id column (FlatIPIndex.doc_ordinals): `ord` the device vector [ntotal] (int32
+    words, the bytes of uint32: ord[r] = the number of distinct ids whose first row lies below the first row of ids[r]),
+    `ndocs` the distinct ids, `n` the ntotal it was built for -- ranking with it on an index of another size raises ValueError.
+    Query independent: build once, pass as ``ordinals=`` to rank_ids / rank_ids_tensors."""
+
+    def __init__(self, ord, ndocs, n):
+        self.ord, self.ndocs, self.n = ord, int(ndocs), int(n)
+
+
+class _IndexStore:
+    """The storage half of FlatIPIndex (see there for the constructor's arguments)."""
+
+    # state an index has from birth, whatever constructed it: the id column and its ping-pong partner (keep_rows), the id
+    # operations' workspace, the H2D stream of the streamed add; a reservation; "auto" starts on the split scan
+    _sid = _sid_spare = _key_ws = _copy_stream = None
+    _reserved = _x3_first = False
+
+    def __init__(self, d, device=None, cap=4096, rank_target=0, precision="auto", center=None, prepin=True, storage="fp32"):
+        if storage not in ("fp32", "fp16"):
+            raise ValueError("FlatIPIndex: storage must be 'fp32' or 'fp16' (got %r)" % (storage,))
+        if storage == "fp16":
+            if precision not in _HALF_PRECISIONS:
+                raise ValueError("FlatIPIndex(storage='fp16'): precision must be one of %s (got %r)" % (_HALF_PRECISIONS, precision))
+            if center:
+                raise ValueError("FlatIPIndex(storage='fp16'): the half store is not centred (center=True)")
+            center = False
+        elif center is None:
+            center = True
+        import torch
+        if not torch.cuda.is_available():
+            raise _lib.ConvdrError("FlatIPIndex needs a GPU (no CPU fallback)")
+        assert precision in _KINDS and (storage == "fp16" or precision != "fp16x2"), precision
+        self.storage, self._half = storage, storage == "fp16"
+        _lib.lib()
+        # the scan contracts in 64-wide K steps: other widths get zero columns, which add exact zeros to every score
+        self.d_in = int(d)
+        self.d = (self.d_in + 63) // 64 * 64
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        self.cap, self.rank_target = int(cap), int(rank_target)
+        self.precision, self.center = precision, bool(center)
+        self.kind = _KINDS[precision]
+        self._half_dtype = torch.float16 if self.kind == "f16" else torch.bfloat16
+        self.host_chunk_bytes = 64 << 20       # staging-buffer size of the streamed host -> HBM path (add); 64 MB x 16
+                                               # threads measured best on the bench host (tools/dbg/block_load_sweep.py)
+        self.host_copy_threads = 16            # file reads / memcpy slices in flight while filling a staging buffer
+        self.host_stage_buffers = 4            # pinned staging buffers (3 chunks being read while one crosses PCIe; 37-41 GB/s of a
+                                               # 44 GB/s pinned-H2D ceiling on the r03 box, tools/dbg/block_load_sweep.py)
+        self.compact_window_rows = 65536       # rows per window of keep_rows / remove_rows (a multiple of 256): the bounce buffer
+                                               # holds one window of the widest buffer, 192 MB at d = 768; best of the sweep
+                                               # 1,024 .. 262,144 at 1 M rows (profiles/compact_rows_time.txt)
+        self.stats = {}
+        self._s32 = self._s16 = self._slo = None
+        self.reset()
+        if prepin:
+            self.prepin_staging()
+
+    def prepin_staging(self, wait=False):
+        """Allocate and page-lock the process-wide staging buffers of the block loader (4 x 64 MB on the GPU's NUMA node, ~60 ms)
+        NOW, on a background thread: the first add() of a block file used to pay for it (19 GB/s against 49 GB/s for every
+        later block; the reference's flow constructs the index, then loads 8 block files: run_convdr_inference.py:353,164-180).
+        Called by the constructor (prepin=True); add() joins the thread if it is still running."""
+        import threading
+        key = _staging_key(self.device, self.d, max(2, int(self.host_stage_buffers)))
+        rows = max(1, int(self.host_chunk_bytes) // (4 * self.d))
+        with _STAGING_LOCK:
+            ent = _STAGING.get(key)
+            th = _STAGING_THREADS.get(key)
+            if not ((ent is not None and ent[0][0].shape[0] >= rows) or (th is not None and th.is_alive())):
+                th = threading.Thread(target=_staging, args=(self.device, rows, self.d, key[2]), daemon=True, name="convdr-prepin")
+                _STAGING_THREADS[key] = th
+                th.start()
+        if wait and th is not None:
+            th.join()
+
+    def twin(self):
+        """An empty index with this one's parameters (search_one_by_one keeps two blocks in flight: one being searched, one
+        being loaded)."""
+        t = type(self)(self.d_in, device=self.device, cap=self.cap, rank_target=self.rank_target, precision=self.precision,
+                         center=None if self._half else self.center, prepin=False, storage=self.storage)
+        t.host_chunk_bytes, t.host_copy_threads, t.host_stage_buffers = self.host_chunk_bytes, self.host_copy_threads, self.host_stage_buffers
+        return t
+
+    # -- faiss-like surface ---------------------------------------------------
+    @property
+    def ntotal(self):
+        return self._n
+
+    # the resident block (views of the used rows of the backing storage)
+    @property
+    def _p32(self):
+        return None if self._s32 is None else self._s32[:self._n]
+
+    @property
+    def _pbf(self):
+        return None if self._s16 is None else self._s16[:self._n]
+
+    @property
+    def _plo(self):
+        return None if self._slo is None else self._slo[:self._n]
+
+    @property
+    def _rows(self):
+        """The rows the canonical re-score reads: the fp32 block, or the half store itself."""
+        return self._pbf if self._half else self._p32
+
+    @property
+    def store(self):
+        """storage="fp16": the resident halves [ntotal, d] = 2^s x the stored passages (s: ``_scale``)."""
+        return self._pbf if self._half else None
+
+    def _row_pair(self, sel):
+        """(re-score rows, scan copy) of a slice or an index vector of the resident rows, contiguous"""
+        if self._half:
+            r = self._pbf[sel].contiguous()
+            return r, r
+        return self._p32[sel].contiguous(), self._pbf[sel].contiguous()
+
+    def _operands(self, rows=None):
+        """What a block looks like to the C ABI: (store code 0 bf16 / 1 fp16 / 2 half store, fp32 rows or NULL, 16-bit operand,
+        scale of that operand, centre or NULL) of the resident block, or of `rows` = (re-score rows, scan copy) of a slice.  The
+        half store has no fp32 rows and no centre, the bf16 copy no scale."""
+        ptr = _lib.ptr
+        p32, p16 = (self._rows, self._pbf) if rows is None else rows
+        store = 2 if self._half else (1 if self.kind == "f16" else 0)
+        return (store, None if self._half else ptr(p32), ptr(p16), float(self._scale) if store else 1.0,
+                None if self._half else ptr(self._centre))
+
+    def _queries(self, q, padded_ok=False):
+        """The queries as every entry reads them: fp32 [nq, d] on the index's device, contiguous, the zero columns of a padded
+        width appended (padded_ok: a tensor that already has them is taken as it is)."""
+        import torch
+        qt = torch.as_tensor(q)
+        if qt.dtype != torch.float32:
+            qt = qt.float()
+        if self.d != self.d_in and not (padded_ok and qt.dim() == 2 and qt.shape[1] == self.d):
+            qt = self._pad_columns(qt)
+        qt = qt.to(self.device).contiguous()
+        assert qt.dim() == 2 and qt.shape[1] == self.d
+        return qt
+
+    def reset(self):
+        """faiss ``index.reset()``: forget the passages.  A reservation made with reserve() survives (its memory is reused
+        by the next block); ``release()`` drops it."""
+        import torch
+        self._n = 0
+        if not self._reserved:
+            self._s32 = self._s16 = self._slo = None
+        self._sid = self._sid_spare = None      # the id column and its ping-pong partner (keep_rows): an index has ids or not,
+                                                # from its first add on; a reset forgets that too
+        self._centre = None
+        self._scale = 1.0                       # power of two applied to the fp16 scan copy (1 for bf16)
+        self._max_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self._half:
+            # max norm and the flag word of convdr_ip_store_rows_f16 side by side: ONE host read at the end of an add()
+            self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self._max_norm, self._flags = self._mf[:1], self._mf[1:2].view(torch.int32)
+            self._uflags = self._mf[2:].view(torch.int32)       # update_rows has a flag word of its own: update_flags()
+        self._ws = None
+        self._x3_first = False
+
+    def release(self):
+        self._reserved = False
+        self.reset()
+
+    def reserve(self, n, lo=None):
+        """Backing storage for n passages (fp32 block + 16-bit scan copy, + the remainder copy of the split scan when
+        `lo`, default: only if the precision pins it; + the id column of an index that carries ids).  Existing rows are kept."""
+        import torch
+        held = {"_s16": self._half_dtype}          # the buffers this index holds: a half store keeps its 16-bit rows and nothing else
+        if not self._half:
+            held["_s32"] = torch.float32
+            if self._slo is not None or ((self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)):
+                held["_slo"] = self._half_dtype
+        rows = max(int(n), 0 if self._s16 is None else self._s16.shape[0])      # (all of them keep one row count)
+        with torch.cuda.device(self.device):
+            for name, dtype in held.items():
+                old = getattr(self, name)
+                if old is None or old.shape[0] < rows:
+                    t = torch.empty((rows, self.d), dtype=dtype, device=self.device)
+                    if old is not None and self._n:
+                        t[:self._n].copy_(old[:self._n])
+                    setattr(self, name, t)
+            if self._sid is not None:
+                self._reserve_ids(rows)
+        self._reserved = True
+
+    def _reserve_ids(self, rows, keep=None):
+        """the id column for `rows` rows (the first `keep` entries kept, default ntotal); its ping-pong partner is re-made on
+        its next use"""
+        import torch
+        keep = self._n if keep is None else keep
+        if self._sid is None or self._sid.shape[0] < rows:
+            t = torch.empty(int(rows), dtype=torch.int64, device=self.device)
+            if self._sid is not None and keep:
+                t[:keep].copy_(self._sid[:keep])
+            self._sid, self._sid_spare = t, None
+
+    def _prepare_into(self, src32, dst16, dstlo):
+        """scan copy (and remainder copy) of the fp32 rows `src32`; folds their norms into the block's max norm"""
+        ptr = _lib.ptr
+        name, scale = ("convdr_ip_prepare_block_f16", (float(self._scale),)) if self.kind == "f16" else ("convdr_ip_prepare_block", ())
+        _lib.check(getattr(_lib.lib(), name)(ptr(src32), src32.shape[0], self.d, ptr(self._centre), *scale, ptr(dst16), ptr(dstlo),
+                                             ptr(self._max_norm), _lib.stream_ptr()), name)
+
+    def _first_rows(self, t):
+        """The first rows an empty index sees fix its centring vector and, for the fp16 scan, the power-of-two scale of the
+        scan copy (from these rows' largest centred norm: one extra pass over them and one host read per index
+        lifetime; later rows may be up to 7x longer before the copy has to be rebuilt, see _rebuild_scaled)."""
+        if self.center:
+            self._set_centre(t)
+        if self.kind == "f16":
+            L = _lib.lib()
+            _lib.check(L.convdr_ip_prepare_block_f16(_lib.ptr(t), t.shape[0], self.d, _lib.ptr(self._centre), 1.0, None, None,
+                                                     _lib.ptr(self._max_norm), _lib.stream_ptr()), "convdr_ip_prepare_block_f16")
+            self._scale = float(L.convdr_ip_f16_scale(float(self._max_norm.item())))
+
+    def _rebuild_scaled(self):
+        """CONVDR_IP_RANGE: rows added after the scale was fixed are more than 7x longer than the first block's longest.
+        Re-derive the scale from the block's max norm and rebuild the fp16 copies from the resident fp32 rows."""
+        import torch
+        if self._half:
+            # the half store is rescaled IN PLACE by 2^(s_new - s_old) <= 1, s_new >= 0: exact (convdr_ip_store_rows_f16)
+            new = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
+            with torch.cuda.device(self.device):
+                if self._n and new != self._scale:
+                    self._store_rows(self._pbf, self._pbf, new / self._scale, fold_norm=False)
+                    if int(self._flags.item()):
+                        raise _lib.ConvdrError("half store: the in-place rescale %g -> %g was not exact" % (self._scale, new))
+            self._scale = new
+            return
+        with torch.cuda.device(self.device):
+            self._scale = float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item())))
+            if self._n:
+                self._prepare_into(self._p32, self._pbf, self._plo)
+
+    def _grow_for(self, m, want_lo=False):
+        """rows [n, n + m) of the backing storage (fp32 block, scan copy, remainder copy; None for a buffer the index does not
+        hold), growing it when needed (exact fit unless reserved larger)"""
+        need = self._n + m
+        if self._s16 is None or self._s16.shape[0] < need or (want_lo and self._slo is None):
+            keep = self._reserved
+            self.reserve(need, lo=want_lo)
+            self._reserved = keep
+        return tuple(None if t is None else t[self._n:need] for t in (self._s32, self._s16, self._slo))
+
+    def _source(self, x, chunk_bytes, np_dtype, keep):
+        """What add() was given, normalised.  (host array, reader) when it is to be streamed: a `np_dtype` [n, d] array of more
+        than chunk_bytes // 2 that is a numpy array, a pageable CPU tensor (of keep[0], np_dtype's torch name) or the payload
+        of a blocks.BlockView (reader: its positioned reads from the file).  Otherwise (contiguous device tensor [n, d], None);
+        dtypes outside `keep` become fp32."""
+        import torch
+        if self.d != self.d_in:
+            x = self._pad_columns(x.array if hasattr(x, "array") else x)
+        reader = None
+        if hasattr(x, "read_rows_into") and hasattr(x, "array"):        # a blocks.BlockView
+            reader, x = x.read_rows_into, x.array
+        arr = x
+        if isinstance(x, torch.Tensor) and x.device.type == "cpu" and not x.is_pinned() and x.dtype == keep[0]:
+            arr = x.numpy()
+        if isinstance(arr, np.ndarray) and arr.dtype == np_dtype and arr.ndim == 2 and arr.nbytes > chunk_bytes // 2:
+            assert arr.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, arr.shape)
+            return arr, reader
+        from_host = not (isinstance(x, torch.Tensor) and x.is_cuda)
+        if isinstance(x, np.ndarray) and not x.flags.writeable:
+            # a read-only array (the mmap of a small block file): torch.as_tensor would alias it without knowing it must
+            # never write (a UserWarning today, undefined behaviour the day someone does) -- small by construction (large
+            # host blocks are streamed), so it is copied first
+            x = np.array(x, order="C")
+        t = torch.as_tensor(x)
+        if t.dtype not in keep:
+            t = t.float()
+        # (a host source that is not pinned -- e.g. the mmap of a small block file, which search_one_by_one closes right
+        #  after add() returns -- is copied synchronously: nothing may still be reading it when add() is back)
+        t = t.to(self.device, non_blocking=not from_host or t.is_pinned()).contiguous()
+        assert t.dim() == 2 and t.shape[1] == self.d, "expected [n, %d], got %s" % (self.d, tuple(t.shape))
+        return t, None
+
+    def add(self, x, chunk_bytes=None, ids=None):
+        """x: numpy / torch [n, d] float32 (host or device).  Appends to the index.
+        A HOST array -- typically the memory-mapped payload of a block file (blocks.BlockView) -- is streamed: chunks of
+        ~chunk_bytes (default 64 MB) go through pinned staging buffers, the H2D copy of chunk i + 1 (copy stream) runs under the
+        centring / rounding / norm pass of chunk i (convdr_ip_prepare_block*), and the host fills one staging buffer
+        (page faults on the mmap = the disk read) while the others are in flight.  The reference does pickle.load (a full
+        host copy of the 14.6 GB block) and a pageable copy (run_convdr_inference.py:164-180).
+
+        ids (FAISS ``add_with_ids``): an int64 vector [n], numpy or torch, host or device -- the rows' ids (``passage_embedding2id``,
+        ``offset2pid``), kept in a device column beside the rows (``idx.ids``) and carried through keep_rows / remove_rows.  Ids
+        need not be distinct: the chunk rows of one document share theirs.  Every add of an index carries ids or none does;
+        a mixed add, a vector of another length or dtype, or the reserved id INT64_MIN raises ValueError and leaves the index
+        as it was (ids on the device cost one host read for that check), and an add the index refuses leaves the column as it
+        was, too."""
+        if ids is None:
+            if self._n and self._sid is not None:
+                raise ValueError("FlatIPIndex.add: this index carries row ids (%d rows), an add without ids= would leave rows "
+                                 "without one; the index is unchanged" % self._n)
+            return self._add_rows(x, chunk_bytes)
+        if self._n and self._sid is None:
+            raise ValueError("FlatIPIndex.add: this index holds %d rows without ids, ids= cannot start now; the index is unchanged"
+                             % self._n)
+        rows = x.array if hasattr(x, "array") else x
+        m = int(rows.shape[0]) if hasattr(rows, "shape") else len(rows)
+        self._add_keyed(x, chunk_bytes, self._id_list("add", ids, length=m))
+
+    def _add_keyed(self, x, chunk_bytes, t):
+        """the rows `x` and their checked ids `t` (device int64, one per row) behind the resident rows and the column"""
+        n0, m = self._n, int(t.numel())
+        self._add_rows(x, chunk_bytes)                  # (raises: nothing below has touched the column)
+        if m:
+            self._reserve_ids(max(n0 + m, 0 if self._s16 is None else self._s16.shape[0]), keep=n0)
+            self._sid[n0:n0 + m].copy_(t)
+
+    def _id_list(self, who, ids, length=None):
+        """ids of a caller -> device int64 vector, contiguous.  ValueError: not an int64 vector, not `length` entries, or the
+        reserved id INT64_MIN (looked for here only where that costs no more than it does for add: `length` given, or the
+        ids are on the host; the kernels flag it for the others)."""
+        import torch
+        if isinstance(ids, np.ndarray) and not ids.flags.writeable:
+            ids = np.array(ids)                     # (a read-only array -- a memory-mapped id table: as in _source)
+        t = torch.as_tensor(ids)
+        if t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError("%s: ids must be an int64 vector (got %s, shape %s)" % (who, t.dtype, tuple(t.shape)))
+        if length is not None and int(t.numel()) != length:
+            raise ValueError("%s: %d ids for %d rows" % (who, int(t.numel()), length))
+        if (length is not None or t.device.type == "cpu") and t.numel() and bool((t == RESERVED_ID).any()):
+            raise ValueError("%s: the id %d (INT64_MIN) is reserved" % (who, RESERVED_ID))
+        return t.to(self.device).contiguous()
+
+    def _add_rows(self, x, chunk_bytes=None):
+        """add() without the id column"""
+        import time
+        import torch
+        chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
+        if self._half:
+            return self._add_half(x, chunk_bytes)
+        t, reader = self._source(x, chunk_bytes, np.float32, (torch.float32,))
+        m = int(t.shape[0])
+        if m == 0:
+            return
+        want_lo = self.precision in ("bf16x3", "fp16x3") or self._slo is not None
+        with torch.cuda.device(self.device):
+            if isinstance(t, np.ndarray):
+                t0 = time.perf_counter()
+                p32, p16, plo = self._grow_for(m, want_lo)
+                first = self._n == 0
+
+                def prepare(ci, s, e):
+                    if first and ci == 0:
+                        # centre = column mean of the first chunk (>= 40 k passages): any centre keeps the search exact -- it
+                        # shifts every score of a query by the same constant -- it only has to be close to the mean to shrink
+                        # the rounding-error band; likewise the fp16 scale comes from the first chunk's norms
+                        self._first_rows(p32[s:e])
+                    self._prepare_into(p32[s:e], p16[s:e], plo[s:e] if plo is not None else None)
+                self._stream_rows(t, p32, reader, chunk_bytes, prepare, t0)
+            else:
+                if self._n == 0:
+                    self._first_rows(t)
+                if self._s32 is None and not want_lo:
+                    # first block of an unreserved index: adopt the caller's device tensor instead of copying it
+                    self._s32 = t
+                    self._s16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
+                    dst32, dst16, dstlo = self._s32, self._s16, None
+                else:
+                    dst32, dst16, dstlo = self._grow_for(m, want_lo)
+                    dst32.copy_(t)
+                self._prepare_into(dst32, dst16, dstlo)
+        self._n += m
+
+    # -- the half store (storage="fp16") ----------------------------------------
+    def _store_rows(self, src, dst, scale, fold_norm=True, flags=None):
+        """convdr_ip_store_rows_f16: dst = half(src) * scale (dst None: norms and the non-finite flag only)"""
+        import torch
+        _lib.check(_lib.lib().convdr_ip_store_rows_f16(_lib.ptr(src), int(src.dtype == torch.float32), src.shape[0], self.d,
+                                                       float(scale), _lib.ptr(dst), _lib.ptr(self._max_norm) if fold_norm else None,
+                                                       _lib.ptr(self._flags if flags is None else flags), _lib.stream_ptr()),
+                   "convdr_ip_store_rows_f16")
+
+    def update_flags(self):
+        """Flag word of the update_rows calls so far (one host read): bit 0 = a new row held a value that is not finite as
+        a half, bit 1 = a scaled value overflowed (the rows outgrew the scale by more than CONVDR_IP_RANGE catches)."""
+        return int(self._uflags.item())
+
+    def _half_first_scale(self, src):
+        """An empty half store takes its scale from the first rows' largest norm (one pass, one host read), never below 1."""
+        self._store_rows(src, None, 1.0)
+        self._scale = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
+
+    def _add_half(self, x, chunk_bytes):
+        """add() of a half store.  `write(dst)` below puts the new rows into dst = store[n, n + m) (rounded, scaled, norms
+        and flags folded); the flag word and the max norm are read ONCE, at the end, and decide: keep, refuse (the index is
+        left exactly as it was), or -- a scaled value overflowed: the new rows are too long for the scale -- lower the scale,
+        rescale the resident rows in place and write the new rows once more (the only case with a second read)."""
+        import torch
+        t, reader = self._source(x, chunk_bytes, np.float16, (torch.float16, torch.float32))
+        m = int(t.shape[0])
+
+        def write(dst, first):
+            if not isinstance(t, np.ndarray):
+                if first:
+                    self._half_first_scale(t)
+                return self._store_rows(t, dst, self._scale)
+
+            def scale_in_place(ci, s, e):       # the copy stream wrote the halves straight into the store
+                if first and ci == 0:
+                    self._half_first_scale(dst[s:e])
+                self._store_rows(dst[s:e], dst[s:e], self._scale)
+            self._stream_rows(t, dst, reader, chunk_bytes, scale_in_place)
+        if m == 0:
+            return
+        n0, scale0 = self._n, self._scale
+        with torch.cuda.device(self.device):
+            mn0 = self._max_norm.clone()
+            dst = self._grow_for(m)[1]
+            for attempt in (0, 1):
+                write(dst, n0 == 0 and attempt == 0)
+                got = self._mf[:2].cpu()                                    # the one host read of this add()
+                mn, fl = float(got[0]), int(got.view(torch.int32)[1])
+                self._flags.zero_()
+                if (fl & 1) or not mn <= HALF_NORM_LIMIT:
+                    self._scale = scale0
+                    self._max_norm.copy_(mn0)
+                    raise _lib.ConvdrError("FlatIPIndex(storage='fp16').add: %s; the index is unchanged (%d rows)"
+                                           % ("a value is not finite as a half" if fl & 1 else
+                                              "a row's norm %g exceeds %g" % (mn, HALF_NORM_LIMIT), n0))
+                if not (fl & 2):
+                    break
+                if attempt:
+                    raise _lib.ConvdrError("half store: scaled values overflow at scale %g, max norm %g" % (self._scale, mn))
+                self._rebuild_scaled()          # the scale that fits the new max norm; rows [0, n0) rescaled in place
+            self._n = n0 + m
+
+    def _stream_rows(self, arr, dst, reader, chunk_bytes, each, t0=None):
+        """Host rows `arr` -> device rows `dst` (same shape and element type) through the pinned staging buffers -- viewed as
+        dst's element type, so a buffer holds twice the rows of halves -- with the H2D copies on the copy stream; each(ci, s, e)
+        is called on the main stream's side once chunk ci = rows [s, e) is ordered before it (its copy enqueued and waited
+        for by the main stream).  reader: a BlockView's positioned reads instead of slices of `arr`.  t0: when the add()
+        began to enqueue, for `stats["add_host_s"]` (default: now)."""
+        import time
+        import torch
+        n, d = arr.shape
+        t0 = time.perf_counter() if t0 is None else t0
+        per32 = max(1, int(chunk_bytes) // (4 * d))     # the pinned bytes per buffer, as fp32 rows
+        rows_per = per32 * 4 // dst.element_size()
+        nbuf = max(2, int(self.host_stage_buffers))
+        main = torch.cuda.current_stream()
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        stage, freed = _staging(self.device, min(per32, (n * dst.element_size() + 3) // 4), d, nbuf)
+        stage = [b.view(dst.dtype).view(-1, d) for b in stage]
+        cs = self._copy_stream
+        cs.wait_stream(main)                    # (allocation order / the copy of the old rows in _grow_for)
+        avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        threads = max(1, min(int(self.host_copy_threads), avail))
+        pool = _copy_pool(threads * (nbuf - 1), self.device)
+        chunks = [(s, min(n, s + rows_per)) for s in range(0, n, rows_per)]
+
+        def fill(ci):
+            """start filling staging buffer ci % nbuf with chunk ci: `threads` positioned reads / memcpy slices"""
+            s, e = chunks[ci]
+            bi = ci % nbuf
+            # staging buffer bi may be refilled once its previous H2D copy has completed.  The events live with the
+            # buffers (module-level, shared by every index of the process): the last copies of one add() are still in
+            # flight when the next add() starts filling (1 run in ~500 put rows of a second block into the first
+            # before they did, tests/test_ip_search_gpu.py::test_back_to_back_streamed_adds_keep_their_rows)
+            if freed[bi] is not None:
+                freed[bi].synchronize()
+            buf = stage[bi].numpy()[:e - s]
+            if reader is not None:
+                return reader(buf, s, e, pool=pool, parts=threads, wait=False)
+            step = (e - s + threads - 1) // threads
+            return [pool.submit(np.copyto, buf[a:a + step], arr[s + a:min(e, s + a + step)]) for a in range(0, e - s, step)]
+        inflight = {ci: fill(ci) for ci in range(min(nbuf - 1, len(chunks)))}
+        for ci, (s, e) in enumerate(chunks):
+            for f in inflight.pop(ci):
+                f.result()
+            bi = ci % nbuf
+            with torch.cuda.stream(cs):
+                dst[s:e].copy_(stage[bi][:e - s], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(cs)
+            freed[bi] = ev
+            main.wait_event(ev)
+            if ci + nbuf - 1 < len(chunks):
+                # nbuf - 1 chunks are being read while this one crosses PCIe (the copy stream never waits for the host;
+                # with two buffers -- round 2 -- the reads of chunk i + 1 only started after chunk i had been enqueued)
+                inflight[ci + nbuf - 1] = fill(ci + nbuf - 1)
+            each(ci, s, e)
+        self.stats["add_host_s"] = time.perf_counter() - t0     # host time to enqueue (the last chunks are still in flight)
+        self.stats["add_host_bytes"] = n * d * dst.element_size()
+
+    def _pad_columns(self, x):
+        import torch
+        t = torch.as_tensor(x)
+        t = (t if t.dtype == torch.float32 else t.float()).to(self.device)
+        assert t.dim() == 2 and t.shape[1] == self.d_in, "expected [n, %d], got %s" % (self.d_in, tuple(t.shape))
+        return torch.nn.functional.pad(t, (0, self.d - self.d_in))
+
+    def _set_centre(self, t):
+        import torch
+        self._centre = torch.empty(self.d, dtype=torch.float32, device=self.device)
+        scratch = torch.empty(1024 * self.d, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().convdr_ip_column_mean(_lib.ptr(t), t.shape[0], self.d, _lib.ptr(scratch),
+                                                   _lib.ptr(self._centre), _lib.stream_ptr()), "convdr_ip_column_mean")
+
+    def _ensure_lo(self):
+        """Remainder copy for the split scan, built on first use."""
+        import torch
+        if not self._half and self._slo is None and self._s32 is not None:
+            with torch.cuda.device(self.device):
+                self._slo = torch.empty((self._s32.shape[0], self.d), dtype=self._half_dtype, device=self.device)
+                if self._n:
+                    self._prepare_into(self._p32, self._pbf, self._plo)
+
+    def update_rows(self, row0, emb):
+        """Overwrite rows [row0, row0 + len(emb)) of the resident block with freshly encoded embeddings
+        (device fp32 [m, d]) and refresh their scan copy / the block's max norm.  No sync."""
+        import torch
+        m = int(emb.shape[0])
+        assert emb.dtype == torch.float32 and emb.is_contiguous() and row0 + m <= self.ntotal
+        if self._half:
+            # the new rows are rounded to half and scaled; a row the store cannot hold is an error AFTER the write (the caller
+            # owns the rows it overwrites), a scale the rows outgrow is CONVDR_IP_RANGE at the next search, as for add()
+            src = emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))
+            with torch.cuda.device(self.device):
+                self._store_rows(src.contiguous(), self._pbf[row0:row0 + m], self._scale, flags=self._uflags)
+            return
+        dst32, dstbf = self._p32[row0:row0 + m], self._pbf[row0:row0 + m]
+        dstlo = None if self._slo is None else self._plo[row0:row0 + m]
+        dst32[:, :self.d_in].copy_(emb)      # (zero columns of a padded width stay zero)
+        with torch.cuda.device(self.device):
+            self._prepare_into(dst32, dstbf, dstlo)
+
+    def row_filter(self, mask):
+        """A RowFilter of this index from a bool / uint8 vector [ntotal] (numpy or torch, host or device; non-zero = allowed):
+        packed on the index's device with torch ops, the allowed count read ONCE, here (one host round trip at build time, none
+        per search).  Pass it as ``allowed=`` to search / search_tensors / search_begin / search_device / search_deep_device.
+        Valid while ntotal stays what it was: update_rows keeps it, add and reset do not."""
+        import torch
+        m = torch.as_tensor(mask)
+        if m.dim() != 1 or int(m.numel()) != self.ntotal:
+            raise ValueError("row_filter: the mask must be a vector of ntotal = %d entries (got shape %s)"
+                             % (self.ntotal, tuple(m.shape)))
+        m = m.to(self.device) != 0
+        return RowFilter(pack_row_mask(m), self.ntotal, int(m.sum().item()))
+
+    def _filter(self, allowed):
+        """allowed= of a search call -> None or a RowFilter that fits this index"""
+        if allowed is None:
+            return None
+        if not isinstance(allowed, RowFilter):
+            return self.row_filter(allowed)
+        if allowed.n != self.ntotal or allowed.bits.device != self.device:
+            raise ValueError("stale RowFilter: built for ntotal = %d on %s, the index holds %d rows on %s"
+                             % (allowed.n, allowed.bits.device, self.ntotal, self.device))
+        return allowed
+
+    def _workspace(self, nbytes):
+        import torch
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    # -- removing rows (FAISS remove_ids) and reading rows back (reconstruct) -------------------------------------------
+    def keep_rows(self, allowed):
+        """Compact the index to the allowed rows, IN PLACE: `allowed` is a RowFilter of this index or a bool / uint8 mask
+        [ntotal] (non-zero = keep; a stale filter raises ValueError, as in search).  Returns the number of rows removed.
+
+        The kept rows move to the front of every resident buffer (fp32 block, scan copy, remainder copy; the half store: its
+        one buffer) in their old order, bit for bit: row r becomes row #{kept rows before r}, so ``search`` afterwards equals
+        ``search(..., allowed=keep)`` before, with the ids renumbered by ``cumsum(keep) - 1``.  No buffer is copied: the device
+        works through windows of ``compact_window_rows`` rows (convdr_ip_compact_*, include/convdr_hip.h "Removing rows") and
+        the extra memory is one window of the widest buffer.  ntotal becomes the filter's ``n_allowed``, which is already on
+        the host: nothing is read back, the whole removal is enqueued.
+
+        What stays: the centre and the scale (any centre keeps the search exact, and the scale still fits); ``_max_norm``,
+        which remains an UPPER bound of the kept rows' norms -- all the certificate needs, so it is not recomputed; a
+        reservation and the backing storage, which is not shrunk: the next ``add`` fills rows [ntotal, ...).
+        The id column of an index that carries ids (add(ids=)) is compacted with the same bitmap and plan: ``idx.ids`` stays in
+        step, nothing is cut by hand.
+        What the caller does: filters built for the old ntotal are stale (unless nothing was removed); side tables the index
+        does not hold (the keys of search_distinct) are cut with the same mask, ``keys[keep]``; a first block adopted from
+        the caller's device tensor is modified in place, as by update_rows; a search_begin handle is finished first.
+        ``stats``: removed, compact_windows (windows per buffer)."""
+        f = self._filter(allowed)
+        if f is None:
+            raise ValueError("keep_rows: a RowFilter or a mask of ntotal = %d entries is needed (got None)" % self.ntotal)
+        n, w = self.ntotal, int(self.compact_window_rows)
+        if w < ROW_FILTER_TILE or w % ROW_FILTER_TILE:
+            raise ValueError("keep_rows: compact_window_rows must be a positive multiple of %d (got %d)" % (ROW_FILTER_TILE, w))
+        removed = n - f.n_allowed
+        self.stats = {"removed": removed, "compact_windows": 0}
+        if removed:
+            self._compact(f, w)
+            self._n = f.n_allowed
+            self.stats["compact_windows"] = (n + w - 1) // w
+        return removed
+
+    def remove_rows(self, rows):
+        """FAISS ``remove_ids``: `rows` is an int64 id vector (numpy or torch, host or device; duplicates allowed) or a bool /
+        uint8 mask [ntotal] (non-zero = remove).  An id outside [0, ntotal) raises ValueError and leaves the index as it was.
+        The keep mask is built on the device and handed to ``keep_rows`` (one host read: the kept count and the range check
+        together).  Returns the number of rows removed."""
+        import torch
+        n = self.ntotal
+        t = torch.as_tensor(rows)
+        if t.dtype in (torch.bool, torch.uint8):
+            if t.dim() != 1 or int(t.numel()) != n:
+                raise ValueError("remove_rows: the mask must be a vector of ntotal = %d entries (got shape %s)" % (n, tuple(t.shape)))
+            return self.keep_rows(t.to(self.device) == 0)
+        if t.is_floating_point() or t.is_complex() or t.dim() != 1:
+            raise ValueError("remove_rows: rows must be an integer id vector or a bool / uint8 mask (got %s, shape %s)"
+                             % (t.dtype, tuple(t.shape)))
+        if not t.numel():
+            self.stats = {"removed": 0, "compact_windows": 0}
+            return 0
+        if t.device.type == "cpu" and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError("remove_rows: row ids %d..%d outside [0, ntotal = %d)" % (int(t.min()), int(t.max()), n))
+        if n == 0:
+            raise ValueError("remove_rows: the index is empty, no id is inside [0, ntotal = 0)")
+        t = t.to(torch.int64).to(self.device)
+        keep = torch.ones(n, dtype=torch.bool, device=self.device)
+        keep[t.clamp(0, n - 1)] = False                    # (a scratch mask: the index is untouched until the ids are known good)
+        counts = torch.stack([keep.sum(), ((t < 0) | (t >= n)).sum()]).cpu()
+        if int(counts[1]):
+            raise ValueError("remove_rows: %d row ids outside [0, ntotal = %d)" % (int(counts[1]), n))
+        return self.keep_rows(RowFilter(pack_row_mask(keep), n, int(counts[0])))
+
+    def _compact(self, f, window_rows):
+        """convdr_ip_compact_plan once, convdr_ip_compact_rows per resident buffer; no host read.  The plan's device scalar
+        stays in ``_n_kept`` (int64 [1])."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        # (a block shorter than the window is one window either way: the bounce buffer need not be larger than the block)
+        window_rows = min(int(window_rows), (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * ROW_FILTER_TILE)
+        bufs = [t for t in (self._s32, self._s16, self._slo) if t is not None]
+        widest = max(int(t.shape[1]) * t.element_size() for t in bufs)
+        need = L.convdr_ip_compact_workspace_bytes(n, widest, window_rows)
+        if not need:
+            raise _lib.ConvdrError("convdr_ip_compact_rows: sizes outside the contract: %s" % L.convdr_last_error().decode())
+        ws = self._workspace(need)
+        words = int(f.bits.numel())
+        with torch.cuda.device(self.device):
+            self._n_kept = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_ip_compact_plan(ptr(f.bits), words, n, ptr(ws), ws.numel(), ptr(self._n_kept), _lib.stream_ptr()),
+                       "convdr_ip_compact_plan")
+            for t in bufs:
+                _lib.check(L.convdr_ip_compact_rows(ptr(t), int(t.shape[1]) * t.element_size(), n, ptr(f.bits), words, window_rows,
+                                                    ptr(ws), ws.numel(), _lib.stream_ptr()), "convdr_ip_compact_rows")
+            if self._sid is not None:
+                # the id column: 8-byte rows, out of place into its partner by the same plan; the two then change roles
+                if self._sid_spare is None or self._sid_spare.shape[0] != self._sid.shape[0]:
+                    self._sid_spare = torch.empty_like(self._sid)
+                _lib.check(L.convdr_ip_compact_ids(ptr(self._sid), ptr(self._sid_spare), n, ptr(f.bits), words, ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr()), "convdr_ip_compact_ids")
+                self._sid, self._sid_spare = self._sid_spare, self._sid
+
+    # -- row ids (FAISS IndexIDMap2): the column add(ids=) fills, and the operations that speak in ids ---------------------
+    # No key -> row table is kept: every call builds a hash set of ITS list on the device (convdr_keyset_build) and all rows
+    # probe it in one pass over the column (convdr_keys_member / convdr_keys_locate; include/convdr_hip.h "Row ids").
+    @property
+    def ids(self):
+        """The rows' ids: device int64 [ntotal], a view of the column; None for an index that never got ids."""
+        return None if self._sid is None else self._sid[:self._n]
+
+    def _need_ids(self, who):
+        if self.ids is None:
+            raise ValueError("%s: this index carries no row ids (give them to add: add(x, ids=...))" % who)
+
+    def _keyset(self, who, t, need=None):
+        """convdr_keyset_build of the device int64 list `t` -> (workspace, status int32 [1]); enqueued, no host read.
+        need: bytes of a workspace that keeps more behind the set (0: sizes outside that entry's contract)"""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        m = int(t.numel())
+        need = int(L.convdr_keyset_workspace_bytes(m)) if need is None else need
+        if not need:
+            raise ValueError("%s: %s" % (who, L.convdr_last_error().decode()))
+        ws = self._key_workspace(need)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.check(L.convdr_keyset_build(ptr(t), m, ptr(ws), ws.numel(), ptr(status), _lib.stream_ptr()), "convdr_keyset_build")
+        return ws, status
+
+    def _key_workspace(self, need, keep=0):
+        """the workspace of the id operations, at least `need` bytes; one that has to grow takes the first `keep` bytes over"""
+        import torch
+        ws = self._key_ws
+        if ws is None or ws.numel() < need:
+            self._key_ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+            if keep:
+                self._key_ws[:keep].copy_(ws[:keep])
+        return self._key_ws
+
+    @staticmethod
+    def _key_codes(ws, status):
+        """the two status words (the build's, the row pass's) as device int64 [2], to ride along with the caller's host read"""
+        import torch
+        return torch.cat([status, ws[:4].view(torch.int32)]).to(torch.int64)
+
+    def _key_read(self, who, parts, ws, status=None, reserved_ok=False):
+        """THE host read of an id operation: the caller's device int64 vectors `parts` and the status words (`status`, the build's,
+        where a set was built; the row pass's, in the workspace's head) in one copy.  The words go through _key_status
+        (reserved_ok: INT64_MIN in the list is padding, not an error); `parts` come back joined, as numpy int64."""
+        import torch
+        codes = ws[:4].view(torch.int32).to(torch.int64) if status is None else self._key_codes(ws, status)
+        got, words = np.split(torch.cat([*parts, codes]).cpu().numpy(), [-int(codes.numel())])
+        self._key_status(who, int(np.bitwise_or.reduce(words)) & ~(KEY_ST_LIST if reserved_ok else 0))
+        return got
+
+    @staticmethod
+    def _key_status(who, code):
+        if code & (KEY_ST_LIST | KEY_ST_COLUMN):
+            raise ValueError("%s: the id %d (INT64_MIN) is reserved; %s holds it" %
+                             (who, RESERVED_ID, "the list" if code & KEY_ST_LIST else "the index's id column"))
+        if code:
+            raise _lib.ConvdrError("%s: the key set reported status %d (2: a probe hit its bound, 8: no set in the workspace)" % (who, code))
+
+    def _member(self, who, ids, invert):
+        """(bitmap of the rows whose id is / is not in `ids`, bits set, distinct listed ids on no row): ONE host read"""
+        import torch
+        self._need_ids(who)
+        t = self._id_list(who, ids)
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        words = (n + ROW_FILTER_TILE - 1) // ROW_FILTER_TILE * 8
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t)
+            bits = torch.empty(words, dtype=torch.int32, device=self.device)
+            counts = torch.empty(2, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_member(ptr(self.ids), n, ptr(ws), ws.numel(), int(bool(invert)), ptr(bits), words, ptr(counts),
+                                            _lib.stream_ptr()), "convdr_keys_member")
+            got = self._key_read(who, [counts], ws, status)
+        return bits, int(got[0]), int(got[1])
+
+    def remove_ids(self, ids):
+        """FAISS ``IndexIDMap2.remove_ids``: every row whose id is in `ids` (int64 vector, numpy or torch, host or device;
+        repeats allowed) goes -- all chunk rows of a repeated id included --, ids that are on no row are ignored.  Returns the
+        number of rows removed.  The keep bitmap is built on the device and handed to ``keep_rows``, which compacts the rows
+        and the id column; one host read (the kept count, the missing count and the status words together).
+        ``stats``: removed, compact_windows, ids_missing (distinct listed ids found on no row)."""
+        n = self.ntotal
+        bits, kept, missing = self._member("remove_ids", ids, True)
+        removed = self.keep_rows(RowFilter(bits, n, kept))
+        self.stats["ids_missing"] = missing
+        return removed
+
+    def id_filter(self, ids, invert=False):
+        """A RowFilter of the rows whose id is in `ids` (invert: is NOT in it) -- a sub-collection, the judged pool of a topic
+        set -- for ``allowed=`` of the searches and for keep_rows.  Built on the device straight into the bitmap layout of
+        pack_row_mask; one host read (the allowed count), as for row_filter, and the same staleness rule: valid while ntotal
+        stays what it was."""
+        bits, n_allowed, _ = self._member("id_filter", ids, invert)
+        return RowFilter(bits, self.ntotal, n_allowed)
+
+    def _locate(self, who, ids, want_dup=False):
+        import torch
+        self._need_ids(who)
+        t = self._id_list(who, ids)
+        L, ptr = _lib.lib(), _lib.ptr
+        m = int(t.numel())
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t)
+            first = torch.empty(m, dtype=torch.int64, device=self.device)
+            count = torch.empty(m, dtype=torch.int32, device=self.device)
+            dup = torch.empty(m, dtype=torch.int32, device=self.device) if want_dup else None
+            _lib.check(L.convdr_keys_locate(ptr(self.ids), self.ntotal, ptr(ws), ws.numel(), ptr(t), m, ptr(first), ptr(count), ptr(dup),
+                                            _lib.stream_ptr()), "convdr_keys_locate")
+        return t, first, count, dup, ws, status
+
+    def rows_of(self, ids):
+        """Where the ids are: device (first_row int64 [m], count int32 [m]) -- the smallest row holding ids[j] or -1, and the
+        number of rows holding it.  Enqueued, no sync (so a reserved id in a device list is not an error here: it is on no
+        row, -1 and 0)."""
+        return self._locate("rows_of", ids)[1:3]
+
+    def reconstruct_ids(self, ids):
+        """FAISS ``IndexIDMap2.reconstruct`` for a list: float32 numpy [m, d_in], the first row of every id (rows_tensors of
+        rows_of).  An id that is on no row raises IndexError."""
+        first, _ = self.rows_of(ids)
+        if first.numel():
+            absent = int((first < 0).sum().item())
+            if absent:
+                raise IndexError("reconstruct_ids: %d of the %d ids are on no row" % (absent, int(first.numel())))
+        return self.rows_tensors(first).cpu().numpy()
+
+    def _emb_arg(self, who, emb, rows):
+        import torch
+        if not (isinstance(emb, torch.Tensor) and emb.dtype == torch.float32 and emb.device == self.device
+                and tuple(emb.shape) == (rows, self.d_in)):
+            raise ValueError("%s: emb must be a float32 tensor [%d, %d] on %s" % (who, rows, self.d_in, self.device))
+
+    @staticmethod
+    def _no_repeats(who, dup):
+        rep = np.nonzero(dup != np.arange(len(dup)))[0]
+        if rep.size:
+            raise ValueError("%s: the list repeats an id (position %d repeats position %d); nothing was written"
+                             % (who, int(rep[0]), int(dup[rep[0]])))
+
+    def upsert(self, ids, emb):
+        """Re-encoded passages: `emb` (device fp32 [m, d_in]) replaces the rows of `ids` (int64 [m]).  An id that is on exactly
+        one row gets that row overwritten in place (the scan copies and the max norm refreshed as by update_rows; the half
+        store's update_flags() rule applies); an id on no row is appended, in list order, with its id.  Returns
+        (n_updated, n_added).  A list that repeats an id, or an id that sits on more than one row (chunk rows: which one?),
+        raises ValueError BEFORE anything is written -- one host read, the one that also splits the list."""
+        import torch
+        t, first, count, dup, ws, status = self._locate("upsert", ids, want_dup=True)
+        m = int(t.numel())
+        self._emb_arg("upsert", emb, m)
+        fr, cnt, dp = self._key_read("upsert", [first, count.to(torch.int64), dup.to(torch.int64)], ws, status).reshape(3, m)
+        self._no_repeats("upsert", dp)
+        many = np.nonzero(cnt > 1)[0]
+        if many.size:
+            raise ValueError("upsert: the id at position %d sits on %d rows; nothing was written" % (int(many[0]), int(cnt[many[0]])))
+        upd, new = np.nonzero(cnt == 1)[0], np.nonzero(cnt == 0)[0]
+        emb = emb.contiguous()
+        with torch.cuda.device(self.device):
+            if upd.size:
+                sel = torch.as_tensor(upd, device=self.device)
+                self._overwrite_rows(torch.as_tensor(fr[upd], device=self.device), emb if upd.size == m else emb[sel])
+            if new.size:
+                sel = torch.as_tensor(new, device=self.device)
+                self.add(emb[sel], ids=t[sel])
+        return int(upd.size), int(new.size)
+
+    def _overwrite_rows(self, rows, emb):
+        """update_rows for scattered rows: the scan copies of `emb` are made by the same pass on a contiguous temporary (norms
+        folded into the max norm, the half store's flags into the update word), then every resident buffer takes its rows."""
+        import torch
+        m = int(emb.shape[0])
+        src = (emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))).contiguous()
+        t16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
+        if self._half:
+            self._store_rows(src, t16, self._scale, flags=self._uflags)
+            self._s16.index_copy_(0, rows, t16)
+            return
+        tlo = None if self._slo is None else torch.empty_like(t16)
+        self._prepare_into(src, t16, tlo)
+        self._s32.index_copy_(0, rows, src)
+        self._s16.index_copy_(0, rows, t16)
+        if tlo is not None:
+            self._slo.index_copy_(0, rows, tlo)
+
+    # -- documents by id: a document is EVERY row that carries one id (the chunk rows of a MaxP block share theirs) ----------
+    # Two device primitives (include/convdr_hip.h, "Documents by id"): all rows of the listed ids as a CSR
+    # (convdr_keys_rows_count / convdr_keys_rows_fill) and the MaxP score of (query, document) pairs (convdr_ip_score_docs).
+    def _rows_csr(self, who, t, reserved_ok=False, host=False):
+        """The CSR of the device id list `t` (int64 [m]): (start int64 [m], count int32 [m], rows int64 [total], host) --
+        convdr_keyset_build, convdr_keys_rows_count, ONE host read (total and the status words; with `host` also start, count
+        and dup_of, returned as numpy int64 [3, m]), convdr_keys_rows_fill into a list of exactly `total` entries.
+        reserved_ok: INT64_MIN in the list is padding (on no row), not an error."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        m, n = int(t.numel()), self.ntotal
+        need0 = int(L.convdr_keys_rows_workspace_bytes(m, 0))
+        with torch.cuda.device(self.device):
+            ws, status = self._keyset(who, t, need0)
+            start = torch.empty(m, dtype=torch.int64, device=self.device)
+            count = torch.empty(m, dtype=torch.int32, device=self.device)
+            dup = torch.empty(m, dtype=torch.int32, device=self.device) if host else None
+            total = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_rows_count(ptr(self.ids), n, ptr(ws), ws.numel(), ptr(t), m, ptr(start), ptr(count), ptr(dup),
+                                                ptr(total), _lib.stream_ptr()), "convdr_keys_rows_count")
+            got = self._key_read(who, [total] + ([start, count.to(torch.int64), dup.to(torch.int64)] if host else []), ws, status,
+                                 reserved_ok)
+            tot = int(got[0])
+            # the two lists of the fill lie behind what the count wrote: a larger buffer takes that part over
+            ws = self._key_workspace(int(L.convdr_keys_rows_workspace_bytes(m, tot)), keep=need0)
+            rows = torch.empty(tot, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_keys_rows_fill(ptr(self.ids), n, ptr(ws), ws.numel(), m, ptr(rows), tot, _lib.stream_ptr()),
+                       "convdr_keys_rows_fill")
+        return start, count, rows, (got[1:].reshape(3, m) if host else None)
+
+    def rows_all(self, ids):
+        """ALL rows of the listed ids (int64 vector, numpy or torch, host or device; repeats allowed): device (start int64 [m],
+        count int32 [m], rows int64 [total]).  The rows that carry ids[j] are rows[start[j] : start[j] + count[j]], ascending;
+        an id on no row has count 0; a repeated id shares the segment of its first occurrence, so total = the rows of the
+        DISTINCT listed ids.  The same bits in every run.  One host read (total, to size `rows`, and the status words; a
+        device list that holds the reserved id INT64_MIN raises ValueError there, as for remove_ids)."""
+        self._need_ids("rows_all")
+        return self._rows_csr("rows_all", self._id_list("rows_all", ids))[:3]
+
+    def doc_ordinals(self):
+        """The DocOrdinals of this index: every row's dense document number (convdr_doc_ordinals; include/convdr_hip.h,
+        "Document rank"), 0 .. ndocs - 1 in the order of the documents' first rows -- what numpy gives as
+        ``argsort(argsort(first))[inv]`` of ``np.unique(ids, return_index=True, return_inverse=True)``, the same bits in every
+        run.  Query independent: one pass over the id column, ONE host read (ndocs together with the status words).  Valid while
+        the column stays as it was; ntotal is what is checked (a stale one raises ValueError in rank_ids).  As for a RowFilter,
+        ``upsert_docs`` of documents whose chunk count changed moves rows without changing ntotal: rebuild after it."""
+        import torch
+        self._need_ids("doc_ordinals")
+        L, ptr = _lib.lib(), _lib.ptr
+        n = self.ntotal
+        need = int(L.convdr_doc_ordinals_workspace_bytes(n))
+        if not need:
+            raise ValueError("doc_ordinals: %s" % L.convdr_last_error().decode())
+        with torch.cuda.device(self.device):
+            ws = self._key_workspace(need)
+            ord_ = torch.empty(n, dtype=torch.int32, device=self.device)
+            nd = torch.empty(1, dtype=torch.int64, device=self.device)
+            _lib.check(L.convdr_doc_ordinals(ptr(self.ids), n, ptr(ws), ws.numel(), ptr(ord_), ptr(nd), _lib.stream_ptr()),
+                       "convdr_doc_ordinals")
+            ndocs = int(self._key_read("doc_ordinals", [nd], ws)[0])
+        return DocOrdinals(ord_, ndocs, n)
+
+    def reconstruct_docs(self, ids):
+        """All chunk rows of the listed documents: numpy (start int64 [m], count int32 [m], emb float32 [total, d_in]) --
+        ``rows_all`` followed by ``rows_tensors``; the rows of ids[j] are emb[start[j] : start[j] + count[j]], in ascending row
+        order.  An id on no row has count 0 (``reconstruct_ids`` raises for it)."""
+        start, count, rows = self.rows_all(ids)
+        return start.cpu().numpy(), count.cpu().numpy(), self.rows_tensors(rows).cpu().numpy()
+
+    def upsert_docs(self, ids, counts, emb):
+        """Re-encoded documents: document ids[j] (int64 [m]) now has counts[j] >= 1 chunk rows (host integers [m]), given in
+        list order in `emb` (device fp32 [sum(counts), d_in]).
+          * a document on no row is appended with its id repeated;
+          * a document that sits on counts[j] rows has them overwritten in place, in ascending row order (``_overwrite_rows``:
+            the scan copies and the max norm refreshed, the half store's update_flags() rule applies);
+          * a document on another number of rows has ALL its old rows removed -- one ``keep_rows`` for all such documents --
+            and its new rows appended, in list order among the appended documents.
+        Returns (n_in_place, n_replaced, n_added) in documents.  A list that repeats an id, or counts / emb of another shape,
+        dtype or device, raises ValueError BEFORE anything is written; one host read (total, status, and what splits the list).
+        Consequences: replaced documents move to the END of the index; and whenever a document was replaced, rows were
+        removed and others added, so a RowFilter built before the call must not be reused even where ntotal happens to come
+        out equal -- the staleness check compares ntotal only.  Side tables in row order are cut as for keep_rows."""
+        import torch
+        self._need_ids("upsert_docs")
+        t = self._id_list("upsert_docs", ids)
+        m = int(t.numel())
+        if isinstance(counts, torch.Tensor):
+            if counts.device.type != "cpu":
+                raise ValueError("upsert_docs: counts must be host integers (got a tensor on %s)" % (counts.device,))
+            counts = counts.numpy()
+        cn = np.asarray(counts)
+        if cn.ndim != 1 or cn.shape[0] != m or cn.dtype.kind not in "iu" or (m and int(cn.min()) < 1):
+            raise ValueError("upsert_docs: counts must be an integer vector [%d] with every entry >= 1 (got %s, shape %s)"
+                             % (m, cn.dtype, tuple(cn.shape)))
+        cn = cn.astype(np.int64)
+        self._emb_arg("upsert_docs", emb, int(cn.sum()))
+        if not m:
+            return 0, 0, 0
+        _, _, rows, (st, cur, dp) = self._rows_csr("upsert_docs", t, host=True)
+        self._no_repeats("upsert_docs", dp)
+
+        def spans(first, length):
+            """the concatenation of arange(first[j], first[j] + length[j]), on the device"""
+            begin = np.cumsum(length) - length
+            at = np.repeat(first, length) + (np.arange(int(length.sum()), dtype=np.int64) - np.repeat(begin, length))
+            return torch.as_tensor(at, device=self.device)
+        off = np.cumsum(cn) - cn                                   # first row of document j in emb
+        same, new = cur == cn, cur == 0
+        repl = ~same & ~new
+        emb, n = emb.contiguous(), self.ntotal
+        with torch.cuda.device(self.device):
+            if same.any():
+                self._overwrite_rows(rows[spans(st[same], cn[same])], emb if same.all() else emb[spans(off[same], cn[same])])
+            if repl.any():
+                keep = torch.ones(n, dtype=torch.bool, device=self.device)
+                keep[rows[spans(st[repl], cur[repl])]] = False
+                self.keep_rows(RowFilter(pack_row_mask(keep), n, n - int(cur[repl].sum())))
+            if not same.all():
+                app = ~same
+                who = torch.as_tensor(np.repeat(np.nonzero(app)[0], cn[app]), device=self.device)
+                self._add_keyed(emb[spans(off[app], cn[app])], None, t[who])       # (the list's ids are known clean)
+        return int(same.sum()), int(repl.sum()), int(new.sum())
+
+    def rows_tensors(self, ids):
+        """The corpus rows `ids` (integers, any shape [..]) as a device fp32 tensor [.., d_in]: the fp32 store returns the fp32
+        block's rows bit for bit, the half store its stored halves un-scaled and widened (exact); the zero columns of a
+        padded width are cut off.  An id outside [0, ntotal) raises IndexError (ids in a device tensor cost one host read)."""
+        import torch
+        t = torch.as_tensor(ids)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise IndexError("reconstruct: row ids must be integers (got %s)" % t.dtype)
+        t = t.to(torch.int64)
+        if t.numel():
+            lo, hi = (int(v) for v in torch.stack([t.min(), t.max()]).cpu())
+            if lo < 0 or hi >= self.ntotal:
+                raise IndexError("reconstruct: row ids %d..%d outside [0, ntotal = %d)" % (lo, hi, self.ntotal))
+        t = t.to(self.device)
+        if self._rows is None:
+            return torch.empty(tuple(t.shape) + (self.d_in,), dtype=torch.float32, device=self.device)
+        r = self._rows[t.reshape(-1)][:, :self.d_in]
+        if self._half:
+            r = r.float() * (1.0 / float(self._scale))     # (a power of two: exact)
+        return r.reshape(tuple(t.shape) + (self.d_in,)).contiguous()
+
+    def reconstruct(self, i):
+        """FAISS ``reconstruct``: row i as float32 numpy [d_in] (see rows_tensors)."""
+        return self.rows_tensors(int(i)).cpu().numpy()
+
+    def reconstruct_n(self, i0, ni):
+        """FAISS ``reconstruct_n``: rows [i0, i0 + ni) as float32 numpy [ni, d_in]."""
+        i0, ni = int(i0), int(ni)
+        if ni < 0 or i0 < 0 or i0 + ni > self.ntotal:
+            raise IndexError("reconstruct_n: rows [%d, %d) outside [0, ntotal = %d)" % (i0, i0 + ni, self.ntotal))
+        return self.rows_tensors(np.arange(i0, i0 + ni, dtype=np.int64)).cpu().numpy()
+
+    def reconstruct_batch(self, ids):
+        """FAISS ``reconstruct_batch``: the rows `ids` (int64 vector) as float32 numpy [len(ids), d_in]."""
+        return self.rows_tensors(ids).cpu().numpy()

@@ -204,7 +204,7 @@ def count_blocks(ann_data_dir, max_blocks=8):
 
 
 def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, group=None, timings=None, max_depth=None):
-    """search.search_one_by_one over ANY number of block files with ANY number of ranks: every rank searches the blocks
+    """block_search.search_one_by_one over ANY number of block files with ANY number of ranks: every rank searches the blocks
     plan_block_shards gives it, the per-rank top-topN lists are exchanged once (exchange_topk) and merged.
     Returns (D float64 [nq, topN], record offsets int64 [nq, topN]) as numpy, identical on every rank and equal to
     ``search_one_by_one(...)[:, :topN]`` of one process over all blocks.  Only these topN columns are defined: the
@@ -275,12 +275,12 @@ def search_blocks_sharded(ann_data_dir, index, queries, topN, max_blocks=8, grou
 
 def search_blocks_sharded_distinct(ann_data_dir, index, queries, topN, rows_per_key=None, key_map=None, max_blocks=8, group=None,
                                    timings=None, max_depth=None):
-    """search.search_distinct_one_by_one over any number of ranks: per query the topN best DISTINCT keys (documents) over all
+    """block_search.search_distinct_one_by_one over any number of ranks: per query the topN best DISTINCT keys (documents) over all
     block files, identical on every rank and equal to the one-process result.
     search_blocks_sharded runs at ROW depth m = topN * rows_per_key (<= 4096); the rows of one key may sit in blocks of
     different ranks, so nothing is de-duplicated before the exchange: it stays at depth m, i.e. rows_per_key times the bytes
     of a topN exchange (unmeasured on more than one GPU).  The merged row lists come back on the host
-    on every rank -- search_blocks_sharded's contract -- and the distinct walk (search.distinct_topk, nq x m entries) runs
+    on every rank -- search_blocks_sharded's contract -- and the distinct walk (toplists.distinct_topk, nq x m entries) runs
     there, on every rank alike.  rows_per_key=None: counted from the id files by every rank for itself
     (blocks.max_rows_per_key), no collective.  An understated rows_per_key raises ConvdrError on every rank.
     max_depth (default FlatIPIndex.MAX_K = 4096, at most DEEP_MAX_K = 65536) bounds m and is passed on to

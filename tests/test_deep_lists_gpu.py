@@ -79,6 +79,7 @@ def _outputs(nq, n_out):
 @pytest.mark.parametrize("nq,n,n_out", DISTINCT_SHAPES)
 def test_distinct_deep_equals_the_seen_pid_walk(torch_cuda, nq, n, n_out, monkeypatch):
     from convdr_amd import search as S
+    from convdr_amd import toplists              # (owns distinct_topk_device and the global it reads)
     for ki, kind in enumerate(XC.KINDS):
         D, I, key_map = XC.distinct_case(kind, nq, n, 100 * n + 10 * nq + ki)
         want = DC.seen_walk(D, I, n_out, key_map)
@@ -107,11 +108,11 @@ def test_distinct_deep_equals_the_seen_pid_walk(torch_cuda, nq, n, n_out, monkey
         # the python wrapper: one call, and a call its workspace budget splits into one query at a time
         _same(*S.distinct_topk_device(Dt, It, n_out, km), want, ("wrapper", kind, nq, n, n_out))
         if n > 4096 and nq > 1 and kind in ("mult", "oob"):
-            monkeypatch.setattr(S, "DISTINCT_DEEP_WS_BYTES", XC.distinct_ws_bytes(1, n))
+            monkeypatch.setattr(toplists, "DISTINCT_DEEP_WS_BYTES", XC.distinct_ws_bytes(1, n))
             names = _Counting.NAMES
             with _Counting() as c:
                 got = S.distinct_topk_device(Dt, It, n_out, km)
-            monkeypatch.setattr(S, "DISTINCT_DEEP_WS_BYTES", None)
+            monkeypatch.setattr(toplists, "DISTINCT_DEEP_WS_BYTES", None)
             assert c.calls == dict({x: 0 for x in names}, convdr_topk_distinct_deep=nq), c.calls
             _same(*got, want, ("wrapper/split", kind, nq, n, n_out))
 

@@ -1,8 +1,6 @@
 """Documents by id, the parts that need no GPU: the four entries are declared and exported, the size function against the
 documented regions, every refusal (argument validation happens before anything touches a device), the id checks of the new
 FlatIPIndex methods against a scripted index, and the oracle of tests/doc_cases.py against brute force."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,10 +8,10 @@ import torch
 
 from convdr_amd import _lib
 from convdr_amd import search as S
+from tests import capi_decl
 from tests import doc_cases as DC
 from tests import key_cases as K
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("convdr_keys_rows_workspace_bytes", "convdr_keys_rows_count", "convdr_keys_rows_fill", "convdr_ip_score_docs")
 METHODS = ("rows_all", "score_ids", "score_ids_tensors", "search_docs", "reconstruct_docs", "upsert_docs")
 P = 1 << 20                     # a pointer that is never dereferenced on the host (16-byte aligned)
@@ -23,11 +21,9 @@ BIG = 1 << 40                   # a workspace size that fits every call
 
 def test_header_ctypes_and_exports_agree_on_the_entries():
     L = _lib.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "convdr_hip.h")).read(), flags=re.S)
     for name in ENTRIES:
         assert name in _lib.exported_symbols() and hasattr(L, name)
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
-        assert len(params.split(",")) == len(_lib._SIGNATURES[name][1]), name
+        assert len(capi_decl.params(name).split(",")) == len(_lib._SIGNATURES[name][1]), name
 
 
 def _slots(m):

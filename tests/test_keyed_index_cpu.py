@@ -1,8 +1,6 @@
 """Row ids, the parts that need no GPU: the five entries are declared and exported, every refusal (argument validation happens
 before anything touches a device), the workspace size against the documented regions, the argument checks of
 FlatIPIndex.add(ids=) and of the id methods against a scripted index, and the oracle of tests/key_cases.py against brute force."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,9 +8,9 @@ import torch
 
 from convdr_amd import _lib
 from convdr_amd import search as S
+from tests import capi_decl
 from tests import key_cases as K
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("convdr_keyset_workspace_bytes", "convdr_keyset_build", "convdr_keys_member", "convdr_keys_locate", "convdr_ip_compact_ids")
 P = 1 << 20                     # a pointer that is never dereferenced on the host (16-byte aligned)
 N = 100000
@@ -22,11 +20,9 @@ BIG = 1 << 40                   # a workspace size that fits every set
 
 def test_header_ctypes_and_exports_agree_on_the_entries():
     L = _lib.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "convdr_hip.h")).read(), flags=re.S)
     for name in ENTRIES:
         assert name in _lib.exported_symbols() and hasattr(L, name)
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
-        assert len(params.split(",")) == len(_lib._SIGNATURES[name][1]), name
+        assert len(capi_decl.params(name).split(",")) == len(_lib._SIGNATURES[name][1]), name
 
 
 def _slots(m):

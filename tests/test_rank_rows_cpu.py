@@ -4,7 +4,6 @@ device), the workspace layout against tests/golden/ip_rank_workspace_layout.json
 the argument checks and the host ladder of FlatIPIndex.rank_rows against a scripted pass."""
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 
 from convdr_amd import _lib
 from convdr_amd import search as S
+from tests import capi_decl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, OVERFLOW, RANGE = 0, 1, 4
@@ -20,11 +20,9 @@ ENTRIES = ("convdr_ip_score_rows", "convdr_ip_rank_workspace_bytes", "convdr_ip_
 
 def test_header_ctypes_and_exports_agree_on_the_entries():
     L = _lib.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "convdr_hip.h")).read(), flags=re.S)
     for name in ENTRIES:
         assert name in _lib.exported_symbols() and hasattr(L, name)
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
-        assert len(params.split(",")) == len(_lib._SIGNATURES[name][1]), name
+        assert len(capi_decl.params(name).split(",")) == len(_lib._SIGNATURES[name][1]), name
 
 
 def _rank(L, store=1, np_=5, scale=4.0, centre=None, n=100000, d=768, cap=4096, bits=None, words=0, n_allowed=0):

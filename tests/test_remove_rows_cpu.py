@@ -1,8 +1,6 @@
 """Removing rows, the parts that need no GPU: the three convdr_ip_compact_* entries are declared and exported, every refusal
 (argument validation happens before anything touches a device), the workspace size against the documented region order, and
 the argument checks of FlatIPIndex.keep_rows / remove_rows / reconstruct* against a scripted index."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,8 +8,8 @@ import torch
 
 from convdr_amd import _lib
 from convdr_amd import search as S
+from tests import capi_decl
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("convdr_ip_compact_workspace_bytes", "convdr_ip_compact_plan", "convdr_ip_compact_rows")
 N = 100000
 WORDS = (N + 255) // 256 * 8
@@ -20,11 +18,9 @@ BITS = 1 << 20                  # a pointer that is never dereferenced on the ho
 
 def test_header_ctypes_and_exports_agree_on_the_entries():
     L = _lib.lib()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "convdr_hip.h")).read(), flags=re.S)
     for name in ENTRIES:
         assert name in _lib.exported_symbols() and hasattr(L, name)
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1)
-        assert len(params.split(",")) == len(_lib._SIGNATURES[name][1]), name
+        assert len(capi_decl.params(name).split(",")) == len(_lib._SIGNATURES[name][1]), name
 
 
 def _rows(L, row_bytes=3072, n=N, bits=BITS, words=WORDS, window=1024):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Cost of the two deep list kernels on one GPU, each beside the route the same job took before them.
 
-(a) convdr_topk_distinct_deep (search.distinct_topk_device for n > 4096) against the device-to-host copy of the ranked lists +
-    search.distinct_topk (the numpy walk), the only route lists of that length had.
+(a) convdr_topk_distinct_deep (toplists.distinct_topk_device for n > 4096) against the device-to-host copy of the ranked lists +
+    toplists.distinct_topk (the numpy walk), the only route lists of that length had.
 (b) convdr_topk_merge_deep (parallel.merge_rank_topk for k > 4096) against the stable descending torch.sort of the
     rank-ordered concatenation on the device + two gathers.
 
@@ -84,7 +84,7 @@ def main():
                 f.write("\n".join(lines) + "\n")
     say("# deep_distinct_time: %s; ms per call (device events around the whole call), %d rounds of (old, new, old)"
         % (torch.cuda.get_device_name(0), args.rounds))
-    say("# (a) first entry per key: copy to the host + search.distinct_topk (numpy)  vs  convdr_topk_distinct_deep")
+    say("# (a) first entry per key: copy to the host + toplists.distinct_topk (numpy)  vs  convdr_topk_distinct_deep")
     for nq, n, n_out, keys in DISTINCT_SHAPES:
         D, I = ranked_lists(nq, n, keys, 1000 + n + nq)
 

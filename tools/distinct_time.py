@@ -3,7 +3,7 @@
 the same length from the same process -- the two-way merge is the step search_one_by_one pays per block, the yardstick.
 
 Per shape: synthetic ranked lists with ties and keys on 1..4 rows (through a key map), the kernel's result asserted equal to
-search.distinct_topk (numpy), both calls warmed up, then `--rounds` rounds of three windows each -- merge, distinct, merge
+toplists.distinct_topk (numpy), both calls warmed up, then `--rounds` rounds of three windows each -- merge, distinct, merge
 again -- every window `reps` launches between two device events, at least `--window` seconds long.  The second merge
 series prices the noise ("spread": distance between the medians of the two merge series).  Times are per launch.
 
@@ -86,7 +86,7 @@ def main():
             _lib.check(L.convdr_topk_distinct(_lib.ptr(Dt), _lib.ptr(It), n, n, nq, _lib.ptr(km), km.numel(), n_out, _lib.ptr(Do),
                                               _lib.ptr(Io), _lib.ptr(Ko), n_out, _lib.ptr(counts), st), "convdr_topk_distinct")
 
-        def merge():        # two lists of n entries -> the complete merge of 2n, as search.merge_topk_device runs it per block
+        def merge():        # two lists of n entries -> the complete merge of 2n, as toplists.merge_topk_device runs it per block
             _lib.check(L.convdr_topk_merge(_lib.ptr(Dt), _lib.ptr(It), n, n, _lib.ptr(Dt), _lib.ptr(It), n, n, nq, 2 * n, _lib.ptr(Dm),
                                            _lib.ptr(Im), 2 * n, st), "convdr_topk_merge")
         distinct()

@@ -7,7 +7,7 @@ beside the host route, on one GPU, in one process.
            list and 10 others, grades -1..3.
   device   judge_run(D, I, qrels, key_map, cutoffs=(3, 10, 100)) and, separately, run_negatives on its K and labels: device
            events around the calls, medians and min..max of `--rounds` windows after a warm-up.  mean() (the one host read) apart.
-  host     what a caller does without these kernels: D.cpu(), I.cpu(), convdr_amd.search.distinct_topk (numpy), then the oracle of
+  host     what a caller does without these kernels: D.cpu(), I.cpu(), convdr_amd.toplists.distinct_topk (numpy), then the oracle of
            the tests (tests/judge_cases.py: dict lookups, plain loops) for labels, measures and negatives.  The oracle is plain
            Python, so at the deeper shapes it is run on the first `--host-queries` queries only and the time for all of them is
            that figure scaled by nq / queries (marked "scaled").
