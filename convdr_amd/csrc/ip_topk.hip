@@ -1401,6 +1401,8 @@ static int launch_scan_mark(const ScanArgs& a, int tile, int kind, hipStream_t s
 #include "ip_docs.hpp"
 // document rank: dense document numbers of the id column, the marking band scan's finish (convdr_doc_ordinals, convdr_ip_rank_docs)
 #include "ip_docrank.hpp"
+// the digest a snapshot file is checked against, on the device and on the host (convdr_digest_rows, convdr_digest_host)
+#include "ip_digest.hpp"
 // judging a run against the qrels: labels, rank measures, negatives (convdr_run_*)
 #include "run_judge.hpp"
 

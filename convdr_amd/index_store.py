@@ -1,6 +1,7 @@
 """The rows a FlatIPIndex holds: the resident buffers (fp32 block, scan copy, remainder copy, id column) and everything that writes
 them or speaks only about rows and ids -- add / update / remove, row filters, the id operations, reading rows back.  The questions
 asked of the rows (search, range, score, rank) are ``search.FlatIPIndex(_IndexStore)``; nothing here calls into it."""
+import functools
 import os
 
 import numpy as np
@@ -514,7 +515,12 @@ class _IndexStore:
             # staging buffer bi may be refilled once its previous H2D copy has completed.  The events live with the
             # buffers (module-level, shared by every index of the process): the last copies of one add() are still in
             # flight when the next add() starts filling (1 run in ~500 put rows of a second block into the first
-            # before they did, tests/test_ip_search_gpu.py::test_back_to_back_streamed_adds_keep_their_rows)
+            # before they did, tests/test_ip_search_gpu.py::test_back_to_back_streamed_adds_keep_their_rows).
+            # The rule, for every user of the buffers (this loop, _load_bytes, and save's _save_bytes, which runs them the
+            # other way): freed[bi] is the event of the LAST device copy that read or wrote buffer bi, recorded on the
+            # stream that ran it; whoever touches the buffer next waits for it first (the host with synchronize(), a copy
+            # stream with wait_event()); and nobody returns to its caller while a host thread still reads or writes a
+            # buffer.  A save therefore leaves every freed[bi] recorded and its file writes returned.
             if freed[bi] is not None:
                 freed[bi].synchronize()
             buf = stage[bi].numpy()[:e - s]
@@ -1051,3 +1057,293 @@ class _IndexStore:
     def reconstruct_batch(self, ids):
         """FAISS ``reconstruct_batch``: the rows `ids` (int64 vector) as float32 numpy [len(ids), d_in]."""
         return self.rows_tensors(ids).cpu().numpy()
+
+    # -- snapshots (FAISS write_index / read_index): one verified file, snapshot.py; the digest is convdr_digest_rows --------
+    # What is written: the re-score rows at the resident width, the id column, the centre, and in the header the scale, the max
+    # norm's bits and the x3_first flag.  The scan copy and the remainder copy are a pure function of (row, centre, scale) and
+    # are rebuilt by load as add builds them; RowFilter / DocOrdinals are derived and stale across a save / load.
+    def _sections(self):
+        """[(name, device tensor of the used rows or None, rows, row_bytes)] of what a snapshot holds, in file order"""
+        secs = [("rows", self._rows, self._n, self.d * (2 if self._half else 4))]
+        if self._sid is not None:
+            secs.append(("ids", self.ids, self._n, 8))
+        if self._centre is not None:
+            secs.append(("centre", self._centre, 1, self.d * 4))
+        return secs
+
+    def _digest_into(self, t, rows, row_bytes, word0, window_rows, out):
+        """convdr_digest_rows of the first `rows` rows of `t` into out int64 [windows, 2] (the bytes of uint64); enqueued"""
+        if rows:
+            _lib.check(_lib.lib().convdr_digest_rows(_lib.ptr(t), int(rows), int(row_bytes), int(word0), int(window_rows), _lib.ptr(out),
+                                                     _lib.stream_ptr()), "convdr_digest_rows")
+
+    def _digest_sections(self, secs, window_rows, word0_rows=0):
+        """One launch per section, every section's windows in ONE device tensor int64 [total + 1, 2] whose last row holds the
+        max norm's bits, so that one host read fetches everything: -> (tensor, {name: (first window, end window)})"""
+        import torch
+        spans, at = {}, 0
+        for name, _t, rows, _rb in secs:
+            c = (rows + window_rows - 1) // window_rows
+            spans[name] = (at, at + c)
+            at += c
+        dg = torch.zeros((at + 1, 2), dtype=torch.int64, device=self.device)
+        for name, t, rows, rb in secs:
+            w0 = 0 if name == "centre" else word0_rows * (rb // 8)
+            self._digest_into(t, rows, rb, w0, window_rows, dg[spans[name][0]:spans[name][1]])
+        dg[at, :1].copy_(self._max_norm.view(torch.int32))
+        return dg, spans
+
+    @staticmethod
+    def _digest_read(dg, spans):
+        """THE host read: ({name: [(A, B)]}, max-norm bits)"""
+        host = dg.cpu().numpy().astype(np.uint64)
+        return ({name: [(int(host[j, 0]), int(host[j, 1])) for j in range(a, b)] for name, (a, b) in spans.items()},
+                int(host[-1, 0]) & 0xffffffff)
+
+    def fingerprint(self):
+        """What this index holds, as a small dict that is equal for equal content whatever sequence of add / reserve / removal
+        produced it: d_in, storage, precision, center, n, the scale's and the max norm's fp32 bits (hex), and ONE digest
+        (A, B) each of the re-score rows, the id column and the centre (None where the index has none) -- convdr_digest_rows
+        over the resident buffers, word0 = 0, one window; no host copy of the rows, one host read.  Not cryptographic."""
+        import struct
+        import torch
+        with torch.cuda.device(self.device):
+            dg, spans = self._digest_sections(self._sections(), max(1, self._n))
+            got, mn = self._digest_read(dg, spans)
+        fp = {"d_in": self.d_in, "storage": self.storage, "precision": self.precision, "center": self.center, "n": self._n,
+              "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "%08x" % mn}
+        for name in ("rows", "ids", "centre"):
+            fp[name] = None if name not in got else (got[name][0] if got[name] else (0, 0))
+        return fp
+
+    def _stage_bytes(self, total):
+        """the pinned staging buffers as flat byte views (torch, numpy), their events, the chunk size in bytes, the copy stream"""
+        import torch
+        per32 = max(1, int(self.host_chunk_bytes) // (4 * self.d))
+        nbuf = max(2, int(self.host_stage_buffers))
+        stage, freed = _staging(self.device, min(per32, (int(total) + 4 * self.d - 1) // (4 * self.d)), self.d, nbuf)
+        flat = [b.view(torch.uint8).view(-1) for b in stage]
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        return flat, [f.numpy() for f in flat], freed, per32 * self.d * 4, self._copy_stream
+
+    def _copy_threads(self):
+        avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        return max(1, min(int(self.host_copy_threads), avail))
+
+    def _save_bytes(self, t, fd, offset):
+        """Device tensor `t` (contiguous) -> the file, bytes [offset, offset + t.nbytes): the mirror image of _stream_rows.  D2H
+        copies of host_chunk_bytes on the copy stream into the pinned staging buffers, host_stage_buffers - 1 of them in flight;
+        the pool's threads os.pwrite slices of a landed chunk while the next chunks cross PCIe.  A buffer is reused only after
+        its D2H has completed AND its file writes have returned; on return every write has returned and every freed[bi] is a
+        recorded event (the rule beside the events in _stream_rows)."""
+        import torch
+        from .snapshot import _pwrite_all
+        if t is None or not t.numel():
+            return
+        src = t.reshape(-1).view(torch.uint8)
+        total = int(src.numel())
+        flat, flat_np, freed, cap, cs = self._stage_bytes(total)
+        nbuf, threads = len(flat), self._copy_threads()
+        pool = _copy_pool(threads * (nbuf - 1), self.device)
+        cs.wait_stream(torch.cuda.current_stream())         # (the rows are what the main stream has made of them so far)
+        chunks = [(s, min(total, s + cap)) for s in range(0, total, cap)]
+        events, writes = {}, {}
+
+        def land(ci):
+            """chunk ci has crossed PCIe: its file writes, `threads` slices on the pool"""
+            s, e = chunks[ci]
+            events.pop(ci).synchronize()
+            buf = flat_np[ci % nbuf]
+            step = ((e - s + threads - 1) // threads + 4095) // 4096 * 4096
+            writes[ci] = [pool.submit(_pwrite_all, fd, buf[a:min(e - s, a + step)], offset + s + a) for a in range(0, e - s, step)]
+
+        def written(ci):
+            for f in writes.pop(ci):
+                f.result()
+        try:
+            for ci, (s, e) in enumerate(chunks):
+                bi = ci % nbuf
+                if ci >= nbuf:
+                    written(ci - nbuf)                      # (the buffer's last file writes have returned)
+                elif freed[bi] is not None:
+                    cs.wait_event(freed[bi])                # (an earlier add's H2D copy may still be reading the buffer)
+                with torch.cuda.stream(cs):
+                    flat[bi][:e - s].copy_(src[s:e], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(cs)
+                freed[bi] = events[ci] = ev
+                if ci >= nbuf - 1:
+                    land(ci - (nbuf - 1))
+            for ci in range(max(0, len(chunks) - (nbuf - 1)), len(chunks)):
+                land(ci)
+        finally:
+            for ev in events.values():                      # (after an error, too: no copy in flight, no thread in a buffer)
+                ev.synchronize()
+            err = None
+            for ci in sorted(writes):
+                for f in writes[ci]:
+                    try:
+                        f.result()
+                    except BaseException as e:              # noqa: PERF203
+                        err = err or e
+            writes.clear()
+        if err is not None:
+            raise err
+
+    def _load_bytes(self, fd, offset, dst):
+        """the file's bytes [offset, offset + dst.nbytes) -> the device tensor `dst` (contiguous) through the staging buffers,
+        one chunk after the other (the id column: 8 bytes per row beside the rows' 1.5 - 3 KB)"""
+        import torch
+        from .snapshot import pread_into
+        flat_dst = dst.reshape(-1).view(torch.uint8)
+        total = int(flat_dst.numel())
+        if not total:
+            return
+        flat, flat_np, freed, cap, cs = self._stage_bytes(total)
+        main = torch.cuda.current_stream()
+        cs.wait_stream(main)
+        for ci, s in enumerate(range(0, total, cap)):
+            e, bi = min(total, s + cap), ci % len(flat)
+            if freed[bi] is not None:
+                freed[bi].synchronize()
+            pread_into(fd, memoryview(flat_np[bi][:e - s]), offset + s)
+            with torch.cuda.stream(cs):
+                flat_dst[s:e].copy_(flat[bi][:e - s], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(cs)
+            freed[bi] = ev
+            main.wait_event(ev)
+
+    def save(self, path, window_rows=65536):
+        """FAISS ``write_index``: the index as ONE verified snapshot file (snapshot.py; layout in include/convdr_hip.h).  Per
+        section -- rows, ids, centre -- one convdr_digest_rows launch over the used rows gives the per-window digests the
+        header stores (windows of `window_rows` rows), then the bytes go D2H through the process-wide pinned staging buffers
+        and to the file with positioned writes (_save_bytes).  One host read (the digests and the max norm's bits).  The file
+        is written to path + ".tmp" and renamed: a failed save leaves an existing snapshot untouched.  Returns when the file
+        is in place.  ``stats``: save_bytes (the file's size), save_s, save_fsync_s (the share of save_s spent in fsync)."""
+        import struct
+        import time
+        import torch
+        from . import snapshot
+        t0 = time.perf_counter()
+        w = int(window_rows)
+        if w < 1:
+            raise ValueError("save: window_rows must be >= 1 (got %d)" % w)
+        secs = self._sections()
+        meta = {"d_in": self.d_in, "d": self.d, "storage": self.storage, "precision": self.precision, "center": self.center,
+                "n": self._n, "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "0" * 8,
+                "x3_first": bool(self._x3_first), "has_ids": self._sid is not None, "window_rows": w}
+        timings = {}
+        with torch.cuda.device(self.device):
+            dg, spans = self._digest_sections(secs, w)
+
+            def finish():
+                got, mn = self._digest_read(dg, spans)
+                meta["max_norm"] = "%08x" % mn              # (fixed width: the JSON's length was known before)
+                return got
+            size = snapshot.write_snapshot(path, meta, [(name, rows * rb, rb, functools.partial(self._save_section, t))
+                                                        for name, t, rows, rb in secs], finish, timings)
+        self.stats["save_bytes"], self.stats["save_s"], self.stats["save_fsync_s"] = size, time.perf_counter() - t0, timings["fsync_s"]
+
+    def _save_section(self, t, fd, offset):
+        self._save_bytes(t, fd, offset)
+        return None                                         # (the digests come with finish(): one host read for all sections)
+
+    @classmethod
+    def load(cls, path, device=None, rows=None, reserve=None, verify=True, precision=None, cap=4096, rank_target=0, prepin=True,
+             chunk_bytes=None):
+        """FAISS ``read_index``: the index a snapshot file holds (``save``).  Constructed from the header; the centre, the scale,
+        the max norm's bits and the x3_first flag are the saved ones (never re-derived from the rows); storage for
+        max(n, reserve) rows (``reserve`` given: kept as a reservation, as by reserve()); the rows stream from the file with
+        positioned reads through the staging buffers exactly as add(BlockView) streams a block -- the fp32 store makes its scan
+        copy per chunk (convdr_ip_prepare_block*), the half store's halves land in the store and no kernel runs --, then the ids.
+        verify: one convdr_digest_rows launch per section over what landed in HBM, compared with the header's per-window digests
+        in ONE host read at the end; a mismatch raises ConvdrError naming the section and the window, and no index is returned.
+        precision: overrides the saved one (the fp32 store: any of its precisions, the scale re-derived from the saved max norm
+        when the scan kind changes, as _rebuild_scaled does; the half store: its own three).
+        rows=(r0, r1): that slice only -- one rank's share of a shared snapshot; r0 a multiple of the file's window_rows, r1 a
+        multiple of it or n (else ValueError); only the covered windows are verified; centre, scale and max norm stay the whole
+        snapshot's (an upper bound is all the certificate needs, as after remove_rows).
+        chunk_bytes: the staging chunk (default host_chunk_bytes).  ``stats``: load_bytes, load_s."""
+        import struct
+        import time
+        import torch
+        from . import snapshot
+        t0 = time.perf_counter()
+        h = snapshot.read_header(path)
+        n_file, w, secs = int(h["n"]), int(h["window_rows"]), h["sections"]
+        r0, r1 = (0, n_file) if rows is None else (int(rows[0]), int(rows[1]))
+        if not (0 <= r0 <= r1 <= n_file) or r0 % w or (r1 % w and r1 != n_file):
+            raise ValueError("load: rows=(%d, %d) must lie in [0, n = %d], r0 a multiple of the file's window_rows = %d and r1 a "
+                             "multiple of it or n" % (r0, r1, n_file, w))
+        half = h["storage"] == "fp16"
+        precision = h["precision"] if precision is None else precision
+        if precision not in _KINDS or (not half and precision == "fp16x2"):
+            raise ValueError("load: precision %r is none of the %s store's" % (precision, h["storage"]))
+        idx = cls(int(h["d_in"]), device=device, cap=cap, rank_target=rank_target, precision=precision,
+                  center=None if half else bool(h["center"]), prepin=prepin, storage=h["storage"])
+        n, esz = r1 - r0, 2 if half else 4
+        rb = idx.d * esz
+        want = {"rows": (n_file * rb, rb)}
+        if h["has_ids"]:
+            want["ids"] = (n_file * 8, 8)
+        if "centre" in secs:
+            want["centre"] = (idx.d * 4, idx.d * 4)
+        for name, (nbytes, rbytes) in want.items():
+            if name not in secs or (secs[name]["bytes"], secs[name]["row_bytes"]) != (nbytes, rbytes) or int(h["d"]) != idx.d:
+                raise _lib.ConvdrError("load %s: section %r does not have the %d bytes of %d-byte rows the header's n, d and storage "
+                                       "imply" % (path, name, nbytes, rbytes))
+        if chunk_bytes is not None:
+            idx.host_chunk_bytes = int(chunk_bytes)
+        L = _lib.lib()
+        mn_bits = int(h["max_norm"], 16)
+        scale = struct.unpack("<f", struct.pack("<I", int(h["scale"], 16)))[0]
+        if not half and idx.kind != _KINDS[h["precision"]]:
+            # another scan kind: the scale that fits the saved max norm, as _rebuild_scaled derives it (bf16 has none)
+            scale = float(L.convdr_ip_f16_scale(struct.unpack("<f", struct.pack("<I", mn_bits))[0])) if idx.kind == "f16" else 1.0
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            with torch.cuda.device(idx.device):
+                if "centre" in secs:
+                    c = np.empty(idx.d, dtype=np.float32)
+                    snapshot.pread_into(fd, memoryview(c).cast("B"), secs["centre"]["offset"])
+                    idx._centre = torch.from_numpy(c).to(idx.device)
+                idx._scale, idx._x3_first = scale, bool(h["x3_first"])
+                # (copy_ INTO the tensor: the half store's max norm is a view of its (norm, flags) triple and must stay one)
+                idx._max_norm.copy_(torch.tensor([mn_bits - (1 << 32) if mn_bits >> 31 else mn_bits], dtype=torch.int32).view(torch.float32))
+                room = max(n, int(reserve or 0))
+                if room:
+                    idx.reserve(room)
+                    idx._reserved = reserve is not None
+                if n:
+                    src = snapshot.FileRows(fd, secs["rows"]["offset"], rb, r0, n, idx.d)
+                    if half:
+                        idx._stream_rows(src, idx._s16[:n], src.read_rows_into, idx.host_chunk_bytes, lambda ci, s, e: None, t0)
+                    else:
+                        p32, p16, plo = idx._s32[:n], idx._s16[:n], None if idx._slo is None else idx._slo[:n]
+
+                        def prepare(ci, s, e):              # (never _first_rows: centre and scale are the saved ones)
+                            idx._prepare_into(p32[s:e], p16[s:e], None if plo is None else plo[s:e])
+                        idx._stream_rows(src, p32, src.read_rows_into, idx.host_chunk_bytes, prepare, t0)
+                idx._n = n
+                if h["has_ids"]:
+                    idx._sid, idx._sid_spare = torch.empty(max(room, 0), dtype=torch.int64, device=idx.device), None
+                    idx._load_bytes(fd, secs["ids"]["offset"] + r0 * 8, idx._sid[:n])
+                if verify:
+                    dg, spans = idx._digest_sections(idx._sections(), w, word0_rows=r0)
+                    got, _ = idx._digest_read(dg, spans)
+                    for name in sorted(got):
+                        first = 0 if name == "centre" else r0 // w
+                        for j, pair in enumerate(got[name]):
+                            if pair != secs[name]["digests"][first + j]:
+                                raise _lib.ConvdrError("load %s: section %r, window %d: what landed on the device has digest %016x %016x, "
+                                                       "the header says %016x %016x; no index is returned"
+                                                       % ((path, name, first + j) + pair + secs[name]["digests"][first + j]))
+                else:
+                    torch.cuda.current_stream().synchronize()       # (the call returns when the index is in place)
+        finally:
+            os.close(fd)
+        idx.stats["load_bytes"] = sum(secs[name]["bytes"] if name == "centre" else n * want[name][1] for name in want)
+        idx.stats["load_s"] = time.perf_counter() - t0
+        return idx

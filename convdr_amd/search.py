@@ -22,6 +22,7 @@ from .block_search import (EvalDevQuery, _check_distinct_certificate, _load_coll
                            search_distinct_one_by_one, search_one_by_one)
 from .index_store import (_HALF_PRECISIONS, _KINDS, HALF_NORM_LIMIT, KEY_ST_COLUMN, KEY_ST_LIST, KEY_ST_NOSET, KEY_ST_PROBE, RESERVED_ID,
                           ROW_FILTER_TILE, DocOrdinals, RowFilter, _IndexStore, pack_row_mask)
+from .snapshot import read_header as snapshot_info, verify_file as verify_snapshot
 from .staging import (_NUMA, _POOLS, _STAGING, _STAGING_BUILD, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _on_cpus, _staging, _staging_key,
                       gpu_numa_cpus, pinned_near)
 from .toplists import (DEEP_MAX_K, DEEP_WS_BYTES, DISTINCT_DEEP_WS_BYTES, DISTINCT_KERNEL_MAX, MAX_K, MERGE_KERNEL_MAX, PAD_SCORE,

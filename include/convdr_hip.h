@@ -472,6 +472,45 @@ int convdr_ip_rank_docs(int store, const float* q_f32, int np, const int64_t* ta
                         size_t workspace_bytes, int64_t* rank, double* X, int64_t* counts, int64_t* above, int32_t* status,
                         convdr_stream_t stream);
 
+/* Digest and snapshot file: a resident index (rows in their compacted order, id column, centre, scale, max norm) written to ONE
+ * file and read back (FAISS: write_index / read_index), every byte covered by a digest that is checked where the bytes land.
+ *   the digest   a buffer is m little-endian 64-bit words w[0 .. m) with a starting word index word0.  With g_i = word0 + i + 1,
+ *                mix = the mixer of "Row ids" above, K1 = 0x9e3779b97f4a7c15, K2 = 0xd6e8feb86659fd93, all arithmetic mod 2^64:
+ *                  A = sum_i mix(w_i ^ (g_i * K1)),   B = sum_i mix(rotl(w_i, 29) ^ (g_i * K2)).
+ *                The digest is (A, B); the empty buffer gives (0, 0).  POSITION-DEPENDENT: swapped, shifted or stale rows show
+ *                up, and so does a window of zeros at the wrong place.  ADDITIVE: the digest of a concatenation is the wrapping
+ *                sum of the parts' digests taken at their own word0, so any split into windows, chunks or workgroups gives the
+ *                same bits; the device sums with integer atomics and is deterministic.  NOT cryptographic: it catches
+ *                accidents, not an adversary.
+ * convdr_digest_rows   buf: device memory, 8-byte aligned (it need not be 16-byte aligned), n_rows rows of row_bytes bytes,
+ *                row_bytes > 0 and a multiple of 8 (at most 2^20; n_rows at most 2^40).  Window j covers rows [j * window_rows,
+ *                min(n_rows, (j + 1) * window_rows)), window_rows >= 1 (at most 2^30 windows); its first word has index word0 +
+ *                j * window_rows * row_bytes / 8.  out: device uint64 [ceil(n_rows / window_rows)][2] = (A, B) per window; the
+ *                entry zeroes it on `stream` and overwrites it, nothing is read from it.  One launch: 16-byte streaming loads
+ *                with an 8-byte head / tail where a window starts or ends on an odd word, two 64-bit sums per lane, one pair of
+ *                64-bit atomic adds per workgroup.  n_rows == 0: returns 0, launches nothing, writes nothing (buf, out may be NULL).
+ * convdr_digest_host   the same function of n_bytes bytes of HOST memory (n_bytes % 8 == 0, any alignment), out[2] = (A, B) on
+ *                the host.  No GPU is touched; it may be called from several threads at once.
+ * Arguments are validated before anything touches a device: a refusal is a negative code and a convdr_last_error message that
+ * names the entry; no allocation, no sync.
+ *
+ * The snapshot file (one file, little-endian; convdr_amd/snapshot.py writes and reads it):
+ *   bytes 0-63   "CONVDRIX" | u32 version = 1 | u32 0 | u64 JSON length | u64 A | u64 B = the digest (word0 = 0) of the JSON bytes
+ *                zero padded to a multiple of 8 | 24 zero bytes
+ *   from byte 64 the JSON object: d_in, d (the resident width: d_in rounded up to a multiple of 64), storage ("fp32" | "fp16"),
+ *                precision, center, n, scale and max_norm (fp32 bit patterns as 8 hex digits), x3_first, has_ids, window_rows,
+ *                sections = {name: {offset, bytes, row_bytes, digests}}; digests = one [A, B] per window of window_rows rows as
+ *                16-digit hex strings, window j of a section taken at word0 = j * window_rows * row_bytes / 8
+ *   sections     each at an offset that is a multiple of 4,096: "rows" n x d elements of the re-score rows at the resident width
+ *                (fp32 store: the fp32 block; half store: the resident halves, i.e. already multiplied by the saved scale),
+ *                "ids" n x 8 bytes (int64) when has_ids, "centre" ONE row of d x 4 bytes (one window) when centred
+ *   not stored   the scan copy and the remainder copy: a pure function of (row, centre, scale), rebuilt by the loader
+ * A writer writes the sections first and the header last into a temporary file and renames it; a reader refuses a bad magic,
+ * an unknown version, a header digest mismatch, a section that runs past the end of the file and a truncated file. */
+int convdr_digest_rows(const void* buf, int64_t n_rows, int64_t row_bytes, uint64_t word0, int64_t window_rows, uint64_t* out,
+                       convdr_stream_t stream);
+int convdr_digest_host(const void* buf, int64_t n_bytes, uint64_t word0, uint64_t* out);
+
 /* Instrumentation of the last convdr_ip_search on this workspace (device uint32 [nq] each):
  * candidates emitted by the scan / size of the exactly re-scored band. */
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
