@@ -2,14 +2,14 @@
 //
 // The shallow finish (k_ip_cut / k_ip_select / k_ip_finish) holds a query's candidate list and its re-scored band in LDS,
 // which ends at 8,192 entries.  Here the same three phases run through global memory, one workgroup per query:
-//   k_ip_cut_deep     radix select of S~(k) with the list left in global memory (four passes over it), the same eps /
-//                     cut / status / tau_retry expressions as k_ip_cut, the band compacted into a SECOND pair of arrays
+//   k_ip_cut_deep     radix select of S~(k) with the list left in global memory (four passes over it), the eps and the
+//                     verdict of k_ip_cut (ip_certify.hpp), the band compacted into a SECOND pair of arrays
 //   k_ip_rescore      unchanged (it always worked on a band in global memory, for any cap)
 //   k_ip_select_deep  radix select of the k-th exact score on the high key word, survivors compacted into a third
 //                     array, ordered by a tiled bitonic network, D / I written with FAISS padding
 // and the threshold comes from COMPLETE scores of a row sample (k_tau_select_deep), because the TOP2 sample of the shallow
 // plan keeps two scores per 64 rows and cannot represent a rank above n / 128.
-// The certificate is k_ip_cut's, expression for expression: it never depended on where the list lives.
+// The certificate is k_ip_cut's (the proof is above that kernel): it never depended on where the list lives.
 #pragma once
 
 namespace convdr {
@@ -52,15 +52,13 @@ __global__ void __launch_bounds__(IP_DEEP_THREADS) k_ip_cut_deep(int64_t n, int 
                                                                  const uint32_t* __restrict__ list_id,
                                                                  const float* __restrict__ list_s,
                                                                  uint32_t* __restrict__ band_id,
-                                                                 const float* __restrict__ tau, const float* __restrict__ qnorm,
-                                                                 const float* __restrict__ p_max_norm, float eps_coef,
-                                                                 float eps_abs, float p_scale, float norm_limit,
+                                                                 const float* __restrict__ tau, const IpBand band,
                                                                  uint32_t* __restrict__ m_out, int32_t* __restrict__ status,
                                                                  float* __restrict__ tau_retry) {
   __shared__ SelectScratch sc;
   __shared__ uint32_t sh_m;
   const int q = blockIdx.x;
-  const uint32_t cnt = counts[(int64_t)q * IP_COUNT_STRIDE];
+  const uint32_t cnt = ip_hits(counts, q);
   if (threadIdx.x == 0) counts_packed[q] = cnt;
   const int c = cnt < (uint32_t)cap ? (int)cnt : cap;
   const float* ls = list_s + (int64_t)q * cap;
@@ -70,8 +68,8 @@ __global__ void __launch_bounds__(IP_DEEP_THREADS) k_ip_cut_deep(int64_t n, int 
   __syncthreads();
   const int need = (int64_t)k < n ? k : (int)n;
   const float t = tau[q];
-  const float pm = p_max_norm[0] * p_scale;
-  const float eps = (eps_coef * qnorm[q] * pm + eps_abs * (qnorm[q] + pm) + eps_abs * eps_abs) * 1.001f + 1e-30f;
+  const float eps = band.eps(q);
+  const bool out_of_range = band.out_of_range(q);
   const bool have_k = need > 0 && c >= need;
   float cut = -INFINITY;
   if (have_k)
@@ -86,26 +84,10 @@ __global__ void __launch_bounds__(IP_DEEP_THREADS) k_ip_cut_deep(int64_t n, int 
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int st = CONVDR_IP_OK;
-    float retry = -INFINITY;
-    if (cnt > (uint32_t)cap) {
-      st = CONVDR_IP_OVERFLOW;
-      const float cand = nextafterf(cut, -INFINITY);
-      retry = cand > t ? cand : t;
-    } else if (c < need) {
-      st = CONVDR_IP_TOO_FEW;
-      retry = t - 4.f * eps - 1e-3f * fabsf(t);
-    } else if (need > 0 && t > -INFINITY && cut < t) {
-      st = CONVDR_IP_UNCERTAIN;
-      retry = nextafterf(cut, -INFINITY);
-    }
-    if (pm > norm_limit || qnorm[q] > norm_limit) {
-      st = CONVDR_IP_RANGE;
-      retry = -INFINITY;
-    }
+    const IpVerdict v = ip_topk_verdict(cnt, cap, c, need, t, cut, eps, out_of_range);
     m_out[q] = sh_m;
-    status[q] = st;
-    tau_retry[q] = retry;
+    status[q] = v.status;
+    tau_retry[q] = v.retry;
   }
 }
 
@@ -305,7 +287,7 @@ static int ip_search_deep(const char* name, const IpBlock& b, const IpTopkArgs& 
   uint32_t* band_id = (uint32_t*)(ws + p.o_bid);
   double* band_x = (double*)(ws + p.o_bx);
   double* sort_x = (double*)(ws + p.o_sx);
-  uint32_t* band = (uint32_t*)(ws + p.o_m);
+  uint32_t* band_m = (uint32_t*)(ws + p.o_m);
   bf16_t* qlo = b.split() ? (bf16_t*)(ws + p.o_qlo) : nullptr;
   const bool all_candidates = p.mode < 0 || (b.row_bits && b.n_allowed <= cap);
 
@@ -335,21 +317,20 @@ static int ip_search_deep(const char* name, const IpBlock& b, const IpTopkArgs& 
   {
     ProfScope prof("ip_cut_deep", st);
     hipLaunchKernelGGL(k_ip_cut_deep, dim3(nq), dim3(IP_DEEP_THREADS), 0, st, b.n_need(), k, cap, counts, counts_packed, list_id, list_s,
-                       band_id, tau, qnorm, b.p_max_norm, b.eps_coef(), b.eps_abs(), b.scan_scale(), b.norm_limit(), band, c.status,
-                       c.tau_retry);
+                       band_id, tau, b.band(qnorm), band_m, c.status, c.tau_retry);
     CONVDR_CHECK_LAUNCH("k_ip_cut_deep");
   }
   if (n > 0) {
     // (bands are thousands of rows per query here: more waves per query than the shallow call's 64 when queries are few)
     ProfScope prof("ip_rescore_deep", st);
-    if (int e = ip_rescore(b, c.q_f32, nq, nq < 64 ? 128 : 16, cap, band, band_id, band_x, st)) return e;
+    if (int e = ip_rescore(b, c.q_f32, nq, nq < 64 ? 128 : 16, cap, band_m, band_id, band_x, st)) return e;
   }
   static DeviceOnce attr_done;
   if (attr_done.first())
     CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_select_deep, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          IP_DEEP_TILE * 12));
   ProfScope prof("ip_select_deep", st);
-  hipLaunchKernelGGL(k_ip_select_deep, dim3(nq), dim3(IP_DEEP_THREADS), (size_t)IP_DEEP_TILE * 12, st, k, cap, band, band_id, band_x,
+  hipLaunchKernelGGL(k_ip_select_deep, dim3(nq), dim3(IP_DEEP_THREADS), (size_t)IP_DEEP_TILE * 12, st, k, cap, band_m, band_id, band_x,
                      list_id, sort_x, c.D, c.I);
   CONVDR_CHECK_LAUNCH("k_ip_select_deep");
   return 0;

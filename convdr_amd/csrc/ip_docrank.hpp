@@ -9,7 +9,7 @@
 //   k_docs_scan_blocks  exclusive scan of the block sums, one workgroup; the total is ndocs (ip_docs.hpp)  ordinals, launch 4
 //   k_ord_starts        the scan inside each block; every owner writes its document's number into its slot ordinals, launch 5
 //   k_ord_write         ord[r] = the number in the slot of row_keys[r]                                     ordinals, launch 6
-//   k_ip_scan_r3<MARK>  the band-count scan; a row with S~ >= tau_hi also ORs its document's bit (ip_topk.hip)
+//   k_ip_scan_r3<MARK>  the band-count scan; a row with S~ >= tau_hi also ORs its document's bit (ip_scan.hpp)
 //   k_ip_docrank_mark_band   the re-scored band entries that precede the target OR their document's bit    rank, after the re-score
 //   k_ip_docrank_count  popcount of the pair's bitmap with the target's own document cleared; status       rank, last launch
 //
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_docrank_mark_band(int ca
   const int q = blockIdx.x;
   const int64_t t = tgt[q];
   if (!(t >= 0 && t < n)) return;                                    // (uniform) nothing was scanned for it
-  const uint32_t cnt = hits[(int64_t)q * IP_COUNT_STRIDE];
+  const uint32_t cnt = ip_hits(hits, q);
   const int m = cnt < (uint32_t)cap ? (int)cnt : cap;
   const double x_t = xt[q];
   const uint32_t* li = list_id + (int64_t)q * cap;
@@ -136,9 +136,7 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_docrank_mark_band(int ca
 __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_docrank_count(int cap, int64_t n, const uint32_t* __restrict__ hits,
                                                                       const uint32_t* __restrict__ above_in,
                                                                       const uint32_t* __restrict__ bad, const int64_t* __restrict__ tgt,
-                                                                      const float* __restrict__ qnorm,
-                                                                      const float* __restrict__ p_max_norm, float p_scale,
-                                                                      float norm_limit, const uint32_t* __restrict__ ord, int64_t ndocs,
+                                                                      const IpBand band, const uint32_t* __restrict__ ord, int64_t ndocs,
                                                                       int64_t mark_words, const uint32_t* __restrict__ marks,
                                                                       int64_t* __restrict__ rank, int64_t* __restrict__ counts,
                                                                       int64_t* __restrict__ above, int32_t* __restrict__ status) {
@@ -166,14 +164,11 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_docrank_count(int cap, i
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&sh_g, mine);       // (a sum of integers: the order of arrival does not show)
   __syncthreads();
   if (threadIdx.x == 0) {
-    const uint32_t cnt = hits[(int64_t)q * IP_COUNT_STRIDE];
-    const float pm = p_max_norm[0] * p_scale;
-    int st = CONVDR_IP_OK;
-    if (cnt > (uint32_t)cap) st = CONVDR_IP_OVERFLOW;
-    if (bad[q] || pm > norm_limit || qnorm[q] > norm_limit) st = CONVDR_IP_RANGE;   // (as in k_ip_rank_finish)
+    const uint32_t cnt = ip_hits(hits, q);
+    const int st = ip_list_verdict(cnt, cap, bad[q], band.out_of_range(q));
     rank[q] = st == CONVDR_IP_OK ? (int64_t)sh_g : -1;
     counts[q] = (int64_t)cnt;
-    above[q] = (int64_t)above_in[(int64_t)q * IP_COUNT_STRIDE];
+    above[q] = (int64_t)ip_hits(above_in, q);
     status[q] = st;
   }
 }
@@ -188,8 +183,8 @@ static int ip_docrank_finish(const DocRankFinish& f, hipStream_t st) {
                        f.xt, f.ord, f.ndocs, f.mark_words, f.marks);
     CONVDR_CHECK_LAUNCH("k_ip_docrank_mark_band");
   }
-  hipLaunchKernelGGL(k_ip_docrank_count, dim3(f.np), dim3(IP_RANK_THREADS), 0, st, f.cap, f.n, f.hits, f.above_u, f.bad, f.target, f.qnorm,
-                     f.p_max_norm, f.p_scale, f.norm_limit, f.ord, f.ndocs, f.mark_words, f.marks, f.rank, f.counts, f.above, f.status);
+  hipLaunchKernelGGL(k_ip_docrank_count, dim3(f.np), dim3(IP_RANK_THREADS), 0, st, f.cap, f.n, f.hits, f.above_u, f.bad, f.target, f.band,
+                     f.ord, f.ndocs, f.mark_words, f.marks, f.rank, f.counts, f.above, f.status);
   CONVDR_CHECK_LAUNCH("k_ip_docrank_count");
   return 0;
 }

@@ -1,4 +1,4 @@
-// Host side of the search entries, included by ip_topk.hip after its kernels and the scan launcher; ip_deep.hpp and
+// Host side of the search entries, included by ip_topk.hip after the kernel headers (ip_scan.hpp, ip_select.hpp); ip_deep.hpp and
 // ip_range.hpp follow with their pipelines.  The map of all three: DESIGN.md section 4, "Host side of the search entries".
 #pragma once
 
@@ -28,6 +28,8 @@ struct IpBlock {
   int64_t n_need() const { return row_bits ? n_allowed : n; }   // TOP-K ONLY (range search sets no n_allowed): need = min(k, n_need)
   float eps_coef() const { return ip_eps_coef(d, split(), kind()); }
   float eps_abs() const { return ip_eps_abs(d, split(), kind()); }
+  // the error band of this block's scan scores for queries whose norms are at qnorm (device, [nq]): what every finishing kernel takes
+  IpBand band(const float* qnorm) const { return {qnorm, p_max_norm, eps_coef(), eps_abs(), scan_scale(), norm_limit()}; }
 };
 
 // per-call arguments of the seven top-k entries, in the entries' order
@@ -232,7 +234,7 @@ static int ip_search(const char* name, const IpBlock& b, const IpTopkArgs& c, co
   uint32_t* cand_id = (uint32_t*)(ws + p.o_id);
   float* cand_s = (float*)(ws + p.o_s);
   double* cand_x = (double*)(ws + p.o_x);
-  uint32_t* band = (uint32_t*)(ws + p.o_m);
+  uint32_t* band_m = (uint32_t*)(ws + p.o_m);
   bf16_t* qlo = b.split() ? (bf16_t*)(ws + p.o_qlo) : nullptr;
   const bool all_candidates = p.mode < 0 || (b.row_bits && b.n_allowed <= cap);
 
@@ -283,29 +285,27 @@ static int ip_search(const char* name, const IpBlock& b, const IpTopkArgs& c, co
   if (g_ip_fused_finish && n > 0) {
     ProfScope prof("ip_finish", st);
     if (b.rows_f16())
-      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(1024), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
-                         cand_id, cand_s, tau, qnorm, b.p_max_norm, b.eps_coef(), b.eps_abs(), b.scan_scale(), b.norm_limit(),
-                         c.q_f32, (const _Float16*)b.p_half, b.d, band, c.status, c.tau_retry, c.D, c.I, b.unscale());
+      hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
+                         cand_id, cand_s, tau, b.band(qnorm), c.q_f32, (const _Float16*)b.p_half, b.d, band_m, c.status, c.tau_retry,
+                         c.D, c.I, b.unscale());
     else
-      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(1024), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
-                         cand_id, cand_s, tau, qnorm, b.p_max_norm, b.eps_coef(), b.eps_abs(), b.scan_scale(), b.norm_limit(),
-                         c.q_f32, b.p_f32, b.d, band, c.status, c.tau_retry, c.D, c.I, b.unscale());
+      hipLaunchKernelGGL(k_ip_finish<float>, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
+                         cand_id, cand_s, tau, b.band(qnorm), c.q_f32, b.p_f32, b.d, band_m, c.status, c.tau_retry, c.D, c.I, b.unscale());
     CONVDR_CHECK_LAUNCH("k_ip_finish");
     return 0;
   }
   {
     ProfScope prof("ip_cut", st);
     hipLaunchKernelGGL(k_ip_cut, dim3(nq), dim3(1024), (size_t)cap * 8, st, b.n_need(), k, cap, counts, counts_packed, cand_id, cand_s,
-                       tau, qnorm, b.p_max_norm, b.eps_coef(), b.eps_abs(), b.scan_scale(), b.norm_limit(), band, c.status,
-                       c.tau_retry);
+                       tau, b.band(qnorm), band_m, c.status, c.tau_retry);
     CONVDR_CHECK_LAUNCH("k_ip_cut");
   }
   if (n > 0) {
     ProfScope prof("ip_rescore", st);
-    if (int e = ip_rescore(b, c.q_f32, nq, 16, cap, band, cand_id, cand_x, st)) return e;
+    if (int e = ip_rescore(b, c.q_f32, nq, 16, cap, band_m, cand_id, cand_x, st)) return e;
   }
   ProfScope prof("ip_select", st);
-  hipLaunchKernelGGL(k_ip_select, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 12, st, k, cap, band, cand_id, cand_x, c.D, c.I);
+  hipLaunchKernelGGL(k_ip_select, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 12, st, k, cap, band_m, cand_id, cand_x, c.D, c.I);
   CONVDR_CHECK_LAUNCH("k_ip_select");
   return 0;
 }

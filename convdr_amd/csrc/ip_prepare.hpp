@@ -1,0 +1,191 @@
+// Preparing operands for the similarity scan (included by ip_topk.hip after its constants): rows fp32 -> 16-bit scan
+// operand with norms (k_rows_to_half: blocks and queries, bf16 and fp16), the half store (k_store_rows_f16), the column mean
+// a block is centred by, and the fill kernel of a given threshold.  The entries that launch them are in ip_topk.hip.
+#pragma once
+
+namespace convdr {
+
+// ------------------------------------------------------------------------------------------
+// rows fp32 -> bf16 of (x - centre) (+ per-row L2 norm of the centred row, + global max norm).
+// Optional second output: the bf16 of the rounding remainder (x - centre) - hi, for the split-bf16 scan.
+// One wave per row, float4 loads.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+  typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+  const f16x2_t r = {(_Float16)lo, (_Float16)hi};   // v_cvt_pkrtz is NOT used: round to nearest even
+  return *(const uint32_t*)&r;
+}
+template <int KIND>
+__device__ __forceinline__ uint32_t pack_half2(float lo, float hi) {
+  return KIND == IP_KIND_F16 ? pack_f16x2(lo, hi) : pack_bf16x2(lo, hi);
+}
+template <int KIND>
+__device__ __forceinline__ float half_lo_to_f32(uint32_t packed) {
+  if constexpr (KIND == IP_KIND_F16) { const uint16_t h = (uint16_t)packed; return (float)*(const _Float16*)&h; }
+  return bf16_to_f32((bf16_t)packed);
+}
+template <int KIND>
+__device__ __forceinline__ float half_hi_to_f32(uint32_t packed) {
+  if constexpr (KIND == IP_KIND_F16) { const uint16_t h = (uint16_t)(packed >> 16); return (float)*(const _Float16*)&h; }
+  return bf16_to_f32((bf16_t)(packed >> 16));
+}
+
+// PER_ROW_SCALE (queries of the fp16 scan): every row is multiplied by its own power of two 2^(12 - e), |row| = m 2^e
+// with m in [0.5, 1), so its scaled norm lies in [2^11, 2^12); row_norm receives the SCALED norm.  Otherwise `scale`
+// (a power of two; 1 for bf16) multiplies every row and row_norm / max_norm are UNSCALED.
+template <int KIND, bool PER_ROW_SCALE>
+__global__ void __launch_bounds__(256) k_rows_to_half(const float* __restrict__ X, int64_t n, int d,
+                                                      const float* __restrict__ centre, float scale, bf16_t* __restrict__ Y,
+                                                      bf16_t* __restrict__ Ylo, float* __restrict__ row_norm,
+                                                      float* __restrict__ max_norm, int64_t n_pad = 0,
+                                                      uint32_t* __restrict__ zero_u32 = nullptr, int64_t zero_count = 0) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float wmax = 0.f;
+  // query preparation of a search: the padding rows [n, n_pad) of Y / Ylo and the candidate counters are zeroed here
+  // instead of by three memsets in front of this kernel (a search of <= 128 queries is a chain of short launches)
+  for (int64_t row = n + (int64_t)blockIdx.x * 4 + wave; row < n_pad; row += (int64_t)gridDim.x * 4)
+    for (int e = lane * 4; e < d; e += 256) {
+      *(uint2*)(Y + row * d + e) = make_uint2(0u, 0u);
+      if (Ylo) *(uint2*)(Ylo + row * d + e) = make_uint2(0u, 0u);
+    }
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < zero_count; i += (int64_t)gridDim.x * 256) zero_u32[i] = 0u;
+  // Norms are summed in fp64: eps is proportional to them, and in fp32 the squares of elements below ~1e-19 underflow
+  // (a block of tiny-magnitude embeddings would get norm 0 = "no rounding error").  The pass is HBM-bound either way.
+  auto sq4 = [](const float4& v) {
+    return (double)v.x * (double)v.x + (double)v.y * (double)v.y + (double)v.z * (double)v.z + (double)v.w * (double)v.w;
+  };
+  auto wave_sum_f64 = [](double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  };
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < n; row += (int64_t)gridDim.x * 4) {
+    const float* x = X + row * d;
+    double ss = 0.0;
+    float sc = scale;
+    if constexpr (PER_ROW_SCALE) {
+      for (int e = lane * 4; e < d; e += 256) ss += sq4(*(const float4*)(x + e));
+      ss = wave_sum_f64(ss);
+      int ex = 0;
+      const float nm0 = (float)sqrt(ss);
+      (void)frexpf(nm0, &ex);
+      int sh = (int)IP_F16_TARGET_EXP - ex;
+      sh = sh > 100 ? 100 : (sh < -100 ? -100 : sh);
+      sc = (nm0 > 0.f && nm0 < INFINITY) ? ldexpf(1.f, sh) : 1.f;
+      ss = 0.0;
+    }
+    for (int e = lane * 4; e < d; e += 256) {
+      float4 v = *(const float4*)(x + e);
+      if (centre) {
+        const float4 c = *(const float4*)(centre + e);
+        v.x -= c.x; v.y -= c.y; v.z -= c.z; v.w -= c.w;
+      }
+      if constexpr (PER_ROW_SCALE) { v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc; }
+      ss += sq4(v);
+      if (Y) {
+        if constexpr (!PER_ROW_SCALE && KIND == IP_KIND_F16) { v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc; }
+        uint2 o;
+        o.x = pack_half2<KIND>(v.x, v.y);
+        o.y = pack_half2<KIND>(v.z, v.w);
+        *(uint2*)(Y + row * d + e) = o;
+        if (Ylo) {
+          uint2 l;
+          l.x = pack_half2<KIND>(v.x - half_lo_to_f32<KIND>(o.x), v.y - half_hi_to_f32<KIND>(o.x));
+          l.y = pack_half2<KIND>(v.z - half_lo_to_f32<KIND>(o.y), v.w - half_hi_to_f32<KIND>(o.y));
+          *(uint2*)(Ylo + row * d + e) = l;
+        }
+      }
+    }
+    ss = wave_sum_f64(ss);
+    const float nm = (float)(sqrt(ss) * (1.0 + 1e-6));   // (rounded up: a bound)
+    if (row_norm && lane == 0) row_norm[row] = nm;
+    wmax = fmaxf(wmax, nm);
+  }
+  if (max_norm) {
+    __shared__ float sm[4];
+    if (lane == 0) sm[wave] = wmax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float m = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+      atomicMax((int*)max_norm, __float_as_int(m));  // non-negative floats order like ints
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// The half store: the passage IS its stored half v; the resident copy holds 2^s v (scale = 2^s, s >= 0), which is at once
+// the corpus (re-scored in fp64 and multiplied by 2^-s, see k_ip_rescore) and the un-centred fp16 scan operand.
+// src: rows of halves (kept bit for bit) or fp32 rows (rounded to nearest even once, here).  store = half * scale; the
+// rows' UNSCALED norm is folded into *max_norm.  flags |= 1: a value is not finite (after rounding); flags |= 2: the
+// scaled value left the half range or does not divide back to the half (scaling a half by 2^s, s >= 0, is exact,
+// subnormals included, unless it overflows -- this is the check of that).  `store` may be `src` (halves): the in-place
+// rescale by 2^(s_new - s_old) <= 1 with s_new >= 0, equally exact; a lane reads its 8 bytes before it writes them.
+// store == nullptr: norms and flag 1 only.  One wave per row, 8- / 16-byte loads and 8-byte stores, no LDS.
+// ------------------------------------------------------------------------------------------
+template <bool SRC_F32>
+__global__ void __launch_bounds__(256) k_store_rows_f16(const void* src, int64_t n, int d, float scale, float inv_scale,
+                                                        _Float16* store, float* __restrict__ max_norm,
+                                                        int32_t* __restrict__ flags) {
+  typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float wmax = 0.f;
+  int bad = 0;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < n; row += (int64_t)gridDim.x * 4) {
+    double ss = 0.0;
+    for (int e = lane * 4; e < d; e += 256) {
+      f16x4_t h;
+      if constexpr (SRC_F32) {
+        const float4 v = *(const float4*)((const float*)src + row * d + e);
+        h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};   // round to nearest even
+      } else {
+        const uint2 raw = *(const uint2*)((const _Float16*)src + row * d + e);
+        h = *(const f16x4_t*)&raw;
+      }
+      f16x4_t o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float f = (float)h[c];
+        o[c] = (_Float16)(f * scale);          // fp32 product of a half and a power of two: exact; then one conversion
+        // the sign comes from the source bits: a half of -0 stays -0 however the product above is contracted
+        // (a multiply selected as a fused multiply-add with a +0 addend returns +0 for it)
+        o[c] = __builtin_copysignf16(o[c], h[c]);
+        const float back = (float)o[c];
+        if (!(fabsf(f) <= 65504.f)) bad |= 1;
+        else if (!(fabsf(back) <= 65504.f) || back * inv_scale != f) bad |= 2;
+        ss += (double)f * (double)f;
+      }
+      if (store) *(uint2*)(store + row * d + e) = *(const uint2*)&o;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    wmax = fmaxf(wmax, (float)(sqrt(ss) * (1.0 + 1e-6)));   // (rounded up: a bound; NaN rows raise flag 1 instead)
+  }
+  if (max_norm && lane == 0 && wmax > 0.f) atomicMax((int*)max_norm, __float_as_int(wmax));  // non-negative floats order like ints
+  if (bad) atomicOr(flags, bad);
+}
+
+// column sums of fp32 rows: part[chunk][d]; grid (ceil(d / 256), chunks)
+__global__ void __launch_bounds__(256) k_colsum_f32(const float* __restrict__ X, int64_t n, int d, float* __restrict__ part) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  const int64_t per = (n + gridDim.y - 1) / gridDim.y;
+  const int64_t t0 = per * blockIdx.y, t1 = t0 + per < n ? t0 + per : n;
+  if (c >= d) return;
+  float s = 0.f;
+  for (int64_t t = t0; t < t1; ++t) s += X[t * d + c];
+  part[(int64_t)blockIdx.y * d + c] = s;
+}
+__global__ void __launch_bounds__(256) k_colmean_finish(const float* __restrict__ part, int chunks, int d, int64_t n,
+                                                        float* __restrict__ mean) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= d) return;
+  double s = 0.0;
+  for (int p = 0; p < chunks; ++p) s += part[(int64_t)p * d + c];
+  mean[c] = (float)(s / (double)n);
+}
+
+__global__ void k_fill_f32(float* p, int n, float v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+}  // namespace convdr

@@ -31,10 +31,10 @@ constexpr int IP_RANGE_LDS_SORT = 8192;        // survivors ordered by the LDS n
 //      g |q| (|c| + |v|) =: e_x.  So X > radius implies q . v > radius - q . c - e_x.
 //   2. q . c is summed in fp64 here, same depth: |fl(q . c) - q . c| <= g sum |q_i c_i| =: e_c.  t below is
 //      radius - fl(q . c) - e_c - e_x with every operation's rounding (relative 2^-53) charged by the final
-//      t -= 2^-50 (|radius| + |fl(q . c)| + e_c + e_x): t <= radius - q . c - e_x, hence q . v > t.
+//      t -= 2^-50 (|radius| + |fl(q . c)| + e_c + e_x) (IpCentreTerms::bound): t <= radius - q . c - e_x, hence q . v > t.
 //   3. The scan operands are qs q and p_scale fl32(v): powers of two scale exactly, so qs p_scale q . v > qs p_scale t
 //      =: s (exact in fp64: a power-of-two factor; overflow to +-inf keeps the order).  f = s rounded to fp32 toward -inf.
-//   4. |S~ - qs p_scale q . v| <= eps: the band of k_ip_cut, the same expression.  (It bounds the error against the
+//   4. |S~ - qs p_scale q . v| <= eps: the band of k_ip_cut (IpBand::eps).  (It bounds the error against the
 //      fp32-rounded v; the rounding of the subtraction itself, <= 2^-24 |q| |v|, sits inside the 1.0001 and 1.001
 //      factors the band already carries: the smallest coefficient, fp16 one pass, is 2^-11 + d 2^-23 > 4.8e-4, and
 //      1.1e-3 of it exceeds 2^-24.)  Hence S~ > f - eps.
@@ -47,59 +47,23 @@ constexpr int IP_RANGE_LDS_SORT = 8192;        // survivors ordered by the LDS n
 // power of two, is recovered from its ratio to the unscaled norm summed here (the ratio is 2^k (1 +- 1e-6); a zero or
 // non-finite query was left unscaled: qs = 1).
 __global__ void __launch_bounds__(256) k_ip_range_tau(const float* __restrict__ Q, int nq, int d, const float* __restrict__ centre,
-                                                      const float* __restrict__ radius, const float* __restrict__ qnorm,
-                                                      const float* __restrict__ p_max_norm, float p_scale, float eps_coef,
-                                                      float eps_abs, int per_row_scale, float* __restrict__ tau) {
+                                                      const float* __restrict__ radius, const IpBand band, int per_row_scale,
+                                                      float* __restrict__ tau) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x * 4 + wave;
   if (q >= nq) return;
-  const float* qv = Q + (int64_t)q * d;
-  double dot = 0.0, adot = 0.0, qq = 0.0, cc = 0.0;
-  for (int e = lane * 4; e < d; e += 256) {
-    const float4 x = *(const float4*)(qv + e);
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (centre) c = *(const float4*)(centre + e);
-    const double xs[4] = {(double)x.x, (double)x.y, (double)x.z, (double)x.w};
-    const double cs[4] = {(double)c.x, (double)c.y, (double)c.z, (double)c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dot = fma(xs[i], cs[i], dot);
-      adot += fabs(xs[i] * cs[i]);
-      qq = fma(xs[i], xs[i], qq);
-      cc = fma(cs[i], cs[i], cc);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    dot += __shfl_xor(dot, o, 64);
-    adot += __shfl_xor(adot, o, 64);
-    qq += __shfl_xor(qq, o, 64);
-    cc += __shfl_xor(cc, o, 64);
-  }
+  const IpCentreSums sums = ip_centre_sums(Q + (int64_t)q * d, centre, d, lane);
   if (lane != 0) return;
   const double r = (double)radius[q];
-  const float qn = qnorm[q];
-  const float pm = p_max_norm[0] * p_scale;                  // scaled units, as in k_ip_cut
   float t32;
   if (r == (double)INFINITY) {
     t32 = INFINITY;
   } else if (r == -(double)INFINITY) {
     t32 = -FLT_MAX;
   } else {
-    const double nq_u = sqrt(qq) * (1.0 + 1e-9), nc = sqrt(cc) * (1.0 + 1e-9);   // (rounded up: bounds)
-    double qs = 1.0;
-    if (per_row_scale && nq_u > 0.0 && nq_u < (double)INFINITY && qn > 0.f && qn < INFINITY)
-      qs = ldexp(1.0, (int)rint(log2((double)qn / nq_u)));
-    const double g = (double)(d + 8) * 2.220446049250313e-16;                      // (d + 8) 2^-52
-    const double e_c = g * adot * (1.0 + 1e-9);
-    const double e_x = g * nq_u * (nc + (double)p_max_norm[0] * (1.0 + 1e-6)) * (1.0 + 1e-9);
-    double t = r - dot - e_c - e_x;
-    t -= 8.881784197001252e-16 * (fabs(r) + fabs(dot) + e_c + e_x);                // 2^-50: the roundings of the line above
-    const double s = t * qs * (double)p_scale;
-    float f = (float)s;                                                            // to nearest ...
-    if ((double)f > s) f = nextafterf(f, -INFINITY);                               // ... then toward -inf
-    const float eps = (eps_coef * qn * pm + eps_abs * (qn + pm) + eps_abs * eps_abs) * 1.001f + 1e-30f;   // k_ip_cut's band
-    t32 = nextafterf(f - eps, -INFINITY);
+    const IpCentreTerms ct(sums, d, band.qnorm[q], band.p_max_norm[0], per_row_scale);
+    const float f = ip_scan_units<false>(ct.bound<false>(r), ct.qs, band.p_scale);   // steps 2 and 3
+    t32 = nextafterf(f - band.eps(q), -INFINITY);
     if (!(t32 >= -FLT_MAX)) t32 = -FLT_MAX;  // (NaN from a non-finite norm or query -- RANGE reports it --, or -inf: see above)
   }
   tau[q] = t32;
@@ -108,7 +72,7 @@ __global__ void __launch_bounds__(256) k_ip_range_tau(const float* __restrict__ 
 __global__ void k_ip_range_clamp(const uint32_t* __restrict__ counts, int nq, int cap, uint32_t* __restrict__ m_out) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
-  const uint32_t c = counts[(int64_t)q * IP_COUNT_STRIDE];
+  const uint32_t c = ip_hits(counts, q);
   m_out[q] = c < (uint32_t)cap ? c : (uint32_t)cap;
 }
 
@@ -121,26 +85,21 @@ template <bool COUNT_ONLY>
 __global__ void __launch_bounds__(IP_RANGE_THREADS) k_ip_range_select(int cap, const uint32_t* __restrict__ counts,
                                                                       const uint32_t* __restrict__ list_id,
                                                                       const double* __restrict__ list_x,
-                                                                      const float* __restrict__ radius,
-                                                                      const float* __restrict__ qnorm,
-                                                                      const float* __restrict__ p_max_norm, float p_scale,
-                                                                      float norm_limit, uint32_t* sort_id, double* sort_x,
+                                                                      const float* __restrict__ radius, const IpBand band,
+                                                                      uint32_t* sort_id, double* sort_x,
                                                                       uint32_t* __restrict__ nsurv, int64_t* __restrict__ counts_out,
                                                                       int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ uint32_t sh_g;
   const int q = blockIdx.x;
-  const uint32_t cnt = counts[(int64_t)q * IP_COUNT_STRIDE];
+  const uint32_t cnt = ip_hits(counts, q);
   const int m = cnt < (uint32_t)cap ? (int)cnt : cap;
   const double r = (double)radius[q];
   const uint32_t* li = list_id + (int64_t)q * cap;
   const double* lx = list_x + (int64_t)q * cap;
   double* gx = sort_x + (int64_t)q * cap;
   uint32_t* gi = sort_id + (int64_t)q * cap;
-  const float pm = p_max_norm[0] * p_scale;
-  int st = CONVDR_IP_OK;
-  if (cnt > (uint32_t)cap) st = CONVDR_IP_OVERFLOW;
-  if (pm > norm_limit || qnorm[q] > norm_limit) st = CONVDR_IP_RANGE;   // (as in k_ip_cut: an operand may hold inf)
+  const int st = ip_list_verdict(cnt, cap, 0u, band.out_of_range(q));
   if (threadIdx.x == 0) sh_g = 0;
   __syncthreads();
   for (int i0 = 0; i0 < m; i0 += IP_RANGE_THREADS) {
@@ -285,8 +244,8 @@ static int ip_range_search(const IpBlock& b, const float* q_f32, int nq, const f
   double* sort_x = (double*)(ws + p.o_sx);
 
   if (int e = ip_prepare_queries(b, p, ws, q_f32, nq, nullptr, st)) return e;   // (one pass: no remainders)
-  hipLaunchKernelGGL(k_ip_range_tau, dim3((nq + 3) / 4), dim3(256), 0, st, q_f32, nq, b.d, centre, radius, qnorm, b.p_max_norm,
-                     b.scan_scale(), b.eps_coef(), b.eps_abs(), b.kind() == IP_KIND_F16 ? 1 : 0, tau);
+  hipLaunchKernelGGL(k_ip_range_tau, dim3((nq + 3) / 4), dim3(256), 0, st, q_f32, nq, b.d, centre, radius, b.band(qnorm),
+                     b.kind() == IP_KIND_F16 ? 1 : 0, tau);
   CONVDR_CHECK_LAUNCH("k_ip_range_tau");
   if (int e = launch_scan<IP_MODE_EMIT>(ip_scan_args(b, p, ws, nq, cap, nullptr, nullptr), p.big, b.kind(), st)) return e;
   hipLaunchKernelGGL(k_ip_range_clamp, dim3((nq + 255) / 256), dim3(256), 0, st, hits, nq, cap, m);
@@ -298,8 +257,8 @@ static int ip_range_search(const IpBlock& b, const float* q_f32, int nq, const f
   {
     ProfScope prof("ip_range_select", st);
     if (count_only) {
-      hipLaunchKernelGGL(k_ip_range_select<true>, dim3(nq), dim3(IP_RANGE_THREADS), 0, st, cap, hits, list_id, list_x, radius, qnorm,
-                         b.p_max_norm, b.scan_scale(), b.norm_limit(), sort_id, sort_x, nsurv, counts, status);
+      hipLaunchKernelGGL(k_ip_range_select<true>, dim3(nq), dim3(IP_RANGE_THREADS), 0, st, cap, hits, list_id, list_x, radius,
+                         b.band(qnorm), sort_id, sort_x, nsurv, counts, status);
     } else {
       const int lds_n = cap < IP_RANGE_LDS_SORT ? cap : IP_RANGE_LDS_SORT;     // (>= IP_DEEP_TILE whenever deep_bitonic can run)
       static DeviceOnce attr_done;
@@ -307,7 +266,7 @@ static int ip_range_search(const IpBlock& b, const float* q_f32, int nq, const f
         CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_range_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              IP_RANGE_LDS_SORT * 12));
       hipLaunchKernelGGL(k_ip_range_select<false>, dim3(nq), dim3(IP_RANGE_THREADS), (size_t)lds_n * 12, st, cap, hits, list_id,
-                         list_x, radius, qnorm, b.p_max_norm, b.scan_scale(), b.norm_limit(), sort_id, sort_x, nsurv, counts, status);
+                         list_x, radius, b.band(qnorm), sort_id, sort_x, nsurv, counts, status);
     }
     CONVDR_CHECK_LAUNCH("k_ip_range_select");
   }

@@ -22,28 +22,8 @@ namespace convdr {
 
 constexpr int IP_RANK_THREADS = 1024;
 
-// The canonical fp64 score of one (query, row) pair, computed by one whole wave and returned on every lane of it: the lane /
-// (j, c) / butterfly order of k_ip_rescore, and its one multiplication by `unscale` for the half store -- the same value bit
-// for bit.  Shared by k_ip_score_rows and k_ip_score_docs (ip_docs.hpp).  The call is wave-uniform.
-template <class PT>
-__device__ __forceinline__ double ip_row_score(const float* __restrict__ qv, const PT* __restrict__ pv, int d, int lane,
-                                               double unscale) {
-  double acc = 0.0;
-  for (int e = lane * 4; e < d; e += 256) {
-    const float4 x = *(const float4*)(qv + e);
-    const f64x4 y = ip_load4_f64<PT>(pv + e);
-    acc = fma((double)x.x, y.x, acc);
-    acc = fma((double)x.y, y.y, acc);
-    acc = fma((double)x.z, y.z, acc);
-    acc = fma((double)x.w, y.w, acc);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if constexpr (sizeof(PT) == 2) acc *= unscale;
-  return acc;
-}
-
-// One wave per (query, row) pair; grid (nq, chunks).  rows / X / D share the pitch ld; the query of pair (q, j) is row q of Q.
+// One wave per (query, row) pair (ip_row_score: the value k_ip_rescore gives it); grid (nq, chunks).  rows / X / D share the
+// pitch ld; the query of pair (q, j) is row q of Q.
 // An id outside [0, n) yields the score FAISS pads with and P is not touched for it.
 template <class PT>
 __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__ Q, const PT* __restrict__ P, int64_t n, int d,
@@ -62,8 +42,8 @@ __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__
   }
 }
 
-// tau_lo[q], tau_hi[q] from the fp64 canonical score X_t = xt[q] of the query's target.  One wave per query, modelled on
-// k_ip_range_tau: the same sums, the same error terms, the same eps; the radius is an fp64 value here.
+// tau_lo[q], tau_hi[q] from the fp64 canonical score X_t = xt[q] of the query's target.  One wave per query, on the pieces
+// k_ip_range_tau uses (ip_certify.hpp: the sums, the error terms, the eps); the radius is an fp64 value here.
 //
 // Notation: x = q . p in real arithmetic, c the centre (0 when there is none), v = p - c, g = (d + 8) 2^-52, qs the query's
 // power-of-two scale, and
@@ -98,59 +78,23 @@ __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__
 // k_ip_rank_finish reports CONVDR_IP_RANGE for it, never a count.
 __global__ void __launch_bounds__(256) k_ip_band_tau(const float* __restrict__ Q, int nq, int d, const float* __restrict__ centre,
                                                      const double* __restrict__ xt, const int64_t* __restrict__ tgt, int64_t n,
-                                                     const float* __restrict__ qnorm, const float* __restrict__ p_max_norm,
-                                                     float p_scale, float eps_coef, float eps_abs, int per_row_scale,
-                                                     float* __restrict__ tau_lo, float* __restrict__ tau_hi,
-                                                     uint32_t* __restrict__ bad) {
+                                                     const IpBand band, int per_row_scale, float* __restrict__ tau_lo,
+                                                     float* __restrict__ tau_hi, uint32_t* __restrict__ bad) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x * 4 + wave;
   if (q >= nq) return;
-  const float* qv = Q + (int64_t)q * d;
-  double dot = 0.0, adot = 0.0, qq = 0.0, cc = 0.0;
-  for (int e = lane * 4; e < d; e += 256) {
-    const float4 x = *(const float4*)(qv + e);
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (centre) c = *(const float4*)(centre + e);
-    const double xs[4] = {(double)x.x, (double)x.y, (double)x.z, (double)x.w};
-    const double cs[4] = {(double)c.x, (double)c.y, (double)c.z, (double)c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dot = fma(xs[i], cs[i], dot);
-      adot += fabs(xs[i] * cs[i]);
-      qq = fma(xs[i], xs[i], qq);
-      cc = fma(cs[i], cs[i], cc);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    dot += __shfl_xor(dot, o, 64);
-    adot += __shfl_xor(adot, o, 64);
-    qq += __shfl_xor(qq, o, 64);
-    cc += __shfl_xor(cc, o, 64);
-  }
+  const IpCentreSums sums = ip_centre_sums(Q + (int64_t)q * d, centre, d, lane);
   if (lane != 0) return;
   float lo = INFINITY, hi = INFINITY;
   uint32_t flag = 0;
   const int64_t t = tgt[q];
   if (t >= 0 && t < n) {
     const double r = xt[q];
-    const float qn = qnorm[q];
-    const float pm = p_max_norm[0] * p_scale;                  // scaled units, as in k_ip_cut
-    const double nq_u = sqrt(qq) * (1.0 + 1e-9), nc = sqrt(cc) * (1.0 + 1e-9);   // (rounded up: bounds)
-    double qs = 1.0;
-    if (per_row_scale && nq_u > 0.0 && nq_u < (double)INFINITY && qn > 0.f && qn < INFINITY)
-      qs = ldexp(1.0, (int)rint(log2((double)qn / nq_u)));
-    const double g = (double)(d + 8) * 2.220446049250313e-16;                      // (d + 8) 2^-52
-    const double e_c = g * adot * (1.0 + 1e-9);
-    const double e_x = g * nq_u * (nc + (double)p_max_norm[0] * (1.0 + 1e-6)) * (1.0 + 1e-9);
-    const double charge = 8.881784197001252e-16 * (fabs(r) + fabs(dot) + e_c + e_x);   // 2^-50: the roundings of the two lines below
-    const double t_lo = (r - dot - e_c - e_x) - charge;
-    const double t_hi = (r - dot + e_c + e_x) + charge;
-    const double s_lo = t_lo * qs * (double)p_scale, s_hi = t_hi * qs * (double)p_scale;
-    float f_lo = (float)s_lo, f_hi = (float)s_hi;                                  // to nearest ...
-    if ((double)f_lo > s_lo) f_lo = nextafterf(f_lo, -INFINITY);                   // ... then toward -inf
-    if ((double)f_hi < s_hi) f_hi = nextafterf(f_hi, INFINITY);                    // ... toward +inf
-    const float eps = (eps_coef * qn * pm + eps_abs * (qn + pm) + eps_abs * eps_abs) * 1.001f + 1e-30f;   // k_ip_cut's band
+    const IpCentreTerms ct(sums, d, band.qnorm[q], band.p_max_norm[0], per_row_scale);
+    double s_lo, s_hi;
+    const float f_lo = ip_scan_units<false>(ct.bound<false>(r), ct.qs, band.p_scale, &s_lo);   // LO steps 2 and 3
+    const float f_hi = ip_scan_units<true>(ct.bound<true>(r), ct.qs, band.p_scale, &s_hi);     // HI steps 4 and 3
+    const float eps = band.eps(q);
     const bool finite = fabs(s_lo) < (double)INFINITY && fabs(s_hi) < (double)INFINITY && eps < INFINITY;   // (false for NaN)
     if (finite) {
       lo = nextafterf(f_lo - eps, -INFINITY);
@@ -174,9 +118,7 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_rank_finish(int cap, int
                                                                     const uint32_t* __restrict__ list_id,
                                                                     const double* __restrict__ list_x,
                                                                     const int64_t* __restrict__ tgt, double* __restrict__ xt,
-                                                                    const float* __restrict__ qnorm,
-                                                                    const float* __restrict__ p_max_norm, float p_scale,
-                                                                    float norm_limit, int64_t* __restrict__ rank,
+                                                                    const IpBand band, int64_t* __restrict__ rank,
                                                                     int64_t* __restrict__ counts, int64_t* __restrict__ above,
                                                                     int32_t* __restrict__ status) {
   __shared__ uint32_t sh_g;
@@ -186,7 +128,7 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_rank_finish(int cap, int
     if (threadIdx.x == 0) { rank[q] = -1; counts[q] = 0; above[q] = 0; status[q] = CONVDR_IP_OK; }
     return;
   }
-  const uint32_t cnt = hits[(int64_t)q * IP_COUNT_STRIDE];
+  const uint32_t cnt = ip_hits(hits, q);
   const int m = cnt < (uint32_t)cap ? (int)cnt : cap;
   const double x_t = xt[q];
   const uint32_t* li = list_id + (int64_t)q * cap;
@@ -203,11 +145,8 @@ __global__ void __launch_bounds__(IP_RANK_THREADS) k_ip_rank_finish(int cap, int
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&sh_g, mine);     // (a sum of integers: the order of arrival does not show)
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float pm = p_max_norm[0] * p_scale;
-    const uint32_t ab = above_in[(int64_t)q * IP_COUNT_STRIDE];
-    int st = CONVDR_IP_OK;
-    if (cnt > (uint32_t)cap) st = CONVDR_IP_OVERFLOW;
-    if (bad[q] || pm > norm_limit || qnorm[q] > norm_limit) st = CONVDR_IP_RANGE;   // (as in k_ip_cut: an operand may hold inf)
+    const uint32_t ab = ip_hits(above_in, q);
+    const int st = ip_list_verdict(cnt, cap, bad[q], band.out_of_range(q));
     rank[q] = st == CONVDR_IP_OK ? (int64_t)ab + (int64_t)sh_g : -1;
     counts[q] = (int64_t)cnt;
     above[q] = (int64_t)ab;
@@ -270,8 +209,7 @@ struct DocRankFinish {       // what the two finishing launches read and write (
   const double* list_x;
   const int64_t* target;
   const double* xt;
-  const float *qnorm, *p_max_norm;
-  float p_scale, norm_limit;
+  IpBand band;
   const uint32_t* ord;
   int64_t ndocs, mark_words;
   uint32_t* marks;
@@ -319,8 +257,8 @@ static int ip_rank_rows(const IpDepth& depth, const IpBlock& b, const float* q_f
   // the targets' canonical scores, straight into the caller's X (an id outside [0, n): the padding score, nothing read)
   if (int e = ip_score_rows_launch(b, q_f32, np, target, 1, 1, X, nullptr, st)) return e;
   // (n == 0: every target is outside the block and p_max_norm may be NULL -- the kernel reads it for valid targets only)
-  hipLaunchKernelGGL(k_ip_band_tau, dim3((np + 3) / 4), dim3(256), 0, st, q_f32, np, b.d, centre, X, target, b.n, qnorm, b.p_max_norm,
-                     b.scan_scale(), b.eps_coef(), b.eps_abs(), b.kind() == IP_KIND_F16 ? 1 : 0, tau_lo, tau_hi, bad);
+  hipLaunchKernelGGL(k_ip_band_tau, dim3((np + 3) / 4), dim3(256), 0, st, q_f32, np, b.d, centre, X, target, b.n, b.band(qnorm),
+                     b.kind() == IP_KIND_F16 ? 1 : 0, tau_lo, tau_hi, bad);
   CONVDR_CHECK_LAUNCH("k_ip_band_tau");
   const bool scan = b.n > 0 && !(b.row_bits && b.n_allowed == 0);     // (no allowed row: nothing precedes any target)
   uint32_t* marks = (uint32_t*)(ws + p.total);
@@ -345,13 +283,13 @@ static int ip_rank_rows(const IpDepth& depth, const IpBlock& b, const float* q_f
   }
   if (docs) {
     ProfScope prof("ip_docrank_finish", st);
-    const DocRankFinish f = {np, cap, b.n, hits, above_u, bad, list_id, list_x, target, X, qnorm, b.p_max_norm, b.scan_scale(),
-                             b.norm_limit(), docs->ord, docs->ndocs, mark_words, marks, rank, counts, above, status};
+    const DocRankFinish f = {np, cap, b.n, hits, above_u, bad, list_id, list_x, target, X, b.band(qnorm), docs->ord, docs->ndocs,
+                             mark_words, marks, rank, counts, above, status};
     if (int e = ip_docrank_finish(f, st)) return e;
   } else {
     ProfScope prof("ip_rank_finish", st);
     hipLaunchKernelGGL(k_ip_rank_finish, dim3(np), dim3(IP_RANK_THREADS), 0, st, cap, b.n, hits, above_u, bad, list_id, list_x, target,
-                       X, qnorm, b.p_max_norm, b.scan_scale(), b.norm_limit(), rank, counts, above, status);
+                       X, b.band(qnorm), rank, counts, above, status);
     CONVDR_CHECK_LAUNCH("k_ip_rank_finish");
   }
   return 0;

@@ -15,7 +15,7 @@ HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM
 
 RESERVED_ID = -(1 << 63)    # INT64_MIN: the free-slot marker of the key set (csrc/ip_keys.hpp), no legal row id
 KEY_ST_LIST, KEY_ST_PROBE, KEY_ST_COLUMN, KEY_ST_NOSET = 1, 2, 4, 8      # status bits of convdr_keyset_build / the row passes
-ROW_FILTER_TILE = 256       # the bitmap covers whole scan tiles of this many rows (csrc/ip_topk.hip: Tile256::TR)
+ROW_FILTER_TILE = 256       # the bitmap covers whole scan tiles of this many rows (csrc/ip_scan.hpp: Tile256::TR)
 
 
 def pack_row_mask(mask):

@@ -226,7 +226,7 @@ class FlatIPIndex(_IndexStore):
         helps: call ``_rebuild_scaled()`` (search_tensors / search_finish do) and search again.  Callers that take one
         uncertified pass (search_sharded_device(certify=False), the C ABI) must treat any non-zero status as "no result"."""
         cap = cap or self.cap
-        while cap < 2 * k and cap < 8192:      # the candidate list holds at least 2k entries (csrc/ip_topk.hip: k <= cap / 2)
+        while cap < 2 * k and cap < 8192:      # the candidate list holds at least 2k entries (csrc/ip_host.hpp, ip_check_sizes: k <= cap / 2)
             cap *= 2
         return self._enqueue(q, k, tau_in, cap, self.precision in _SPLIT if x3 is None else x3, allowed=self._filter(allowed))
 

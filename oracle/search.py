@@ -19,7 +19,7 @@ Restates:
 
 Canonical score.  FAISS computes scores with an fp32 SGEMM whose summation order
 is unspecified, so no bit-exact score exists to match.  This oracle (and the HIP
-rescoring kernel, convdr_amd/csrc/ip_topk.hip) define ONE canonical value:
+re-score, ip_row_score in convdr_amd/csrc/ip_certify.hpp) define ONE canonical value:
 
     vectors are zero-padded to a multiple of 256; lane l (0..63) owns the elements
     256 j + 4 l + c  (j = 0.., c = 0..3: one float4 per 1 KB line) and accumulates

@@ -124,8 +124,8 @@ def test_targets_through_the_depth(torch_cuda, n, nq, d, clustered, storage, pre
 
 
 def _documented_eps(shape, precision, Q, P):
-    """the band of k_ip_cut in UNSCALED units, from the coefficients documented in csrc/ip_topk.hip (ip_eps_coef): per query,
-    coef |q| max|p - centre|, +1 % for the fp16 scan's absolute term (about 0.1 % at these scales) and the 1.001 factors"""
+    """the band (IpBand::eps, csrc/ip_certify.hpp) in UNSCALED units, from the coefficients documented in csrc/ip_topk.hip
+    (ip_eps_coef): per query, coef |q| max|p - centre|, +1 % for the fp16 scan's absolute term (about 0.1 % at these scales) and the 1.001 factors"""
     d_pad = (shape[2] + 63) // 64 * 64
     u = 2.0 ** -8 if precision == "bf16" else 2.0 ** -11
     coef = 2 * u + u * u + d_pad / 8388608.0
