@@ -382,6 +382,10 @@ extern "C" int convdr_set_option(const char* name, int64_t value) {
     g_hm_blocked = value;
     return 0;
   }
+  if (strcmp(name, "mfma16") == 0) {   // blocked FFN1 / QKV tiles of the forward: 1 the 16x16x32 MFMA main loop, 0 the 32x32x16 kernels (gemm_launch.hpp)
+    g_mfma16 = value;
+    return 0;
+  }
   if (strcmp(name, "cls_fold") == 0) {   // last layer, CLS pooling: 1 Wk / Wv folded through the CLS query (cls_fold.hpp), 0 K / V projection + CLS_Q attention
     g_cls_fold = value;
     return 0;

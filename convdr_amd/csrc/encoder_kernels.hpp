@@ -17,6 +17,8 @@
 //   ctx  [rows, H]  bf16   attention output
 //   Hm   [rows, I]  bf16   gelu(FFN1)
 #pragma once
+#include <type_traits>
+
 #include "../../include/convdr_hip.h"
 #include "dropout.hpp"
 #include "gemm_nt.hpp"
@@ -668,10 +670,16 @@ struct CTile {
 // gemm_launch.hpp launches one workgroup per CU-slot).  While the epilogue of tile i runs, the first K chunk of tile
 // i + 1 is already streaming into the idle operand stage, so neither the workgroup dispatch gap nor the first
 // HBM/L2 round trip of a tile (~2-3 us of a ~20-30 us tile) is exposed.
-template <int EPI, class T>
+// MSHAPE: the MFMA shape of the main loop.  0 = 32x32x16 (every instantiation but two); 1 = 16x16x32 on the same LDS image
+// (gemm_nt_mainloop_r3_m16: the chip holds a higher clock on it), built for the inference forward's 256 x 256 FFN1
+// (EPI_GELU_BLK) and QKV (EPI_QKV with qk_blocked) tiles only -- its epilogues are the blocked one and the V third's.
+template <int EPI, class T, int MSHAPE = 0>
 static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using CT = CTile<T>;
+  constexpr bool M16 = MSHAPE == 1;
+  static_assert(MSHAPE == 0 || (M16 && (EPI == EPI_GELU_BLK || EPI == EPI_QKV) && T::WAVES == 8 && T::MT == 4 && T::NT == 2),
+                "16x16x32: blocked FFN1 / QKV on 256 x 256 tiles");
   const WavePos<T> w;
   const int64_t ldw = a.ldw ? a.ldw : a.K, ldx = a.ldx ? a.ldx : a.K;
   int kbeg = 0, klen = a.K;
@@ -755,9 +763,33 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a)
     const uint32_t next = idx + stride;
     const bool has_next = next < chunk_len;
     const Coord cn = has_next ? decode(next) : c;
-    GemmAcc<T> acc;
-    float bias_lane[T::NT];   // V third only
-    if (c.swap) {
+    std::conditional_t<M16, GemmAcc16<T>, GemmAcc<T>> acc;
+    float bias_lane[M16 ? 2 * T::NT : T::NT];   // V third only
+    if constexpr (M16) {
+      // 16x16x32 register layout (GemmAcc16): block (i, j) holds R indices 16 i + 4 (lane >> 4) + 0..3 of L index 16 j + (lane & 15)
+      if (c.swap) {
+        acc.zero();
+#pragma unroll
+        for (int j = 0; j < 2 * T::NT; ++j) {
+          const int f = c.n0 + w.wl * T::NT * 32 + 16 * j + (w.lane & 15);  // feature on the lane
+          bias_lane[j] = a.bias[f < a.N ? f : a.N - 1];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2 * T::NT; ++j) bias_lane[j] = 0.f;
+        const uint32_t sb = lds_off(sbias) + (w.wr * T::MT * 32 + 4 * (w.lane >> 4)) * 4;
+#pragma unroll
+        for (int i0 = 0; i0 < 2 * T::MT; i0 += 4) {
+          u32x4_t bq[4];
+          lds_read4_b128_hidden(sb + (i0 + 0) * 64, sb + (i0 + 1) * 64, sb + (i0 + 2) * 64, sb + (i0 + 3) * 64, bq[0], bq[1], bq[2], bq[3]);
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int j = 0; j < 2 * T::NT; ++j)
+              acc.c[i0 + g][j] = (f32x4){__uint_as_float(bq[g].x), __uint_as_float(bq[g].y), __uint_as_float(bq[g].z), __uint_as_float(bq[g].w)};
+        }
+      }
+    } else if (c.swap) {
       acc.zero();
 #pragma unroll
       for (int nt = 0; nt < T::NT; ++nt) {
@@ -807,7 +839,11 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a)
     }
     CONVDR_TRACE(0)
     int idle;   // the stage the last K step did not read
-    if constexpr (R3) {
+    if constexpr (M16) {
+      st = gemm_nt_mainloop_r3_m16<T>(src3, c.swap ? a.K : klen, smem, acc, w, st, true, true, landed || a.dbg_prelanded);
+      idle = 0;
+      sbias = sbias_of(st);
+    } else if constexpr (R3) {
       st = gemm_nt_mainloop_r3<T>(src3, c.swap ? a.K : klen, smem, acc, w, st, true, true, landed || a.dbg_prelanded,
                                   (a.trace && trace_tile == 8) ? a.trace + ((size_t)blockIdx.x * 64 + 56) * 16 : nullptr);
       idle = 0;
@@ -859,7 +895,7 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a)
           for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(res_pre[nt][mt][g].x), "+v"(res_pre[nt][mt][g].y));
     }
 #pragma unroll
-    for (int i = 0; i < T::NT; ++i) asm volatile("" : "+v"(bias_lane[i]));
+    for (int i = 0; i < (M16 ? 2 * T::NT : T::NT); ++i) asm volatile("" : "+v"(bias_lane[i]));
     if (threadIdx.x < T::TR) sbias[threadIdx.x] = bias_next;   // (every wave has read this tile's slice before its
     CONVDR_TRACE(1)                                             //  first main-loop barrier; nothing is in flight here)
     if (has_next) {
@@ -890,6 +926,82 @@ static __global__ void __launch_bounds__(T::THREADS, 2) k_gemm(const GemmArgs a)
     const int64_t t0 = c.t0;
     const int n0 = c.n0;
 
+    if constexpr (M16) {
+      const int q16 = we.lane >> 4, l16 = we.lane & 15;
+      lds_barrier();   // every wave is done with the last K step's slots (and the next tile's sbias is visible)
+      if (c.swap) {
+        // ---- V third -> Vt[feature][token]: the same wave-local parked image as the 32x32x16 form (row = feature, 128
+        // tokens of 2 bytes, 16-byte chunk index XOR row), written from the 16x16x32 layout: block (i, j) holds tokens
+        // 16 i + 4 q + 0..3 -- the q & 1 half of chunk 2 i + (q >> 1) -- of feature 16 j + (lane & 15); store_w as it is ----
+#pragma unroll
+        for (int pass = 0; pass < CT::PASSES; ++pass) {
+          static_assert(CT::NTP == 1, "a pass is one 32-feature block: two 16-feature MFMA blocks");
+          const uint32_t wb = CT::wave_base(sC, we.wave);
+#pragma unroll
+          for (int jl = 0; jl < 2; ++jl) {
+            const int j = 2 * pass + jl;
+            const float bv = bias_lane[j];
+            const int row = jl * 16 + l16;
+#pragma unroll
+            for (int i = 0; i < 2 * T::MT; ++i) {
+              const f32x4& v = acc.c[i][j];
+              lds_write_b64_hidden(wb + row * (CT::CW * 16) + (((2 * i + (q16 >> 1)) ^ (row & (CT::CW - 1))) << 4) + (q16 & 1) * 8,
+                                   (u32x2_t){pack_bf16x2(v[0] + bv, v[1] + bv), pack_bf16x2(v[2] + bv, v[3] + bv)});
+            }
+          }
+          if (pass == CT::PASSES - 1 && has_next) {   // the prefetch has had the whole epilogue to land: retire it
+            lds_dma_wait_all();                        // BEFORE the last stores enter the (in-order) queue
+            landed = true;
+          }
+          const int row0 = (we.wl * T::NT + pass * CT::NTP) * 32, col0 = we.wr * T::MT * 32;   // feature / token offsets
+          CT::store_w(a.nt_out != 0, wb, we.lane, a.Vt + (int64_t)(n0 + (a.third0 - 2) * a.H + row0) * a.ldt + t0 + col0, a.ldt,
+                      a.N - n0 - row0, a.rows - t0 - col0);
+        }
+      } else {
+        // ---- blocked bf16 output [rows / 32][cols / 8][32][8] straight from the registers.  Lane (q, t) of block (i, j) holds
+        // features 16 i + 4 q + 0..3 of token 16 j + t.  v_permlane16_swap over the packed blocks (i, 2 g) and (i, 2 g + 1)
+        // hands every lane one whole octet: lane row q then owns octet 2 i + (q >> 1) of token 16 (q & 1) + t of the
+        // 32-token group g -- a wave instruction stores the two whole 512-byte octet blocks 2 i, 2 i + 1 (1 KB contiguous) ----
+        const int64_t rows32 = (a.rows + 31) & ~(int64_t)31;
+        bf16_t* dstm = a.Cb;
+        int oct_w = a.N >> 3, f0 = n0;
+        if constexpr (EPI == EPI_QKV) {
+          const int na = n0 + a.third0 * a.H;
+          dstm = na < a.H ? a.Qo : a.Ko;
+          f0 = na < a.H ? na : na - a.H;
+          oct_w = a.H >> 3;
+        }
+#pragma unroll
+        for (int g = 0; g < T::NT; ++g) {
+          const int64_t tb = t0 + (we.wl * T::NT + g) * 32;   // first token of this 32-token group (wave-uniform)
+          if (g == T::NT - 1 && has_next) {   // the prefetch is retired BEFORE the last stores enter the (in-order) queue
+            lds_dma_wait_all();
+            landed = true;
+          }
+          bf16_t* blk = dstm + ((tb >> 5) * oct_w + ((f0 + we.wr * T::MT * 32) >> 3) + (q16 >> 1)) * 256 + ((q16 & 1) * 16 + l16) * 8;
+#pragma unroll
+          for (int i = 0; i < 2 * T::MT; ++i) {
+            uint2 o[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              const f32x4& v = acc.c[i][2 * g + e];
+              float y0 = v[0], y1 = v[1], y2 = v[2], y3 = v[3];   // bias included
+              if constexpr (EPI == EPI_GELU_BLK) { gelu_tail2(y0, y1); gelu_tail2(y2, y3); }
+              o[e].x = pack_bf16x2(y0, y1);
+              o[e].y = pack_bf16x2(y2, y3);
+            }
+            // the swap exchanges the odd lane rows of its first operand with the even lane rows of its second: lane row q ends
+            // up with features +0..3 (first result) and +4..7 (second) of its octet, for token block 2 g + (q & 1)
+            const auto sx = __builtin_amdgcn_permlane16_swap(o[0].x, o[1].x, false, false);
+            const auto sy = __builtin_amdgcn_permlane16_swap(o[0].y, o[1].y, false, false);
+            u32x4_t q4;
+            q4.x = sx[0]; q4.y = sy[0]; q4.z = sx[1]; q4.w = sy[1];
+            if (tb < rows32 && n0 + we.wr * T::MT * 32 + i * 16 < a.N)
+              store16<NT_GEMM_BLK>(blk + (int64_t)(2 * i) * 256, q4);
+          }
+        }
+      }
+    } else
     if (a.dbg_skip_epi == 1) {
       float s = 0.f;
 #pragma unroll

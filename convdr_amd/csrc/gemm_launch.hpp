@@ -13,13 +13,18 @@ inline void* g_attn_trace = nullptr;
 inline void* g_clock_probe = nullptr;   // convdr_set_option "clock_probe": [slots][4] uint64, one slot per FFN1 launch (round robin)
 inline int64_t g_clock_probe_slots = 1, g_clock_probe_next = 0;
 
-template <int EPI, class T>
+// convdr_set_option "mfma16": 1 (default) = the inference forward's 256 x 256 FFN1 (EPI_GELU_BLK) and QKV (EPI_QKV with blocked Q / K)
+// tiles run the 16x16x32 MFMA main loop (k_gemm<.., 1>: same LDS image, higher delivered clock; profiles/mfma16_ab.txt),
+// 0 = the 32x32x16 kernels every other launch uses (tests and A/B runs exercise both)
+inline int64_t g_mfma16 = getenv("CONVDR_MFMA16") ? atoi(getenv("CONVDR_MFMA16")) : 1;
+
+template <int EPI, class T, int MSHAPE = 0>
 inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
   static_assert(T::TR == T::TL || EPI != EPI_QKV, "square tiles: the QKV kernel swaps operand roles per tile");
   static DeviceOnce attr_done;   // function attributes are per device
   if (attr_done.first()) {
     CONVDR_CHECK_HIP(
-        hipFuncSetAttribute((const void*)k_gemm<EPI, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute((const void*)k_gemm<EPI, T, MSHAPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             T::WAVES == 8 ? 160 * 1024 : T::SMEM_BYTES + T::TR * 4));
   }
 #ifdef CONVDR_ENABLE_TRACE   // timing experiments that produce garbage results: only in the `make TRACE=1` library
@@ -55,13 +60,13 @@ inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
   int64_t grid = (int64_t)a.tilesN * a.tilesT;
   if (splits == 1 && grid > slots) grid = slots;
   const size_t lds = T::WAVES == 8 ? 160 * 1024 : T::SMEM_BYTES + T::TR * 4;
-  hipLaunchKernelGGL((k_gemm<EPI, T>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
+  hipLaunchKernelGGL((k_gemm<EPI, T, MSHAPE>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
 #ifdef CONVDR_ENABLE_TRACE
   // CONVDR_DBG_DOUBLE (tools/dbg/double_probe.sh): a class of idempotent launches goes out TWICE -- the step's difference is that
   // class's marginal cost with the product's own operands (1 = the training / inference forward's GEMMs, 2 = data-gradient GEMMs)
   static const int dbl = getenv("CONVDR_DBG_DOUBLE") ? atoi(getenv("CONVDR_DBG_DOUBLE")) : 0;
   if (dbl & (strcmp(prof_name, "gemm_dgrad") == 0 ? 2 : strncmp(prof_name, "gemm_", 5) == 0 && strcmp(prof_name, "gemm_cls") != 0 ? 1 : 0))
-    hipLaunchKernelGGL((k_gemm<EPI, T>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
+    hipLaunchKernelGGL((k_gemm<EPI, T, MSHAPE>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
 #endif
   CONVDR_CHECK_LAUNCH("k_gemm");
   return 0;
@@ -122,6 +127,9 @@ inline int launch_gemm(GemmArgs a, hipStream_t st, const char* prof_name) {
     }
   }
   if (fits && a.tile_hint == 256) choice = 256;
+  if constexpr (EPI == EPI_GELU_BLK || EPI == EPI_QKV) {
+    if (choice == 256 && g_mfma16 != 0 && (EPI != EPI_QKV || a.qk_blocked)) return launch_gemm_t<EPI, Tile256, 1>(a, st, prof_name);
+  }
   if (choice == 256) return launch_gemm_t<EPI, Tile256>(a, st, prof_name);
   if constexpr (WIDE_OK) {
     if (choice == 192) return launch_gemm_t<EPI, TileWide>(a, st, prof_name);

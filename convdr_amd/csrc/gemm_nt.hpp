@@ -446,6 +446,121 @@ __device__ __forceinline__ R3Slots gemm_nt_mainloop_r3(const TileSrcAll<T>& src,
   return R3Slots{rs, ls};
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The R3 K step on v_mfma_f32_16x16x32_bf16 (k_gemm's inference FFN1 and QKV tiles).  Same LDS image, same staging, same
+// slot contract; only the wave's 128 x 64 tile is computed as 8 x 4 blocks of 16 x 16 in two K = 32 sub-steps instead of
+// 4 x 2 blocks of 32 x 32 in four K = 16 sub-steps.  Why: these GEMMs run power-capped (~1.6-1.75 GHz of 2.4), and the chip
+// holds a higher clock on this shape -- stand-alone at the FFN1 shape, interleaved rounds in one process, random operands
+// (tools/proto/mfma16_proto.hip, profiles/mfma16_proto.txt): 2,566 -> 2,622 ticks per K step, 1,586 -> 1,751 MHz,
+// 1.654 -> 1.555 us of wall per K step.
+// An operand fragment is row (lane & 15), 16-byte k-chunk 4 s2 + (lane >> 4) of sub-step s2: with the image's swizzle
+// c ^ ((row >> 1) & 7) sixteen lanes cover sixteen distinct 16-byte slots of 256 B (conflict-free, like the 32-row read).
+// Registers: 8 R + 4 L fragments per sub-step; ONE set of R fragments -- the blocks are walked i-major, so fragment i is dead
+// after its 4 MFMAs and is re-read for sub-step 1 right there, ~28 MFMAs ahead of its use -- and two sets of L: 64 VGPRs.
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma_16x16x32(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// element reg of c[i][j] for lane l:  R index = wr*MT*32 + 16 i + 4 (l >> 4) + reg,  L index = wl*NT*32 + 16 j + (l & 15)
+template <class T>
+struct GemmAcc16 {
+  static constexpr int MB = 2 * T::MT, NB = 2 * T::NT;
+  f32x4 c[MB][NB];
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) c[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+};
+
+template <class T, bool F16 = false, int R_AUX = 0>
+__device__ __forceinline__ R3Slots gemm_nt_mainloop_r3_m16(const TileSrcAll<T>& src, int K, char* smem, GemmAcc16<T>& acc,
+                                                           const WavePos<T>& w, R3Slots st = R3Slots{0, 0},
+                                                           bool prologue_in_flight = false, bool r1_deferred = false,
+                                                           bool stage0_landed = false) {
+  constexpr int MB = GemmAcc16<T>::MB, NB = GemmAcc16<T>::NB;
+  static_assert(MB == 8 && NB == 4, "the read schedule below is written for the 128 x 64 wave tile");
+  constexpr int R_DPW = R3Issue<T>::R_DPW;
+  const bool r_wave = R3Issue<T>::issues_r(w.wave);
+  const int nk = K / GEMM_BK;
+  const int sw = (w.lane >> 1) & 7;   // (row >> 1) & 7 of row = 16 n + (lane & 15)
+  const int q = w.lane >> 4;
+  const int offR = (w.wr * T::MT * 32 + (w.lane & 15)) * 128;
+  const int offL = (w.wl * T::NT * 32 + (w.lane & 15)) * 128;
+  const int ch0 = ((0 + q) ^ sw) * 16, ch1 = ((4 + q) ^ sw) * 16;   // this lane's chunk of sub-step 0 / 1
+  char* sR = smem;
+  char* sL = smem + 3 * T::R_BYTES;
+  if (!prologue_in_flight) gemm_r3_prologue<T, R_AUX>(src, K, smem, w, st, !r1_deferred);
+  int rs = st.rs, ls = st.ls;
+  for (int kt = 0; kt < nk; ++kt) {
+    // (waits, barrier and DMA issue exactly as in gemm_nt_mainloop_r3)
+    if (kt == 0 && (r1_deferred || stage0_landed)) {
+      if (!stage0_landed) lds_dma_wait_all();
+    } else if (kt + 1 < nk && r_wave) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(R_DPW) : "memory");
+    else lds_dma_wait_all();
+    lds_barrier();
+    const char* tR = sR + rs * T::R_BYTES + offR;
+    const char* tL = sL + ls * T::L_BYTES + offL;
+    bf16x8 fa[MB], fb[2][NB];
+    auto rdR = [&](int s2, int i) { return *(const bf16x8*)(tR + i * 16 * 128 + (s2 ? ch1 : ch0)); };
+    auto rdL = [&](int s2, int j) { return *(const bf16x8*)(tL + j * 16 * 128 + (s2 ? ch1 : ch0)); };
+    // what the first two MFMA rows need, as a block (6 reads, as many as the 32x32x16 loop has here)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) fb[0][j] = rdL(0, j);
+    fa[0] = rdR(0, 0);
+    fa[1] = rdR(0, 1);
+    const bool issue_l = kt + 1 < nk, issue_r = kt + 2 < nk;
+    char* l_dst = sL + (ls ^ 1) * T::L_BYTES;
+    const int rnext = rs == 0 ? 2 : rs - 1;
+    char* r_dst = sR + rnext * T::R_BYTES;
+    __builtin_amdgcn_sched_barrier(0);
+    if (r1_deferred && kt == 0 && issue_l) R3Issue<T>::template r<R_AUX>(src.R, 1, sR + (rs == 2 ? 0 : rs + 1) * T::R_BYTES, w.wave);
+    if (issue_l) R3Issue<T>::l(src.L, kt + 1, l_dst, w.wave);
+    // sub-step 0: one ds_read_b128 behind each of the first 12 MFMAs (the rest of this sub-step's R fragments, the L
+    // fragments of sub-step 1, the first two R re-reads), then one R re-read behind each finished row of 4 MFMAs
+#pragma unroll
+    for (int i = 0; i < MB; ++i) {
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        acc.c[i][j] = mfma_16x16x32<F16>(fa[i], fb[0][j], acc.c[i][j]);
+        const int m = NB * i + j;
+        if (m < 6) fa[m + 2] = rdR(0, m + 2);
+        else if (m < 10) fb[1][m - 6] = rdL(1, m - 6);
+        else if (m < 12) fa[m - 10] = rdR(1, m - 10);
+      }
+      if (i >= 3) fa[i - 1] = rdR(1, i - 1);
+    }
+    fa[MB - 1] = rdR(1, MB - 1);
+#pragma unroll
+    for (int r = 0; r < 12; ++r) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one DS read
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    // sub-step 1: every fragment is in registers
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) acc.c[i][j] = mfma_16x16x32<F16>(fa[i], fb[1][j], acc.c[i][j]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (issue_r) R3Issue<T>::template r<R_AUX>(src.R, kt + 2, r_dst, w.wave);
+    rs = rs == 2 ? 0 : rs + 1;
+    ls ^= 1;
+  }
+  return R3Slots{rs, ls};
+}
+
 // convenience form: contraction range [k_begin, k_begin + K) of R[r0.., :] and L[l0.., :]
 template <class T>
 __device__ __forceinline__ int gemm_nt_mainloop(const bf16_t* __restrict__ R, int64_t ldr, int64_t nR,

@@ -3,6 +3,7 @@ def funcs(path, ren):
     s=open(path).read()
     s=re.sub(r'__hip_cuid_[0-9a-f]+','__hip_cuid_X',s)
     for a,b in ren: s=s.replace(a,b)
+    s=re.sub(r'(k_gemmILi\d+ENS_7TileCfgILi\d+ELi\d+ELi\d+ELi\d+EEE)Li0E',r'\1',s)   # k_gemm<EPI, T, 0> is k_gemm<EPI, T> of before the MFMA shape parameter
     d={}
     for m in re.finditer(r'^(_Z\w+):.*?\n(.*?)^\.Lfunc_end\d+:', s, re.S|re.M):
         body=re.sub(r'\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?','.L',m.group(2))
