@@ -64,7 +64,14 @@ _SIGNATURES = {
     "convdr_ip_rank_docs_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64]),
     "convdr_ip_rank_docs": (C.c_int, [C.c_int, _p, C.c_int, _p, _p, _p, C.c_float, _p, C.c_int64, C.c_int, _p, _p, C.c_int64,
                                       C.c_int64, _p, C.c_int64, C.c_int, _p, C.c_size_t, _p, _p, _p, _p, _p, _p]),
-    "convdr_digest_rows": (C.c_int, [_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _p, _p]),
+    "convdr_excl_build_rows": (C.c_int, [_p, C.c_int, C.c_int, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, _p]),
+    "convdr_excl_build_docs": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int, C.c_int, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, _p]),
+    "convdr_excl_drop_topk": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int64, _p, C.c_int64, _p, C.c_int, _p, _p, _p, _p]),
+    "convdr_excl_count_ragged": (C.c_int, [_p, _p, C.c_int64, C.c_int, _p, C.c_int64, _p, _p, _p]),
+    "convdr_excl_pack_ragged": (C.c_int, [_p, _p, _p, C.c_int64, C.c_int, _p, C.c_int64, _p, _p, _p, _p, C.c_int64, _p]),
+    "convdr_ip_excl_count_ahead": (C.c_int, [C.c_int, _p, C.c_int, _p, _p, C.c_float, C.c_int64, C.c_int, _p, C.c_int64, _p, C.c_int64,
+                                             _p, C.c_int, _p, _p, _p, _p, _p]),
+    "convdr_digest_rows": (C.c_int,[_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _p, _p]),
     "convdr_digest_host": (C.c_int, [_p, C.c_int64, C.c_uint64, _p]),
     "convdr_ip_debug_counts":(_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "convdr_ip_debug_band": (_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),

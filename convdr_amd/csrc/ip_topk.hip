@@ -87,6 +87,8 @@ constexpr float IP_F16_NORM_LIMIT = 60000.f; // scaled norms above this may hold
 #include "ip_keys.hpp"
 // documents by id: all rows of the listed keys as a CSR, the MaxP score of (query, document) pairs (convdr_keys_rows_*, convdr_ip_score_docs)
 #include "ip_docs.hpp"
+// per-query exclusion lists: the canonical rows, the drop from certified lists, the count of excluded rows ahead (convdr_excl_*, convdr_ip_excl_count_ahead)
+#include "ip_exclude.hpp"
 // document rank: dense document numbers of the id column, the marking band scan's finish (convdr_doc_ordinals, convdr_ip_rank_docs)
 #include "ip_docrank.hpp"
 // the digest a snapshot file is checked against, on the device and on the host (convdr_digest_rows, convdr_digest_host)

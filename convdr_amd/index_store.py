@@ -52,6 +52,80 @@ class RowFilter:
         return self._rows
 
 
+EXCLUDE_MAX = 16384         # entries per query of an exclusion list, before de-duplication (csrc/ip_exclude.hpp: EXCL_MAX_ENTRIES)
+EXCL_ST_ROW, EXCL_ST_LONG = 1, 2     # status bits of convdr_excl_build_*: a row >= ntotal; more than EXCLUDE_MAX entries
+
+
+def pack_exclusions(rows, nq):
+    """The per-query exclusion lists of `nq` queries as ONE padded int64 array [nq, e] (negative = padding): the checks that
+    need no device.  rows: an integer array [nq, e] (numpy, or a torch tensor on any device: returned as int64 where it lives),
+    or a host sequence of nq integer sequences of different lengths (padded with -1 to the longest).  Any order, repeats
+    allowed.  ValueError for another shape, a non-integer dtype (bool included), or more than EXCLUDE_MAX = 16,384 entries per
+    query -- of an array, the width e (padding included: it is what the build sorts); of a sequence, its length."""
+    import torch
+    nq = int(nq)
+
+    def width_ok(e):
+        if e > EXCLUDE_MAX:
+            raise ValueError("exclude: %d entries per query, at most %d" % (e, EXCLUDE_MAX))
+    if isinstance(rows, torch.Tensor):
+        if rows.dim() != 2 or int(rows.shape[0]) != nq:
+            raise ValueError("exclude: rows must be [nq, e] with nq = %d (got shape %s)" % (nq, tuple(rows.shape)))
+        if rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+            raise ValueError("exclude: rows must be integers (got %s)" % rows.dtype)
+        width_ok(int(rows.shape[1]))
+        return rows.to(torch.int64)
+    if isinstance(rows, np.ndarray) and rows.dtype != object:
+        if rows.ndim != 2 or rows.shape[0] != nq:
+            raise ValueError("exclude: rows must be [nq, e] with nq = %d (got shape %s)" % (nq, rows.shape))
+        if rows.dtype.kind not in "iu":
+            raise ValueError("exclude: rows must be integers (got %s)" % rows.dtype)
+        width_ok(rows.shape[1])
+        return rows.astype(np.int64)
+    try:
+        lists = list(rows)
+    except TypeError:
+        raise ValueError("exclude: rows must be an integer array [nq, e] or a sequence of nq integer sequences") from None
+    if len(lists) != nq:
+        raise ValueError("exclude: %d lists for nq = %d queries" % (len(lists), nq))
+    cols = []
+    for j, one in enumerate(lists):
+        if isinstance(one, torch.Tensor):
+            one = one.cpu().numpy()
+        a = np.asarray(one)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("exclude: the list of query %d must be a sequence of integers (got %s, shape %s)" % (j, a.dtype, a.shape))
+        width_ok(a.size)
+        cols.append(a.astype(np.int64))
+    out = np.full((nq, max([c.size for c in cols], default=0)), -1, dtype=np.int64)
+    for j, c in enumerate(cols):
+        out[j, :c.size] = c
+    return out
+
+
+class QueryExclusions:
+    """Per-query excluded rows of an index (FlatIPIndex.exclude_rows / exclude_ids), the operand of ``FlatIPIndex.excluding`` (the exact entries with per-query exclusions):
+    `rows` the device lists [nq, ld] (int32 words, the bytes of uint32: each query's excluded rows ascending and distinct, then
+    0xffffffff; ld a multiple of 4), `count` device int32 [nq]; on the host `nq`, `n` (the ntotal it was built for) and `e_max`
+    (the longest list), all from the build's one host read.  Reusable across calls; ``select(idx)`` takes a subset of the queries.
+    Stale under RowFilter's rule: another ntotal or device raises ValueError -- and, as for a RowFilter, ``upsert_docs`` may move
+    rows without changing ntotal: rebuild after it."""
+
+    def __init__(self, rows, count, counts_host, n):
+        self.rows, self.count, self.n = rows, count, int(n)
+        self._host = np.asarray(counts_host, dtype=np.int64).reshape(-1)
+        self.nq = int(self._host.size)
+        self.e_max = int(self._host.max()) if self.nq else 0
+
+    def select(self, idx):
+        """the exclusions of the queries `idx` (integer indices: a sequence, numpy or torch), in that order; no device read
+        unless `idx` lives on a device"""
+        import torch
+        i = (idx.cpu().numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)).astype(np.int64).reshape(-1)
+        t = torch.as_tensor(i, device=self.rows.device)
+        return QueryExclusions(self.rows[t].contiguous(), self.count[t].contiguous(), self._host[i], self.n)
+
+
 class DocOrdinals:
     """Dense document numbers of an index's id column (FlatIPIndex.doc_ordinals): `ord` the device vector [ntotal] (int32
     words, the bytes of uint32: ord[r] = the number of distinct ids whose first row lies below the first row of ids[r]),
@@ -960,6 +1034,82 @@ class _IndexStore:
                        "convdr_doc_ordinals")
             ndocs = int(self._key_read("doc_ordinals", [nd], ws)[0])
         return DocOrdinals(ord_, ndocs, n)
+
+    # -- per-query exclusions: the rows each query of a call leaves out (include/convdr_hip.h, "Per-query exclusions") ----------
+    def exclude_rows(self, rows):
+        """A QueryExclusions from row numbers: rows int64 [nq, e] (numpy or torch, host or device; any order, repeats allowed,
+        negative = padding) or a host list of nq integer sequences of different lengths (``pack_exclusions``).  At most 16,384
+        entries per query.  Sorted and de-duplicated per query on the device (convdr_excl_build_rows); ONE host read (the
+        counts and the status word).  A host row id >= ntotal raises ValueError before anything is launched, a device one
+        after that read.  Pass it to ``excluding``; valid while ntotal stays what it was."""
+        return self._exclusions(rows, int(rows.shape[0]) if hasattr(rows, "shape") else len(rows))
+
+    def exclude_ids(self, ids):
+        """A QueryExclusions from document ids: ids int64 [nq, m] (numpy or torch, host or device; INT64_MIN = padding); query j
+        excludes EVERY row of every document it lists -- resolved on the device through the CSR of ``rows_all`` and
+        convdr_excl_build_docs --, an id on no row excludes nothing.  Needs an id column.  Two host reads: the CSR's size, then
+        the counts and the status word -- more than 16,384 rows for one query raise ValueError there."""
+        import torch
+        self._need_ids("exclude_ids")
+        it = torch.as_tensor(np.array(ids) if isinstance(ids, np.ndarray) and not ids.flags.writeable else ids)
+        if it.dim() != 2 or it.dtype != torch.int64:
+            raise ValueError("exclude_ids: ids must be int64 [nq, m] (got %s, shape %s)" % (it.dtype, tuple(it.shape)))
+        nq, m = int(it.shape[0]), int(it.shape[1])
+        if m > EXCLUDE_MAX:
+            raise ValueError("exclude_ids: %d ids per query, at most %d entries" % (m, EXCLUDE_MAX))
+        if not nq or not m:
+            return self._exclude_build("exclude_ids", nq, 4, None)
+        start, count, rows, _ = self._rows_csr("exclude_ids", it.to(self.device).reshape(-1).contiguous(), reserved_ok=True)
+        tot, L, ptr = int(rows.numel()), _lib.lib(), _lib.ptr
+        return self._exclude_build("exclude_ids", nq, min(EXCLUDE_MAX, tot), lambda ex, ld, cnt, st: _lib.check(
+            L.convdr_excl_build_docs(ptr(rows), tot, ptr(start), ptr(count), nq, m, m, self.ntotal, ptr(ex), ld, ptr(cnt), ptr(st),
+                                     _lib.stream_ptr()), "convdr_excl_build_docs"))
+
+    def _exclude_build(self, who, nq, width, launch):
+        """The build's outputs, its launch (None: every list is empty) and its ONE host read -> QueryExclusions"""
+        import torch
+        ld = max(4, (int(width) + 3) // 4 * 4)
+        ex = torch.full((nq, ld), -1, dtype=torch.int32, device=self.device)          # (0xffffffff: the padding)
+        out = torch.zeros(nq + 1, dtype=torch.int32, device=self.device)             # counts | status
+        if launch is None or not nq:
+            return QueryExclusions(ex, out[:nq], np.zeros(nq, np.int64), self.ntotal)
+        with torch.cuda.device(self.device):
+            launch(ex, ld, out[:nq], out[nq:])
+        host = out.cpu().numpy()
+        if host[nq] & EXCL_ST_LONG:
+            raise ValueError("%s: a query excludes more than %d rows (repeats counted)" % (who, EXCLUDE_MAX))
+        if host[nq] & EXCL_ST_ROW:
+            raise ValueError("%s: a row id >= ntotal = %d" % (who, self.ntotal))
+        used = max(4, (int(host[:nq].max()) + 3) // 4 * 4)
+        return QueryExclusions(ex if used == ld else ex[:, :used].contiguous(), out[:nq], host[:nq], self.ntotal)
+
+    def _exclusions(self, exclude, nq):
+        """the exclusions of a call with nq queries -> None or a QueryExclusions that fits this index and those queries; a raw
+        [nq, e] array or a list of lists is built for the call"""
+        import torch
+        if exclude is None:
+            return None
+        if isinstance(exclude, QueryExclusions):
+            if exclude.n != self.ntotal or exclude.rows.device != self.device:
+                raise ValueError("stale QueryExclusions: built for ntotal = %d on %s, the index holds %d rows on %s"
+                                 % (exclude.n, exclude.rows.device, self.ntotal, self.device))
+            if exclude.nq != nq:
+                raise ValueError("exclude: built for %d queries, the call has %d" % (exclude.nq, nq))
+            return exclude
+        arr = pack_exclusions(exclude, nq)
+        if isinstance(arr, np.ndarray):
+            if arr.size and int(arr.max()) >= self.ntotal:
+                raise ValueError("exclude: row id %d >= ntotal = %d" % (int(arr.max()), self.ntotal))
+            arr = torch.as_tensor(arr)
+        elif arr.device.type == "cpu" and arr.numel() and int(arr.max()) >= self.ntotal:
+            raise ValueError("exclude: row id %d >= ntotal = %d" % (int(arr.max()), self.ntotal))
+        t, e = arr.to(self.device).contiguous(), int(arr.shape[1])
+        if not e:
+            return self._exclude_build("exclude_rows", nq, 4, None)
+        L, ptr = _lib.lib(), _lib.ptr
+        return self._exclude_build("exclude_rows", nq, e, lambda ex, ld, cnt, st: _lib.check(
+            L.convdr_excl_build_rows(ptr(t), nq, e, e, self.ntotal, ptr(ex), ld, ptr(cnt), ptr(st), _lib.stream_ptr()),
+            "convdr_excl_build_rows"))
 
     def reconstruct_docs(self, ids):
         """All chunk rows of the listed documents: numpy (start int64 [m], count int32 [m], emb float32 [total, d_in]) --

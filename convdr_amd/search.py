@@ -20,8 +20,8 @@ from . import _lib
 # (what lives in the modules this one was split into stays importable from here)
 from .block_search import (EvalDevQuery, _check_distinct_certificate, _load_collection, _Passages, _search_block_list, load_block,
                            search_distinct_one_by_one, search_one_by_one)
-from .index_store import (_HALF_PRECISIONS, _KINDS, HALF_NORM_LIMIT, KEY_ST_COLUMN, KEY_ST_LIST, KEY_ST_NOSET, KEY_ST_PROBE, RESERVED_ID,
-                          ROW_FILTER_TILE, DocOrdinals, RowFilter, _IndexStore, pack_row_mask)
+from .index_store import (_HALF_PRECISIONS, _KINDS, EXCLUDE_MAX, HALF_NORM_LIMIT, KEY_ST_COLUMN, KEY_ST_LIST, KEY_ST_NOSET, KEY_ST_PROBE,
+                          RESERVED_ID, ROW_FILTER_TILE, DocOrdinals, QueryExclusions, RowFilter, _IndexStore, pack_exclusions, pack_row_mask)
 from .snapshot import read_header as snapshot_info, verify_file as verify_snapshot
 from .staging import (_NUMA, _POOLS, _STAGING, _STAGING_BUILD, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _on_cpus, _staging, _staging_key,
                       gpu_numa_cpus, pinned_near)
@@ -42,6 +42,9 @@ _Depth = collections.namedtuple("_Depth", "enqueue max_cap shortcut last_rung la
 # the enqueued first pass or None (nothing to scan: deep search of an empty index, or a filter that allows no row),
 # allowed = the RowFilter of a restricted search or None
 _Pending = collections.namedtuple("_Pending", "qt k depth x3 cap first allowed", defaults=(None,))
+# the handle of a search with per-query exclusions: the _Pending of the search at the depth k' = k + e_max, the QueryExclusions
+# and the caller's k
+_PendingExcluded = collections.namedtuple("_PendingExcluded", "pending exclusions k")
 
 
 def _radius_below(x):
@@ -139,9 +142,13 @@ class FlatIPIndex(_IndexStore):
         """Exact top-k DOCUMENTS: ``search_distinct`` with the index's own id column for keys -- no side table to keep in
         step.  Returns device (D fp32 [nq, k], ids int64 [nq, k], rows int64 [nq, k] = each document's best row, counts int32
         [nq, 2]); padding (-3.4028235e38, -1, -1).  ``score_ids_tensors(q, ids)`` reproduces D and rows.  allowed: as for
-        ``search``; a filter may drop some chunk rows of a document (its best ALLOWED row then stands for it) or all of them."""
+        ``search``; a filter may drop some chunk rows of a document (its best ALLOWED row then stands for it) or all of them.
+        ``excluding(ex).search_docs`` applies per-query exclusions to the row lists before the distinct cut."""
+        return self._search_docs(q, k, allowed, depth, strict, max_depth, None)
+
+    def _search_docs(self, q, k, allowed, depth, strict, max_depth, exclude):
         self._need_ids("search_docs")
-        D, I, K, counts = self._search_distinct(q, k, self.ids, depth, strict, max_depth, allowed)
+        D, I, K, counts = self._search_distinct_rows(q, k, self.ids, depth, strict, max_depth, allowed, exclude)
         return D, K, I, counts
 
     def search_ids(self, q, k, allowed=None):
@@ -151,9 +158,12 @@ class FlatIPIndex(_IndexStore):
 
     def search_ids_tensors(self, q, k, allowed=None):
         """``search_tensors`` with I mapped through the id column on the device (-1 stays -1)."""
-        import torch
         self._need_ids("search_ids")
-        D, I = self.search_tensors(q, k, allowed=allowed)
+        return self._ids_of(*self.search_tensors(q, k, allowed=allowed))
+
+    def _ids_of(self, D, I):
+        """(D, I) of a row search -> (D, the rows' ids), -1 kept"""
+        import torch
         if not self.ntotal:
             return D, I
         return D, torch.where(I >= 0, self.ids[I.clamp(min=0)], torch.full_like(I, -1))
@@ -271,7 +281,8 @@ class FlatIPIndex(_IndexStore):
         """FAISS ``index.search``: numpy in, numpy (D, I) out; always the exact top-k (queries no scan can certify take the
         exhaustive rung, `stats["exhaustive_queries"]`).  allowed: a RowFilter (``row_filter``) or a bool / uint8 mask
         [ntotal], packed for this call -- the search is restricted to those rows (FAISS ``IDSelector``): the exact top-k of the
-        allowed rows, I in the index's row numbers, padding where fewer than k rows are allowed."""
+        allowed rows, I in the index's row numbers, padding where fewer than k rows are allowed.  Rows left out PER QUERY:
+        ``excluding(ex).search`` (ExcludedSearch)."""
         D, I = self.search_tensors(q, k, allowed=allowed)
         return D.cpu().numpy(), I.cpu().numpy()
 
@@ -307,6 +318,8 @@ class FlatIPIndex(_IndexStore):
         """The ladder, at either depth: fp16 (or pinned) first pass -> rebuild on RANGE -> retries with tau_retry / a doubled
         list -> split scan -> whatever is still open takes the depth's last rung."""
         import torch
+        if isinstance(handle, _PendingExcluded):
+            return self._finish_excluded(handle)
         qt, k, depth, x3, cap, first, allowed = handle
         kw = {} if allowed is None else {"allowed": allowed}    # (allowed=None: today's calls, argument for argument)
         nq = int(qt.shape[0])
@@ -375,6 +388,52 @@ class FlatIPIndex(_IndexStore):
                 self.stats["deep"] = nq - len(bad)
         return D, I
 
+    def excluding(self, exclude):
+        """The exact entries of this index with rows left out PER QUERY: an ExcludedSearch.  exclude: a QueryExclusions
+        (``exclude_rows`` / ``exclude_ids``, reusable across calls), or a raw int64 [nq, e] array or list of nq lists, built
+        for each call.  ``idx.excluding(ex).search(Q, k, allowed=f)`` is the exact top-k of the (allowed) rows that query j does
+        not exclude; likewise search_tensors, search_begin, search_ids(_tensors), search_docs, range_search(_tensors),
+        range_count and rank_rows(_tensors)."""
+        return ExcludedSearch(self, exclude)
+
+    def _search_begin_excluded(self, q, k, allowed, exclude):
+        """search_begin with per-query exclusions: the first pass is enqueued at the depth k' = k + e_max, the handle carries
+        the exclusions and the caller's k, search_finish drops and cuts."""
+        qt = self._queries(q)
+        k = int(k)
+        f = self._filter(allowed)
+        ex = self._exclusions(exclude, int(qt.shape[0]))
+        if k < 1:
+            raise ValueError("search: k = %d with exclusions" % k)
+        # all of the residual top-k lies in the first k + e_q entries of the (allowed) order; never deeper than the rows the
+        # search can return (DESIGN.md section 4, "Per-query exclusions")
+        rows = self.ntotal if f is None else f.n_allowed
+        deep = min(k + ex.e_max, max(k, rows))
+        return _PendingExcluded(self.search_begin(q, deep, **({} if f is None else {"allowed": f})), ex, k)
+
+    def _finish_excluded(self, handle):
+        """search_finish of a handle with exclusions: the certified lists at the depth k' the handle was begun with, then
+        convdr_excl_drop_topk -- per query the first k entries whose row it does not exclude.  A call whose lists are all
+        empty returns the search's own tensors."""
+        import torch
+        pending, ex, k = handle
+        deep = pending.k
+        D, I = self.search_finish(pending)
+        self.stats.update(exclude_depth=deep, excluded_dropped=0)
+        nq = int(D.shape[0])
+        if ex.e_max == 0 or nq == 0:
+            return D, I
+        D, I = D.contiguous(), I.contiguous()
+        Do = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        Io = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        kept = torch.empty(nq, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().convdr_excl_drop_topk(_lib.ptr(D), _lib.ptr(I), nq, deep, deep, _lib.ptr(ex.rows), int(ex.rows.shape[1]),
+                                                        _lib.ptr(ex.count), k, _lib.ptr(Do), _lib.ptr(Io), _lib.ptr(kept),
+                                                        _lib.stream_ptr()), "convdr_excl_drop_topk")
+        self.stats["excluded_dropped"] = int(((I >= 0).sum() - kept.sum()).item())
+        return Do, Io
+
     def search_distinct(self, q, k, keys, depth=None, strict=True, max_depth=None):
         """Exact top-k DISTINCT keys (documents) of a block whose rows carry keys with repeats (MaxP chunk rows, duplicate
         pids): per query the k best keys, each with its best row, in the canonical order of ``search``.
@@ -392,10 +451,16 @@ class FlatIPIndex(_IndexStore):
         return self._search_distinct(q, k, keys, depth, strict, max_depth, None)
 
     def _search_distinct(self, q, k, keys, depth, strict, max_depth, allowed):
+        """``_search_distinct_rows`` without exclusions"""
+        return self._search_distinct_rows(q, k, keys, depth, strict, max_depth, allowed, None)
+
+    def _search_distinct_rows(self, q, k, keys, depth, strict, max_depth, allowed, exclude):
         """``search_distinct`` with a row filter (``search_docs``).  allowed: a RowFilter or a mask as for ``search``, packed
         once for all passes, or None.  With a filter the result is the walk over the ALLOWED rows, the filter's ``n_allowed``
         takes ntotal's place in the depth defaults, and a query is certified iff it found k keys, or the list ran out of rows,
-        or m >= n_allowed.  None: search_distinct as it was."""
+        or m >= n_allowed.  None: search_distinct as it was.
+        exclude (``excluding(ex).search_docs``): per-query exclusions handed to the row search, sub-selected to the open queries.  The list
+        that comes back is a complete prefix of the residual order, so the certificate is the same one."""
         import torch
         qt = torch.as_tensor(q)
         k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
@@ -407,6 +472,7 @@ class FlatIPIndex(_IndexStore):
         keys = keys.contiguous()
         f = self._filter(allowed)
         kw = {} if f is None else {"allowed": f}
+        ex = self._exclusions(exclude, nq)
         rows = nt if f is None else f.n_allowed          # the rows the search can return
         limit = min(max_depth, rows)
         m = int(depth) if depth else min(max_depth, 2 * k, rows)
@@ -418,11 +484,12 @@ class FlatIPIndex(_IndexStore):
         if nq == 0:
             return D, I, K, counts
         qt = (qt if qt.dtype == torch.float32 else qt.float()).to(self.device)
-        todo = None                                     # indices of the queries still open (None: all)
+        todo = todo_host = None                         # indices of the queries still open (None: all)
         self.distinct_stats = {"depths": [], "searched": []}
         while True:
             qs = qt if todo is None else qt[todo].contiguous()
-            Dm, Im = self.search_tensors(qs, m, **kw)
+            who = self if ex is None else self.excluding(ex if todo is None else ex.select(todo_host))
+            Dm, Im = who.search_tensors(qs, m, **kw)
             Dd, Id, Kd, cd = distinct_topk_device(Dm, Im, k, keys)
             self.distinct_stats["depths"].append(m)
             self.distinct_stats["searched"].append(int(qs.shape[0]))
@@ -445,6 +512,7 @@ class FlatIPIndex(_IndexStore):
                 return D, I, K, counts
             sub = torch.as_tensor(open_, device=self.device)
             todo = sub if todo is None else todo[sub]
+            todo_host = open_ if todo_host is None else todo_host[open_]
             m = min(2 * m, limit)
 
     @property
@@ -611,6 +679,66 @@ class FlatIPIndex(_IndexStore):
         """int64 numpy [nq]: how many rows ``range_search`` would return per query, without ordering or packing them
         (1 + range_count(q, score of a known positive) is that positive's exact rank in the whole index)."""
         return self._range(q, radius, allowed, True)
+
+    def _excluded_ahead(self, ex, f, qt, pairq, x_thr, row_thr):
+        """convdr_ip_excl_count_ahead: device int64 [np], per pair (query pairq[p] of `qt`, threshold (x_thr[p], row_thr[p])) the
+        rows of that query's exclusion list that are allowed by `f` and precede the threshold in the canonical order.  No sync."""
+        import torch
+        ptr = _lib.ptr
+        npairs = int(pairq.numel())
+        ahead = torch.zeros(npairs, dtype=torch.int64, device=self.device)
+        if not npairs:
+            return ahead
+        store, r32, r16, scale, _ = self._operands(None if self.ntotal else (None, None))
+        bits = None if f is None else f.bits
+        pairq, x_thr, row_thr = pairq.to(torch.int32).contiguous(), x_thr.to(torch.float64).contiguous(), row_thr.to(torch.int64).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().convdr_ip_excl_count_ahead(
+                store, ptr(qt), int(qt.shape[0]), r32, r16, scale, self.ntotal, self.d, ptr(bits), 0 if bits is None else bits.numel(),
+                ptr(ex.rows), int(ex.rows.shape[1]), ptr(ex.count), npairs, ptr(pairq), ptr(x_thr), ptr(row_thr), ptr(ahead),
+                _lib.stream_ptr()), "convdr_ip_excl_count_ahead")
+        return ahead
+
+    def _range_excluded(self, q, radius, allowed, count_only, exclude):
+        """range_search / range_count with per-query exclusions: today's result, then the excluded rows taken out of it on the
+        device (convdr_excl_count_ragged, the exclusive scan, convdr_excl_pack_ragged; one host read, the new total) -- or, for
+        the count, the excluded allowed rows above the radius subtracted (nothing is listed).  ``stats`` gains excluded_dropped;
+        range_results counts what is returned."""
+        import torch
+        L, ptr = _lib.lib(), _lib.ptr
+        qt = self._queries(q)
+        nq = int(qt.shape[0])
+        f = self._filter(allowed)
+        ex = self._exclusions(exclude, nq)
+        res = self._range(q, radius, f, count_only)
+        self.stats["excluded_dropped"] = 0
+        if not nq or not ex.e_max:
+            return res
+        if count_only:
+            rad = self._range_radius(radius, nq)
+            ahead = self._excluded_ahead(ex, f, qt, torch.arange(nq, device=self.device), rad,
+                                         torch.full((nq,), -1, dtype=torch.int64, device=self.device)).cpu().numpy()
+            self.stats.update(excluded_dropped=int(ahead.sum()), range_results=int((res - ahead).sum()))
+            return res - ahead
+        lims, D, I = res
+        total = int(I.numel())
+        if not total:
+            return res
+        lims = lims.contiguous()
+        ld = int(ex.rows.shape[1])
+        out = torch.zeros(nq + 1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(L.convdr_excl_count_ragged(ptr(lims), ptr(I), total, nq, ptr(ex.rows), ld, ptr(ex.count), ptr(out[1:]),
+                                                  _lib.stream_ptr()), "convdr_excl_count_ragged")
+            lims_out = torch.cumsum(out, 0)
+            total_out = int(lims_out[-1].item())                # the one host read: it sizes the result
+            Do = torch.empty(total_out, dtype=torch.float32, device=self.device)
+            Io = torch.empty(total_out, dtype=torch.int64, device=self.device)
+            if total_out:
+                _lib.check(L.convdr_excl_pack_ragged(ptr(lims), ptr(D), ptr(I), total, nq, ptr(ex.rows), ld, ptr(ex.count), ptr(lims_out),
+                                                     ptr(Do), ptr(Io), total_out, _lib.stream_ptr()), "convdr_excl_pack_ragged")
+        self.stats.update(excluded_dropped=total - total_out, range_results=total_out)
+        return lims_out, Do, Io
 
     def _range_radius(self, radius, nq):
         import torch
@@ -825,27 +953,45 @@ class FlatIPIndex(_IndexStore):
         of its score, which are re-scored exactly.  The host loop and its fallback are ``_rank_ladder``.
         ``stats``: rank_rounds (passes), rank_cap (the longest band list used), rank_band_rows (band entries re-scored, all
         passes), rank_above (rows counted without a re-score, final passes), rank_fallback_pairs, rescaled."""
+        return self._rank_rows_tensors(q, rows, allowed, None)
+
+    def _rank_rows_tensors(self, q, rows, allowed, exclude):
+        """rank_rows_tensors, with per-query exclusions (``excluding(ex).rank_rows_tensors``) or None"""
+        import torch
         qt, rt, shape = self._rows_arg("rank_rows", q, rows)
         f = self._filter(allowed)
-        out = self._rank_ladder("convdr_ip_rank_rows", qt, rt.reshape(-1), f, lambda qs, ts, cap: self._rank_pass(qs, ts, cap, f),
-                                lambda I, ahead, t: ahead.sum())
+        ex = self._exclusions(exclude, int(qt.shape[0]))
+        tp = rt.reshape(-1).contiguous()
+        out, X = self._rank_ladder_scores("convdr_ip_rank_rows", qt, tp, f, lambda qs, ts, cap: self._rank_pass(qs, ts, cap, f),
+                                          lambda I, ahead, t: ahead.sum())
+        if ex is not None and ex.e_max and X is not None:
+            # whatever rung ranked a pair: minus the excluded allowed rows that precede its target, counted against the
+            # target's fp64 score the ladder holds on the device (a padding target keeps its -1)
+            pairq = torch.arange(int(tp.numel()), device=self.device) // int(rt.shape[1])
+            out = torch.where(out >= 0, out - self._excluded_ahead(ex, f, qt, pairq, X, tp), out)
         return out.reshape(shape)
 
     def _rank_ladder(self, who, qt, tp, f, run_pass, count_ahead, **more_stats):
+        """``_rank_ladder_scores`` without the scores"""
+        return self._rank_ladder_scores(who, qt, tp, f, run_pass, count_ahead, **more_stats)[0]
+
+    def _rank_ladder_scores(self, who, qt, tp, f, run_pass, count_ahead, **more_stats):
         """The host loop of rank_rows_tensors / rank_ids_tensors: device int64 [np], the rank of every pair (query j // m of `qt`,
         target row tp[j]).  It reads ONE tensor per pass, run_pass(queries, targets, cap) = _rank_pass / _rank_docs_pass: the first
         pass runs at ``self.cap``; a pair whose band overflowed is re-run once at the smallest power of two that holds the reported
         band count, up to RANGE_MAX_CAP; CONVDR_IP_RANGE rebuilds the scan copy once (as search_finish).  A pair whose band holds
         more than RANGE_MAX_CAP rows -- more duplicates or near-duplicates of the target than that -- takes the fallback: a
         ``range_search`` just below the target's score (which has its own row-slice rung), the canonical fp64 scores of the rows
-        I it returns, and count_ahead(I, mask of the rows that precede the target, target row).  Correct, not fast."""
+        I it returns, and count_ahead(I, mask of the rows that precede the target, target row).  Correct, not fast.
+        Returns (ranks, X): X the targets' canonical fp64 scores, device float64 [np], as the entry wrote them on whatever
+        rung (None when nothing was ranked: no pair, or an empty index)."""
         import torch
         npairs = int(tp.numel())
         self.stats = {"rank_rounds": 0, "rank_cap": 0, "rank_band_rows": 0, "rank_above": 0, "rank_fallback_pairs": 0, "rescaled": 0,
                       **more_stats}
         out = torch.full((npairs,), -1, dtype=torch.int64, device=self.device)
         if not npairs or not self.ntotal:
-            return out
+            return out, None
         qt = self._queries(qt, padded_ok=True)
         qp = qt if npairs == int(qt.shape[0]) else qt.repeat_interleave(npairs // int(qt.shape[0]), dim=0)
         tp = tp.contiguous()
@@ -878,7 +1024,7 @@ class FlatIPIndex(_IndexStore):
                 Xr = self.score_rows_tensors(qj, I[None, :])[1][0]
                 out[j] = count_ahead(I, (Xr > float(x)) | ((Xr == float(x)) & (I < t)), t)
             self.stats = stats
-        return out
+        return out, X
 
     def _rows_arg(self, who, q, rows):
         """(queries device fp32 [nq, d], rows device int64 [nq, m], the shape of `rows`); the checks that need no device"""
@@ -982,3 +1128,61 @@ class FlatIPIndex(_IndexStore):
         out = self._rank_ladder("convdr_ip_rank_docs", qt, R.reshape(-1), f, lambda qs, ts, cap: self._rank_docs_pass(qs, ts, cap, o, f),
                                 docs_ahead, ndocs=o.ndocs)
         return out.reshape(shape), D, R
+
+
+class ExcludedSearch:
+    """``FlatIPIndex.excluding(exclude)``: the exact entries of an index with rows left out PER QUERY -- the known positives of
+    each query, the passages of its earlier turns, the stored row that is the query itself -- where ``allowed=`` is one set for the
+    whole call.  Every entry has the name, the arguments and the result of the index's own and is exact and certified at every
+    depth, for both stores and every precision, alone or with ``allowed=``: the canonical order of the (allowed) rows with query
+    j's rows removed.  exclude: a QueryExclusions (reusable), or a raw int64 [nq, e] array / list of nq lists built for each call.
+    No new scan ("Per-query exclusions"): the certified search runs at ONE depth for the whole call,
+    k + e_max (the longest list; `stats["exclude_depth"]`), and the excluded rows are dropped from its lists on the device
+    (`stats["excluded_dropped"]`) -- callers whose lists are very uneven should group their queries by list length; ranks and
+    range counts subtract the excluded allowed rows that precede the threshold (the target of a rank never counts, so a query
+    may exclude its own target).  Not offered: rank_ids, the single uncertified pass, search_distinct with caller keys, the
+    block-file and sharded searches."""
+
+    def __init__(self, index, exclude):
+        self.index, self.exclude = index, exclude
+
+    def search(self, q, k, allowed=None):
+        D, I = self.search_tensors(q, k, allowed=allowed)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_tensors(self, q, k, allowed=None):
+        return self.index.search_finish(self.search_begin(q, k, allowed=allowed))
+
+    def search_begin(self, q, k, allowed=None):
+        """the handle for ``index.search_finish``: opaque, it carries the exclusions and the caller's k"""
+        return self.index._search_begin_excluded(q, k, allowed, self.exclude)
+
+    def search_ids(self, q, k, allowed=None):
+        D, I = self.search_ids_tensors(q, k, allowed=allowed)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_ids_tensors(self, q, k, allowed=None):
+        self.index._need_ids("search_ids")
+        return self.index._ids_of(*self.search_tensors(q, k, allowed=allowed))
+
+    def search_docs(self, q, k, allowed=None, depth=None, strict=True, max_depth=None):
+        """the exclusion is applied to the row lists before the distinct cut: a document whose rows are all excluded
+        disappears for that query, one with some rows excluded is represented by its best remaining row"""
+        return self.index._search_docs(q, k, allowed, depth, strict, max_depth, self.exclude)
+
+    def range_search(self, q, radius, allowed=None):
+        lims, D, I = self.range_search_tensors(q, radius, allowed=allowed)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    def range_search_tensors(self, q, radius, allowed=None):
+        return self.index._range_excluded(q, radius, allowed, False, self.exclude)
+
+    def range_count(self, q, radius, allowed=None):
+        return self.index._range_excluded(q, radius, allowed, True, self.exclude)
+
+    def rank_rows(self, q, rows, allowed=None):
+        """``search(q, k)[1][j, rank] == row`` of this view whenever rank < k and the row is not excluded itself"""
+        return self.rank_rows_tensors(q, rows, allowed=allowed).cpu().numpy()
+
+    def rank_rows_tensors(self, q, rows, allowed=None):
+        return self.index._rank_rows_tensors(q, rows, allowed, self.exclude)

@@ -472,6 +472,62 @@ int convdr_ip_rank_docs(int store, const float* q_f32, int np, const int64_t* ta
                         size_t workspace_bytes, int64_t* rank, double* X, int64_t* counts, int64_t* above, int32_t* status,
                         convdr_stream_t stream);
 
+/* Per-query exclusions: every query of a call leaves out ITS OWN rows (its known positives, the passages of its earlier turns,
+ * itself).  Nothing here scans: the exclusion is applied to certified results.  With A the allowed rows (all rows without a
+ * bitmap) and E_q the excluded rows of query q, the canonical order of A \ E_q is the canonical order of A with E_q removed, so
+ *   top-k        = the first k entries of the certified top-(k + |E_q|) of A whose row is not in E_q        (the drop)
+ *   rank(q, t)   = rank_A(q, t) - #{x in E_q and A : X_x > X_t, or X_x == X_t and x < t}                     (the count ahead)
+ *   range count  = count_A(q) - #{x in E_q and A : X_x > (double)radius_q}               (the count ahead with row_thr = -1)
+ * the operand    ex_rows (u32 [nq, ex_ld]) and ex_count (int32 [nq]): row q holds the query's excluded rows ASCENDING and DISTINCT
+ *                in its first ex_count[q] words, then 0xffffffff.  ex_ld is a multiple of 4, 4 <= ex_ld <= 16,384.  Membership is
+ *                a binary search in the row (at most 15 steps).  A count outside [0, ex_ld] is clamped into it.
+ * convdr_excl_build_rows   rows (int64 [nq, e], pitch ld >= e; any order, repeats allowed, negative = padding), e <= 16,384 and
+ *                ex_ld >= e.  One workgroup per query: the entries go to LDS, a bitonic network sorts them (the next power of
+ *                two >= max(e, 64) words), the first of every run of equal rows is written.  *status (device int32, zeroed on the
+ *                stream inside the call) gets bit 0 when a row >= n was met (it is left out).
+ * convdr_excl_build_docs   the same from the CSR of convdr_keys_rows_count / convdr_keys_rows_fill: query q excludes every row of its
+ *                m segments (start, count)[q, 0 .. m) (pitch ld >= m, m <= 16,384) of csr_rows[0 : rows_len]; a segment that does not
+ *                lie inside the list, or is empty, excludes nothing.  The sort always runs over 16,384 words.  Bit 1 of *status:
+ *                a query's segments hold more than 16,384 entries (repeats counted): its row is then incomplete.  A query's
+ *                distinct rows beyond ex_ld are not written and ex_count is clamped to ex_ld: size ex_ld to min(16,384, rows_len)
+ *                rounded up to a multiple of 4 and that cannot happen.
+ * convdr_excl_drop_topk    (D, I) [nq, m], pitch ld >= m: a canonical list, padding I = -1 (at the tail; anywhere, it is skipped).
+ *                (D_out, I_out) [nq, k], contiguous: the first k entries whose row is not in the query's canonical row, in order,
+ *                then (-3.4028235e38, -1); kept[q] (int32) = the survivors BEFORE the cut.  Out of place: the outputs must not
+ *                overlap the inputs.  One workgroup per query walks the list in 256-entry chunks: a ballot per wave and a running
+ *                base give every survivor its place.  1 <= m <= 2^30 (the searches produce up to 131,072), 1 <= k <= 2^30.
+ * convdr_excl_count_ragged / convdr_excl_pack_ragged   the same over a ragged result: query q owns I[lims[q] : lims[q + 1]] (lims
+ *                int64 [nq + 1], clamped to [0, total]).  count: kept[q] (int64) = the entries whose row is not excluded.  pack:
+ *                those entries, in order, to [lims_out[q] : lims_out[q + 1]] of (D_out, I_out) [total_out] -- never past the run's
+ *                end nor past total_out.  lims_out is the exclusive scan of kept, which the caller makes (total_out <= total).
+ * convdr_ip_excl_count_ahead   per pair p < np of query pairq[p] (int32; outside [0, nq): ahead = 0) with the threshold (x_thr[p]
+ *                fp64, row_thr[p] int64): ahead[p] (int64) = #{x in the query's canonical row : x < n, x allowed, X_x > x_thr or
+ *                (X_x == x_thr and x < row_thr)}.  X_x is the value convdr_ip_score_rows gives for (query, x), bit for bit (one
+ *                device function serves both).  Allowed: row_bits (NULL, 0: every row), the bitmap of convdr_ip_search_filtered
+ *                under that entry's contract (16-byte aligned, whole 256-row tiles).  A rank passes (X_t, t): t itself never
+ *                counts.  A range count passes ((double)radius, -1).  One wave per (pair, slice of the list); ahead is zeroed on
+ *                the stream inside the call and summed with integer atomic adds.  store / p_f32 / p_half / p_scale as for
+ *                convdr_ip_score_rows; nq, np >= 0, 0 <= n < 2^31, d % 64 == 0, d <= 4096.
+ * Plain C++ and vector stores only; every loop is bounded by an argument; no workgroup waits for another.  Arguments are validated
+ * before anything touches a device: a refusal is a negative code and a convdr_last_error message that names the entry; no
+ * allocation, no sync. */
+int convdr_excl_build_rows(const int64_t* rows, int nq, int e, int64_t ld, int64_t n, uint32_t* ex_rows, int64_t ex_ld,
+                           int32_t* ex_count, int32_t* status, convdr_stream_t stream);
+int convdr_excl_build_docs(const int64_t* csr_rows, int64_t rows_len, const int64_t* start, const int32_t* count, int nq, int m,
+                           int64_t ld, int64_t n, uint32_t* ex_rows, int64_t ex_ld, int32_t* ex_count, int32_t* status,
+                           convdr_stream_t stream);
+int convdr_excl_drop_topk(const float* D, const int64_t* I, int nq, int m, int64_t ld, const uint32_t* ex_rows, int64_t ex_ld,
+                          const int32_t* ex_count, int k, float* D_out, int64_t* I_out, int32_t* kept, convdr_stream_t stream);
+int convdr_excl_count_ragged(const int64_t* lims, const int64_t* I, int64_t total, int nq, const uint32_t* ex_rows, int64_t ex_ld,
+                             const int32_t* ex_count, int64_t* kept, convdr_stream_t stream);
+int convdr_excl_pack_ragged(const int64_t* lims, const float* D, const int64_t* I, int64_t total, int nq, const uint32_t* ex_rows,
+                            int64_t ex_ld, const int32_t* ex_count, const int64_t* lims_out, float* D_out, int64_t* I_out,
+                            int64_t total_out, convdr_stream_t stream);
+int convdr_ip_excl_count_ahead(int store, const float* q_f32, int nq, const float* p_f32, const void* p_half, float p_scale,
+                               int64_t n, int d, const uint32_t* row_bits, int64_t row_bits_words, const uint32_t* ex_rows,
+                               int64_t ex_ld, const int32_t* ex_count, int np, const int32_t* pairq, const double* x_thr,
+                               const int64_t* row_thr, int64_t* ahead, convdr_stream_t stream);
+
 /* Digest and snapshot file: a resident index (rows in their compacted order, id column, centre, scale, max norm) written to ONE
  * file and read back (FAISS: write_index / read_index), every byte covered by a digest that is checked where the bytes land.
  *   the digest   a buffer is m little-endian 64-bit words w[0 .. m) with a starting word index word0.  With g_i = word0 + i + 1,
