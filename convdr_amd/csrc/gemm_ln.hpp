@@ -373,4 +373,355 @@ __global__ void __launch_bounds__(512, 2) k_gemm_resid_ln(const GemmLnArgs a) {
   CONVDR_LN_TRACE(7)
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The same kernel on v_mfma_f32_16x16x32_bf16 (k_gemm_resid_ln_m16; convdr_set_option("ln_mfma16")).  Why: these GEMMs run
+// power-capped and the chip holds a higher clock on this shape (gemm_nt.hpp, gemm_nt_mainloop_r3_m16;
+// tools/proto/ln_mfma16_proto.hip, profiles/ln_mfma16_proto.txt for this kernel's staging).  Staging, slots, roles, waits and
+// the 96 KB epilogue image are k_gemm_resid_ln's; what differs:
+//   * one 32-wide slice is ONE sub-step: 12 weight fragments x 4 activation fragments = 48 MFMAs per wave, the wave tile
+//     192 features x 64 tokens held as 12 x 4 blocks of 16 x 16 (GemmAcc16<TileLN>, 192 accumulators);
+//   * an operand fragment is row (lane & 15), 16-byte chunk (lane >> 4) of the 64-byte LDS row.  Under the 32-row kernel's
+//     swizzle chunk ^ ((row >> 2) & 3) that read is 2-way bank-conflicted in each of the four ds_read_b128 lane groups;
+//     this kernel stages with chunk ^ ln16_swz(row), conflict-free for it (static_assert below);
+//   * the epilogue is re-indexed for the 16 x 16 accumulator layout, its arithmetic kept; a token's row statistics come in
+//     16 partial sums (4 feature waves x 4 lane quarters) instead of 8, so the image starts 4 KB later.
+constexpr int ln16_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }
+
+// the four 16-lane groups one ds_read_b128 is served in: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, and both + 32
+constexpr bool ln16_frag_read_conflict_free() {
+  for (int g = 0; g < 4; ++g) {
+    unsigned seen = 0;
+    for (int l = 0; l < 64; ++l) {
+      const int m = l & 31;
+      const bool first = m < 4 || (m >= 12 && m < 16) || (m >= 20 && m < 28);
+      if ((l >> 5) != (g >> 1) || first != ((g & 1) == 0)) continue;
+      const int row = l & 15, q = l >> 4;
+      const int slot = ((row * 64 + ((q ^ ln16_swz(row)) << 4)) >> 4) & 15;   // 16-byte slot of the 256 B the 64 banks span
+      if ((seen >> slot) & 1u) return false;
+      seen |= 1u << slot;
+    }
+    if (seen != 0xffffu) return false;
+  }
+  return true;
+}
+static_assert(ln16_frag_read_conflict_free(), "16-row fragment read: 16 distinct 16-byte slots in every ds_read_b128 lane group");
+static_assert(ln16_swz(0) == ln16_swz(16) && ln16_swz(5) == ln16_swz(5 + 16 * LN_W_WAVES), "the swizzle term is round-independent");
+
+constexpr int LN16_RED_SLOTS = 16;                       // partial row sums per token: wr * 4 + (lane >> 4)
+constexpr int LN16_IMG_OFF = 20480;                      // 9 KB parameters + 8 KB partials + 1 KB statistics, then the image
+static_assert((3 * 768 + 128 * LN16_RED_SLOTS + 256) * 4 <= LN16_IMG_OFF && LN16_IMG_OFF + 64 * 1536 <= LN_SMEM_BYTES, "epilogue LDS");
+
+struct Ln16Src {
+  StageSrc W, A;
+  uint32_t w_slice_stride, a_slice_stride;
+};
+
+// the operand windows of k_gemm_resid_ln with the source chunk swizzled by ln16_swz
+__device__ __forceinline__ Ln16Src ln16_sources(const GemmLnArgs& a, int64_t t0, const WavePos<TileLN>& w) {
+  using T = TileLN;
+  Ln16Src s;
+  s.W = a.Wks ? ln_stage_src<LN_W_WAVES, LN_W_FIRST>(a.Wks, LN_SLICE, 0, (int64_t)T::TR * (a.K / LN_SLICE), w.wave, w.lane)
+              : ln_stage_src<LN_W_WAVES, LN_W_FIRST>(a.W, a.K, 0, T::TR, w.wave, w.lane);
+  s.w_slice_stride = a.Wks ? T::TR * LN_SLICE * 2 : LN_SLICE * 2;
+  s.A = ln_stage_src<LN_A_WAVES, LN_A_FIRST>(a.A, a.K, t0, a.rows, w.wave, w.lane);
+  s.a_slice_stride = LN_SLICE * 2;
+  {
+    const int wv = w.wave >= LN_W_FIRST ? w.wave - LN_W_FIRST : 0;
+    const int row = wv * 16 + (w.lane >> 2);
+    const int gch = (w.lane & 3) ^ ln16_swz(row);
+    s.W.voff = (uint32_t)(row * (a.Wks ? LN_SLICE : a.K) * 2) + gch * 16;
+  }
+  const int wv = w.wave >= LN_A_FIRST ? w.wave - LN_A_FIRST : 0;
+  const int row = wv * 16 + (w.lane >> 2);                          // token inside a round of 16 x LN_A_WAVES tokens
+  const int gch = (w.lane & 3) ^ ln16_swz(row);                     // source chunk of the slice for LDS chunk (lane & 3)
+  s.A.voff = (uint32_t)(row * a.K * 2) + gch * 16;
+  if (a.a_blocked) {   // (window and pitch as in k_gemm_resid_ln)
+    const int64_t rows32 = (a.rows + 31) & ~(int64_t)31;
+    const int64_t blk_elems = (int64_t)(a.K >> 3) * 256;
+    int64_t bytes = (rows32 - t0) / 32 * blk_elems * 2;
+    bytes = bytes < 0 ? 0 : (bytes > 0xffffffffll ? 0xffffffffll : bytes);
+    const uint64_t base = (uint64_t)(a.A + (t0 >> 5) * blk_elems);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)base);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32));
+    const uint32_t nb = __builtin_amdgcn_readfirstlane((uint32_t)bytes);
+    s.A.rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), 0, nb, 0x00020000);
+    s.A.voff = (uint32_t)((row >> 5) * blk_elems * 2 + gch * 512 + (row & 31) * 16);
+    s.A.round_pitch = __builtin_amdgcn_readfirstlane((uint32_t)((16 * LN_A_WAVES / 32) * blk_elems * 2));
+    s.a_slice_stride = 4 * 512;
+  }
+  return s;
+}
+
+// Main loop: k_gemm_resid_ln's step (waits, barrier, A(t + 1) at the top, W(t + 2) behind the MFMAs) around one sub-step.
+// The blocks are walked feature-major: unit u = weight fragment u and its 4 MFMAs.  Registers as in the 32x32x16 loop:
+// 4 activation fragments + three rotating weight fragments (28 VGPRs), the fragment of unit u + 2 read before the MFMAs of
+// unit u -- one ds_read_b128 per 64 MFMA cycles.
+// ORDER 0: the first MFMA waits for 6 reads (4 activation, 2 weight).  ORDER 1 / 2: units 0 and 1 run on token blocks 0-1
+// first, then on blocks 2-3; 1 still reads all six fragments ahead of the first MFMA, 2 reads the fragments of blocks 2-3
+// behind the first two MFMAs, so the first MFMA waits for 4 reads.
+template <int ORDER>
+__device__ __forceinline__ void ln_mainloop_m16(const Ln16Src& s, int nk, char* smem, GemmAcc16<TileLN>& acc,
+                                                const WavePos<TileLN>& w) {
+  using T = TileLN;
+  constexpr int MB = GemmAcc16<T>::MB, NB = GemmAcc16<T>::NB;
+  static_assert(MB == 12 && NB == 4, "TileLN: 12 x 4 blocks per wave");
+  char* sW = smem;
+  char* sA = smem + 3 * LN_R_BYTES;
+  const int r16 = w.lane & 15;
+  const int ch = ((w.lane >> 4) ^ ln16_swz(r16)) * 16;
+  const int offR = (w.wr * T::MT * 32 + r16) * 64 + ch;
+  const int offL = (w.wl * T::NT * 32 + r16) * 64 + ch;
+  constexpr int LN_W_DPW = T::TR / (16 * LN_W_WAVES);
+  const bool w_wave = w.wave >= LN_W_FIRST && w.wave < LN_W_FIRST + LN_W_WAVES;
+  ln_stage32<T::TR, LN_W_WAVES, LN_W_FIRST>(s.W, 0, sW, w.wave, s.w_slice_stride);
+  ln_stage32<T::TL, LN_A_WAVES, LN_A_FIRST, LN_A_AUX>(s.A, 0, sA, w.wave, s.a_slice_stride);
+  if (nk > 1) ln_stage32<T::TR, LN_W_WAVES, LN_W_FIRST>(s.W, 1, sW + LN_R_BYTES, w.wave, s.w_slice_stride);
+  int wslot = 0;   // kt % 3
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk && w_wave) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LN_W_DPW) : "memory");
+    else lds_dma_wait_all();
+    lds_barrier();
+    if (kt + 1 < nk) ln_stage32<T::TL, LN_A_WAVES, LN_A_FIRST, LN_A_AUX>(s.A, kt + 1, sA + ((kt + 1) & 1) * LN_L_BYTES, w.wave, s.a_slice_stride);
+    const bool issue_w = kt + 2 < nk;
+    char* w_dst = sW + (wslot == 0 ? 2 : wslot - 1) * LN_R_BYTES;   // slot (kt + 2) % 3
+    const char* tR = sW + wslot * LN_R_BYTES + offR;
+    const char* tL = sA + (kt & 1) * LN_L_BYTES + offL;
+    wslot = wslot == 2 ? 0 : wslot + 1;
+    {
+      bf16x8 fb[NB], fa[3];
+      auto load_a = [&](int u) { fa[u % 3] = *(const bf16x8*)(tR + u * 16 * 64); };
+      auto load_b = [&](int j) { fb[j] = *(const bf16x8*)(tL + j * 16 * 64); };
+      auto mm = [&](int u, int j) { acc.c[u][j] = mfma_16x16x32<false>(fa[u % 3], fb[j], acc.c[u][j]); };
+      if constexpr (ORDER == 0) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) load_b(j);
+        load_a(0);
+        load_a(1);
+#pragma unroll
+        for (int u = 0; u < MB; ++u) {
+          if (u + 2 < MB) load_a(u + 2);
+#pragma unroll
+          for (int j = 0; j < NB; ++j) mm(u, j);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, NB + 2, 0);                   // fb, fa(0), fa(1)
+#pragma unroll
+        for (int u = 0; u < MB; ++u) {
+          if (u + 2 < MB) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // fa(u + 2)
+          __builtin_amdgcn_sched_group_barrier(0x008, NB, 0);                     // the unit's 4 MFMAs
+        }
+      } else {
+        load_b(0); load_b(1);
+        load_a(0); load_a(1);
+        if constexpr (ORDER == 1) { load_b(2); load_b(3); }
+        mm(0, 0); mm(0, 1);
+        if constexpr (ORDER == 2) { load_b(2); load_b(3); }
+        mm(1, 0); mm(1, 1);
+        load_a(2);
+        mm(0, 2); mm(0, 3);
+        load_a(3);
+        mm(1, 2); mm(1, 3);
+#pragma unroll
+        for (int u = 2; u < MB; ++u) {
+          if (u + 2 < MB) load_a(u + 2);
+#pragma unroll
+          for (int j = 0; j < NB; ++j) mm(u, j);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                        // fb(0), fb(1), fa(0), fa(1)
+        if constexpr (ORDER == 1) {
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                      // fb(2), fb(3)
+          __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        } else {
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                      // fb(2), fb(3) behind the first two MFMAs
+          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        // fa(2)
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                        // fa(3)
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+#pragma unroll
+        for (int u = 2; u < MB; ++u) {
+          if (u + 2 < MB) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x008, NB, 0);
+        }
+      }
+    }
+    if (issue_w) ln_stage32<T::TR, LN_W_WAVES, LN_W_FIRST>(s.W, kt + 2, w_dst, w.wave, s.w_slice_stride);
+  }
+}
+// profiles/ln_mfma16_proto.txt, wall per K step at K = 3,072: 1.319 us on 32x32x16; 1.239 (ORDER 0), 1.223 (1), 1.226 (2) here
+constexpr int LN16_ORDER = 1;
+
+// Epilogue: k_gemm_resid_ln's, phase by phase, for the 16 x 16 blocks.  With q = lane >> 4, t = lane & 15, block (i, j)
+// register r is feature wr * 192 + 16 i + 4 q + r of token wl * 64 + 16 j + t.  Image half h holds token blocks 2h, 2h + 1
+// (the same tokens as the 32-row kernel's half h); a token's image row is lrl = wl * 32 + 16 (j & 1) + t, the lane's 8 bytes
+// are half (q & 1) of feature chunk wr * 24 + 2 i + (q >> 1).  wr * 24 + 2 i is even, so the (q >> 1) is one XOR into the
+// per-row base and the per-access address stays the one v_xor of img_at.
+__global__ void __launch_bounds__(512, 2) k_gemm_resid_ln_m16(const GemmLnArgs a) {
+  using T = TileLN;
+  constexpr int MB = GemmAcc16<T>::MB, NB = GemmAcc16<T>::NB;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const WavePos<T> w;
+  const int64_t t0 = (int64_t)blockIdx.x * T::TL;
+  GemmAcc16<T> acc;
+  acc.zero();
+  CONVDR_LN_TRACE(0)
+  {
+    const Ln16Src src = ln16_sources(a, t0, w);
+    ln_mainloop_m16<LN16_ORDER>(src, a.K / LN_SLICE, smem, acc, w);
+  }
+  if (a.dbg_skip_epi) {   // (keeps the accumulators alive; never true in the product)
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s += acc.c[i][j][r];
+    if (s == 12345.678f) a.X[0] = f32_to_bf16(s);
+    return;
+  }
+  CONVDR_LN_TRACE(1)
+  __syncthreads();   // operand buffers are dead
+  float* sBias = (float*)smem;           // [768]
+  float* sGam = sBias + 768;
+  float* sBet = sGam + 768;
+  float* sRed = sBet + 768;              // [128 tokens][16 partial slots]
+  float* sStat = sRed + 128 * LN16_RED_SLOTS;   // [128] mean, [128] rstd
+  char* sC = smem + LN16_IMG_OFF;        // [64][1536 B] residual / output image
+  const int q = w.lane >> 4, t16 = w.lane & 15;
+  const int slot = w.wr * 4 + q;
+  const int f0 = w.wr * T::MT * 32 + 4 * q;   // block i: features f0 + 16 i ... + 3
+  const StageSrc srcR = ln_stage_src(a.R, 768, t0, a.rows, w.wave, w.lane);   // (only .rsrc is used)
+  const __amdgpu_buffer_rsrc_t dstX = ln_stage_src(a.X, 768, t0, a.rows, w.wave, w.lane).rsrc;   // output window [t0, rows)
+  typedef __attribute__((address_space(3))) u32x2_t lds_u2_t;
+  static_assert((LN16_IMG_OFF & 511) == 0, "the image base must leave bits 4-8 to the swizzle");
+  // base of image row lrl for this lane: row, row swizzle, the odd feature chunk of the lane's pair, the 8-byte half
+  auto img_base = [&](int lrl) {
+    return (lds_off(sC) + (uint32_t)(lrl * 1536 + ((lrl & 31) << 4) + (q & 1) * 8)) ^ (uint32_t)((q >> 1) << 4);
+  };
+  auto img_at = [&](uint32_t B, int chunk) {   // chunk even
+    return (lds_u2_t*)(uintptr_t)((B ^ (uint32_t)((chunk & 31) << 4)) + (uint32_t)((chunk & ~31) << 4));
+  };
+  auto opaque = [](int x) {
+    asm volatile("" : "+v"(x));
+    return x;
+  };
+  CONVDR_LN_TRACE(2)
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (h) __syncthreads();   // every lane has consumed the previous half
+    const int tid_a = opaque((int)threadIdx.x);
+    int lr = tid_a / 96, pp = tid_a - lr * 96;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      const int c = (pp & ~31) | ((pp ^ lr) & 31);
+      const int tok = (lr >> 5) * 64 + h * 32 + (lr & 31);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(srcR.rsrc, (lptr_t)(sC + (i * 512 + w.wave * 64) * 16), 16,
+                                               (uint32_t)(tok * 1536 + c * 16), 0, 0, 0);
+      pp += 32; lr += 5;
+      if (pp >= 96) { pp -= 96; lr += 1; }
+    }
+    if (h == 0) {
+      for (int i = threadIdx.x; i < 768; i += 512) { sBias[i] = a.bias[i]; sGam[i] = a.gamma[i]; sBet[i] = a.beta[i]; }
+    }
+    lds_dma_wait_all();
+    __syncthreads();           // (first half: also publishes the LayerNorm parameters)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = 2 * h + jj;
+      float s = 0.f;
+      const uint32_t imgB = img_base(opaque(w.wl * 32 + 16 * jj + t16));
+#pragma unroll
+      for (int i0 = 0; i0 < MB; i0 += 4) {
+        u32x2_t res[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) res[g] = *img_at(imgB, w.wr * 24 + 2 * (i0 + g));
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4& v = acc.c[i0 + g][j];
+          const float4 bv = *(const float4*)(sBias + f0 + 16 * (i0 + g));
+          const u32x2_t r = res[g];
+          v[0] += bv.x + __uint_as_float(r.x << 16);
+          v[1] += bv.y + __uint_as_float(r.x & 0xffff0000u);
+          v[2] += bv.z + __uint_as_float(r.y << 16);
+          v[3] += bv.w + __uint_as_float(r.y & 0xffff0000u);
+          s += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+      }
+      sRed[(w.wl * 64 + 16 * j + t16) * LN16_RED_SLOTS + slot] = s;
+    }
+  }
+  CONVDR_LN_TRACE(3)
+  __syncthreads();
+  CONVDR_LN_TRACE(4)
+  auto sum16 = [](const float* p) {
+    return ((((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]))) +
+            (((p[8] + p[9]) + (p[10] + p[11])) + ((p[12] + p[13]) + (p[14] + p[15]))));
+  };
+  if (threadIdx.x < 128) sStat[threadIdx.x] = sum16(sRed + threadIdx.x * LN16_RED_SLOTS) * (1.f / 768.f);
+  __syncthreads();
+  float mean[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    mean[j] = sStat[w.wl * 64 + 16 * j + t16];
+    float qs = 0.f;
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float d = acc.c[i][j][r] - mean[j];
+        qs += d * d;
+      }
+    sRed[(w.wl * 64 + 16 * j + t16) * LN16_RED_SLOTS + slot] = qs;
+  }
+  CONVDR_LN_TRACE(5)
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const float var = sum16(sRed + threadIdx.x * LN16_RED_SLOTS) * (1.f / 768.f);
+    sStat[128 + threadIdx.x] = rsqrtf(var + a.eps);
+  }
+  __syncthreads();
+  CONVDR_LN_TRACE(6)
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (h) __syncthreads();   // the previous half has been read out
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = 2 * h + jj;
+      const float rstd = sStat[128 + w.wl * 64 + 16 * j + t16];
+      const uint32_t imgB = img_base(opaque(w.wl * 32 + 16 * jj + t16));
+#pragma unroll
+      for (int i = 0; i < MB; ++i) {
+        const int f = f0 + 16 * i;
+        const float4 gg = *(const float4*)(sGam + f), bb = *(const float4*)(sBet + f);
+        const f32x4& v = acc.c[i][j];
+        u32x2_t o;
+        o.x = pack_bf16x2((v[0] - mean[j]) * rstd * gg.x + bb.x, (v[1] - mean[j]) * rstd * gg.y + bb.y);
+        o.y = pack_bf16x2((v[2] - mean[j]) * rstd * gg.z + bb.z, (v[3] - mean[j]) * rstd * gg.w + bb.w);
+        *img_at(imgB, w.wr * 24 + 2 * i) = o;
+      }
+    }
+    __syncthreads();
+    const int tid_s = opaque((int)threadIdx.x);
+    int lr = tid_s / 96, pp = tid_s - lr * 96;
+#pragma unroll
+    for (int i0 = 0; i0 < 12; i0 += 4) {
+      u32x4_t v4[4];
+#pragma unroll
+      for (int jv = 0; jv < 4; ++jv) v4[jv] = *(const u32x4_t*)(sC + ((i0 + jv) * 512 + tid_s) * 16);
+#pragma unroll
+      for (int jv = 0; jv < 4; ++jv) {
+        const int c = (pp & ~31) | ((pp ^ lr) & 31);
+        const int tok = (lr >> 5) * 64 + h * 32 + (lr & 31);
+        // through the output window [t0, rows): rows past the end are dropped by the bounds check; one 32-bit offset
+        __builtin_amdgcn_raw_buffer_store_b128(v4[jv], dstX, (uint32_t)(tok * 1536 + c * 16), 0, NT_LN ? 2 : 0);
+        pp += 32; lr += 5;
+        if (pp >= 96) { pp -= 96; lr += 1; }
+      }
+    }
+  }
+  CONVDR_LN_TRACE(7)
+}
+
 }  // namespace convdr

@@ -7,7 +7,7 @@ def funcs(path, ren):
     d={}
     for m in re.finditer(r'^(_Z\w+):.*?\n(.*?)^\.Lfunc_end\d+:', s, re.S|re.M):
         body=re.sub(r'\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?','.L',m.group(2))
-        body=re.sub(r';.*','',body)
+        body=re.sub(r'[ \t]*;.*','',body)   # (and the padding in front of a comment: it follows the label's width)
         d[m.group(1)]=body
     return d
 ren=[('k_attention_fwdILb0ELb0ELb0ELb0EE','k_attention_fwdILb0ELb0ELb0EE'),('k_attention_fwdILb0ELb0ELb1ELb1EE','k_attention_fwdILb0ELb1ELb1EE'),
