@@ -15,6 +15,8 @@ u = 2^-8 is bf16's unit roundoff; e24 = 2^-24 fp32's.
   E      Y (fp32 pre-LN sums)      X_l           u |ref| + (1 + u) e32                                   derived (ln_fp32_err)
   F      X_{l-1}                   out [B, H]    c rms(ref row), c <= 4 c_ref                            measured, as D; c_ref = the larger
                                                  of the pair on the CLS rows and the pair on all rows of the all-token layer
+  G      cls_b (the pooled row)    head_y        (K + 1) e24 (|x| |W|^T + |b|)  (fp32 sums, not rounded)   derived (head_ratios)
+         head_y                    out [B, E]    ln_fp32_err of the given head_y  (fp32 output)          derived
   -      X_l                       pooled mean   (len + 2) e24 mean|x|                                   derived (k_masked_mean)
 
 Stage B holds only if Q is stored UNSCALED (the EPI_QKV epilogue adds the bias and rounds; AttnArgs carries 0.125), stage C
@@ -281,6 +283,46 @@ def cls_chain(W, l, xprev, lens, fold, acc=F64):
     return tail_chain(W, l, ctx, xc, acc=acc)[2]
 
 
+# ---- stage G: the head, LayerNorm(Linear(H, E)(pooled row)) -----------------------------------------------------------------
+class HeadWeights:
+    """fp64 copies of what packed(head) hands the head kernels: the Linear's weight rounded to bf16, the rest fp32."""
+
+    def __init__(self, lin_mod, ln_mod):
+        d = lambda p: p.detach().cpu().float().to(F64)
+        self.w, self.b, self.g, self.beta = bf16r(d(lin_mod.weight)), d(lin_mod.bias), d(ln_mod.weight), d(ln_mod.bias)
+        self.eps = float(np.float32(ln_mod.eps))
+
+
+def head_ratios(HW, cls_b, head_y, out):
+    """-> (ratio of head_y, ratio of out), both against derived bounds, teacher-forced:
+      head_y  against cls_b W^T + b in fp64 within (K + 1) e24 (|x| |W|^T + |b|): launch_gemm<EPI_F32> stores the fp32 sum of
+              K + 1 terms unrounded -- the `acc` term of proj_ref;
+      out     against the exact LayerNorm of the GIVEN head_y within ln_fp32_err (k_layernorm with H = E, fp32 output)."""
+    y = cls_b @ HW.w.T + HW.b
+    acc = (cls_b.shape[1] + 1) * E24 * (cls_b.abs() @ HW.w.abs().T + HW.b.abs())
+    rY = float(((head_y - y).abs() / acc).max())
+    ref, e32 = ln(head_y, HW.g, HW.beta, HW.eps), ln_fp32_err(head_y, HW.g, HW.beta, HW.eps)
+    return rY, float(((out - ref).abs() / e32).max())
+
+
+def head_sim(HW, cls_b):
+    """The stand-in head: fp32 accumulation, fp32 LayerNorm -> (head_y, out)."""
+    y = lin(cls_b, HW.w, HW.b, F32)
+    return y, ln(y, HW.g, HW.beta, HW.eps, F32)
+
+
+def make_head(H, E, seed=17):
+    """Linear(H, E) + LayerNorm(E) with init statistics: N(0, 0.02) weight and bias, gain 1 + N(0, 0.05), bias N(0, 0.02)."""
+    g = torch.Generator().manual_seed(seed + E)
+    lin_mod, ln_mod = torch.nn.Linear(H, E), torch.nn.LayerNorm(E)
+    with torch.no_grad():
+        lin_mod.weight.copy_(torch.randn(E, H, generator=g) * 0.02)
+        lin_mod.bias.copy_(torch.randn(E, generator=g) * 0.02)
+        ln_mod.weight.add_(torch.randn(E, generator=g) * 0.05)
+        ln_mod.bias.copy_(torch.randn(E, generator=g) * 0.02)
+    return lin_mod, ln_mod
+
+
 # ---- workspace decoders ----------------------------------------------------------------------------------------------
 def blocked_index(rows, N):
     """Element offsets of a [rows, N] matrix in the blocked layout (csrc/encoder_kernels.hpp:hm_blocked_offset)."""
@@ -370,12 +412,14 @@ def make_inputs(lens, vocab, seed, pads=()):
     return ids, lens
 
 
-def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False):
+def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False, head=None):
     """The library's forward cut off after `l` layers, called as EncoderTower.embed does but on a copy of the packed config
     with layers = l, out_dim = 0 and pool_mean = 1 (every layer a full all-token layer; cls=True: pool_mean = 0, the last
     layer's CLS tail) and on a workspace of the library's own size pre-filled with 0xFF (every bf16 / fp32 a NaN).
     -> dict of fp64 CPU tensors for the LIVE rows only: tok_id, tok_pos, X, Q, K, V, ctx, Hm, (Y), out; 'X_bits' = the raw
-    bf16 bits of X.  After l layers Q .. Hm (Y) are layer l's intermediates and X = X_l."""
+    bf16 bits of X.  After l layers Q .. Hm (Y) are layer l's intermediates and X = X_l.
+    head = (Linear, LayerNorm): packed with that head and out_dim kept, so the run ends in the head GEMM + LayerNorm; then
+    also 'cls_b' [B, H] (the pooled row the head consumed, bf16) and 'head_y' [B, out_dim] (its fp32 sums), out [B, out_dim]."""
     from convdr_amd import _lib
     L_ = _lib.lib()
     dev = torch.device("cuda")
@@ -386,10 +430,10 @@ def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False):
     rows, max_len = int(cu[-1]), int(lens.max())
     live = torch.from_numpy(np.concatenate([cu[b] + np.arange(lens[b]) for b in range(B)]).astype(np.int64))
     with torch.cuda.device(dev):
-        c0, w, keep = tower.packed(None)
+        c0, w, keep = tower.packed(head)
         if not kslice and w.layers[0].w2_ks:      # an earlier run built the K-slice-major copies: pack afresh without them
             tower.invalidate_packed()
-            c0, w, keep = tower.packed(None)
+            c0, w, keep = tower.packed(head)
         if kslice:
             from convdr_amd.model import models as MM
             assert MM.KSLICE_MIN_ROWS <= rows, "run under options(kslice=True)"
@@ -397,11 +441,15 @@ def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False):
             assert w.layers[0].w2_ks
         c = _lib.EncoderConfig.from_buffer_copy(c0)
         assert 0 <= l <= c0.layers
-        c.layers, c.pool_mean, c.out_dim = l, 0 if cls else 1, 0
+        c.layers, c.pool_mean = l, 0 if cls else 1
+        if head is None:
+            c.out_dim = 0
+        else:
+            assert c.out_dim == head[0].out_features and l >= 1
         H, I = c.hidden, c.intermediate
         need = L_.convdr_encoder_workspace_bytes(C.byref(c), rows, B)
         ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=dev)
-        out = torch.full((B, H), float("nan"), dtype=torch.float32, device=dev)
+        out = torch.full((B, c.out_dim or H), float("nan"), dtype=torch.float32, device=dev)
         cu_d, lens_d = torch.from_numpy(cu).to(dev), torch.from_numpy(lens).to(dev)
         if ragged:
             tok = torch.from_numpy(np.concatenate([ids[b, :lens[b]] for b in range(B)]).astype(np.int32)).to(dev)
@@ -431,6 +479,11 @@ def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False):
         return ws[off[name]:off[name] + size].view(dtype).cpu()
     lo = layouts(rows, H, I)
     r = {"rows": rows, "live": live, "layout": lo, "out": out.cpu().to(F64)}
+    if head is not None:
+        for name, slot, dtype, n in (("cls_b", 9, torch.bfloat16, H), ("head_y", 12, torch.float32, c.out_dim)):   # (debug_layout's order)
+            o, size = int(lay[slot]), B * n * torch.empty((), dtype=dtype).element_size()
+            assert o + size <= need
+            r[name] = ws[o:o + size].view(dtype).cpu().view(B, n).to(F64)
     r["tok_id"], r["tok_pos"] = buf("tok_id", rows, torch.int32)[live], buf("tok_pos", rows, torch.int32)[live]
     xb = decode_rowmajor(buf("X", rows * H, torch.bfloat16), rows, H)[live]
     r["X"], r["X_bits"] = xb.to(F64), xb.view(torch.int16).clone()
@@ -450,14 +503,26 @@ def run_layers(tower, ids, lens, l, cls=False, ragged=False, kslice=False):
 
 
 # ---- the models and inputs both test files use ----------------------------------------------------------------------------
+# hidden / intermediate of every model shape (heads = hidden / 64).  W and N are the two the stage files grew up with; the
+# ENVELOPE shapes are the other six hidden sizes check_config / check_train_config admit, each with an intermediate size that
+# takes a path of its own:
+#   H128   I = 64: half a feature tile, FFN2 a single K step           H640  I = 448: H % 256 != 0, 2.5 LayerNorm groups
+#   H256   I = 192: no multiple of 128; QKV thirds one 256-tile wide   H896  I = 2304: I % 256 == 0 with H % 256 != 0
+#   H512   I = 1024: thirds two tiles wide                             H1024 I = 4096: every upper limit at once
+SHAPES = dict(W=(768, 3072), N=(384, 320), H128=(128, 64), H256=(256, 192), H512=(512, 1024), H640=(640, 448),
+              H896=(896, 2304), H1024=(1024, 4096))
+ENVELOPE = ["H128", "H256", "H512", "H640", "H896", "H1024"]
+
+
 def make_model(shape, stats):
     """shape 'W': 768 / 12 heads / 3072, 'N': 384 / 6 heads / 320 (N = 1152 is no multiple of 256, I = 2.5 feature tiles, the
-    general LayerNorm); 2 layers, vocabulary 1000.  stats 'init': N(0, 0.02) + the bias and gain noise of the other parity
-    tests, 'trained': tests.helpers.trained_like_.  CPU model (rdot_nll class); its tower is `.roberta`."""
+    general LayerNorm), or one of ENVELOPE (SHAPES above); 2 layers, vocabulary 1000.  stats 'init': N(0, 0.02) + the bias and
+    gain noise of the other parity tests, 'trained': tests.helpers.trained_like_.  CPU model (rdot_nll class); its tower is
+    `.roberta`."""
     from convdr_amd.model.models import MSMarcoConfigDict, RobertaConfig
     from tests.helpers import trained_like_
-    dims = dict(W=dict(hidden_size=768, num_attention_heads=12, intermediate_size=3072),
-                N=dict(hidden_size=384, num_attention_heads=6, intermediate_size=320))[shape]
+    H, I = SHAPES[shape]
+    dims = dict(hidden_size=H, num_attention_heads=H // 64, intermediate_size=I)
     torch.manual_seed(11)
     model = MSMarcoConfigDict["rdot_nll"].model_class(RobertaConfig(vocab_size=1000, num_hidden_layers=2, **dims))
     if stats == "trained":

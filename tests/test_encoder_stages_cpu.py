@@ -2,7 +2,12 @@
   * chained from token ids they reproduce the bf16-emulating oracle (they cannot drift from it);
   * a correct stand-in kernel (the same stage with fp32 accumulation, the oracle's kernel-arithmetic attention) holds every
     derived bound (ratio < 1) and yields the floors c_ref / f_ref of the measured ones;
-  * every planted fault breaks its stage's check (ratio > 1, c above its bar, or f above its cap).
+  * every planted fault breaks its stage's check (ratio > 1, c above its bar, or f above its cap);
+  * the same for the head (stage G) at out_dim 4, 132 and 1024 on the 640- and 1024-wide models;
+  * ES.layouts(), the mirror of encoder_layer_forward's dispatch, answers "nothing blocked, Y live" for every admitted hidden size
+    off 768 at input S.
+Models: W (768 / 12 / 3072), N (384 / 6 / 320) and the six ES.ENVELOPE shapes (128 / 64, 256 / 192, 512 / 1024, 640 / 448,
+896 / 2304, 1024 / 4096), two layers each, all on input S.
 Run with -s to see the ratios and floors."""
 import numpy as np
 import pytest
@@ -63,7 +68,7 @@ def sim(shape, stats):
     return _SIMS[(shape, stats)]
 
 
-CASES = [("W", "init"), ("W", "trained"), ("N", "init")]
+CASES = [("W", "init"), ("W", "trained"), ("N", "init")] + [(sh, "init") for sh in ES.ENVELOPE]
 
 
 def test_stage_references_chain_to_the_emulating_oracle():
@@ -215,3 +220,47 @@ def test_planted_faults_break_their_stage(shape, stats):
         print("%s/%s  %-60s c %.3g (bar %.3g)  f %.3g%% (cap %.3g%%)" % ((shape, stats, name, c) + (ES.tail_bars(c_ref, f_ref)[0], 100 * f,
                                                                                                     100 * ES.tail_bars(c_ref, f_ref)[1])))
         assert _broken(c, f, c_ref, f_ref), name
+
+
+@pytest.mark.parametrize("E", [4, 132, 1024])
+@pytest.mark.parametrize("shape", ["H640", "H1024"])
+def test_head_stage_bounds_and_faults(shape, E):
+    """Stage G on the CLS rows of the stand-in's X_1: the stand-in head holds both derived bounds; head_y or out with its last 4
+    columns dropped (at E = 4: all of them) breaks the check of the value it was planted in, and only that one."""
+    s = sim(shape, "init")
+    HW = ES.HeadWeights(*ES.make_head(s.H, E))
+    cls_b = s.X1[torch.as_tensor(s.starts)]
+    y, out = ES.head_sim(HW, cls_b)
+    rY, rO = ES.head_ratios(HW, cls_b, y, out)
+    print("%s E %d: G ratios head_y %.3f  out %.3f" % (shape, E, rY, rO))
+    assert rY < 1 and rO < 1, (rY, rO)
+    m = y.clone(); m[:, -4:] = 0
+    fY, fO = ES.head_ratios(HW, cls_b, m, ES.ln(m, HW.g, HW.beta, HW.eps, F32))      # teacher-forced: out follows the faulty head_y
+    assert fY > 1 and fO < 1, (fY, fO)
+    m = out.clone(); m[:, -4:] = 0
+    fY, fO = ES.head_ratios(HW, cls_b, y, m)
+    assert fY < 1 and fO > 1, (fY, fO)
+    # a weight that was not rounded to bf16 on the way in is another product: the bound is fp32-tight
+    lin_mod = ES.make_head(s.H, E)[0]
+    y32 = ES.lin(cls_b, lin_mod.weight.detach().double(), HW.b, F32)
+    assert ES.head_ratios(HW, cls_b, y32, out)[0] > 1
+
+
+@pytest.mark.parametrize("H", [128, 256, 384, 512, 640, 768, 896, 1024])
+def test_layouts_mirror_at_input_s(H):
+    """ES.layouts() restates csrc/encoder.hip:encoder_layer_forward's dispatch.  At input S (2,064 rows) under the default options
+    every hand-off is row-major for every admitted hidden size; Y holds FFN2's pre-LayerNorm sums everywhere but at 768 with a
+    long contraction, where the split-contraction slab takes its place.  The envelope GPU test asserts this answer per run; here
+    it is pinned for all eight sizes so that the mirror cannot rot silently."""
+    rows = int(((np.asarray(LENS_S) + 7) // 8 * 8).sum())
+    assert rows == 2064 and dict(ES._opts) == dict(ES.DEFAULTS)
+    for I in (64, 192, 320, 448, 1024, 2304, 3072, 4096):
+        lo = ES.layouts(rows, H, I)
+        assert lo == dict(qk=False, ctx=False, hm=False, y_live=not (H == 768 and I >= 2048)), (H, I, lo)
+    # the fused kernel is keyed on H == 768 alone: lowering its row threshold changes nothing elsewhere
+    ES._opts["fused_ln_min_rows"] = 1
+    try:
+        lo = ES.layouts(rows, H, 1024)
+        assert (lo["qk"], lo["ctx"], lo["y_live"]) == ((True, True, False) if H == 768 else (False, False, True))
+    finally:
+        ES._opts["fused_ln_min_rows"] = ES.DEFAULTS["fused_ln_min_rows"]

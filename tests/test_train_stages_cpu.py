@@ -5,7 +5,9 @@
     stand-in there being a THIRD computation (the fp32 chain over the tokens in another order), not the pair's own member;
   * every planted fault breaks the check of the stage it was planted in -- and of no stage in front of it;
   * the reference pair of the measured stage stays at flip level (c < 0.02, f < 2 %) on these inputs.
-Models W (768 / 12 / 3072) and N (384 / 6 / 320), two layers each; sequences on both sides of 8 and 64 rows and one beyond 128.
+Models W (768 / 12 / 3072), N (384 / 6 / 320) and the six ES.ENVELOPE shapes (128 / 64, 256 / 192, 512 / 1024, 640 / 448,
+896 / 2304, 1024 / 4096: the stand-in at all six, the planted faults at 640 / 448 and 1024 / 4096), two layers each; sequences on
+both sides of 8 and 64 rows and one beyond 128.
 Run with -s to see the ratios."""
 import numpy as np
 import pytest
@@ -45,7 +47,8 @@ def walk(shape, pool_mean, gelu_gp, drop, fault=None):
 
 
 @pytest.mark.parametrize("shape,pool_mean,gelu_gp,drop", [("W", 0, 1, None), ("W", 1, 0, None), ("W", 0, 0, DROP), ("W", 1, 1, DROP),
-                                                          ("N", 0, 0, None), ("N", 1, 1, None), ("N", 0, 1, DROP), ("N", 1, 0, DROP)])
+                                                          ("N", 0, 0, None), ("N", 1, 1, None), ("N", 0, 1, DROP), ("N", 1, 0, DROP)] +
+                         [(sh,) + c for sh in ES.ENVELOPE for c in ((0, 1, None), (1, 0, DROP))])
 def test_stand_in_passes_every_stage(shape, pool_mean, gelu_gp, drop):
     rep = walk(shape, pool_mean, gelu_gp, drop)
     for n, v, b in rep.items:
@@ -104,7 +107,7 @@ def test_every_fault_has_a_case():
     assert sorted(FAULT_CASES) == sorted(TS.FAULTS)
 
 
-@pytest.mark.parametrize("shape", ["W", "N"])
+@pytest.mark.parametrize("shape", ["W", "N", "H640", "H1024"])
 @pytest.mark.parametrize("fault", sorted(FAULT_CASES))
 def test_planted_fault_breaks_its_stage(fault, shape):
     pool_mean, gelu_gp, drop, must = FAULT_CASES[fault]
