@@ -59,7 +59,6 @@ static EncBufs enc_plan(const convdr_encoder_config* c, int64_t rows, int B, cha
 static int64_t g_fused_ln_max_k = 1 << 30;
 static int64_t g_hm_blocked = 1;    // blocked activation hand-offs; convdr_set_option("hm_blocked", 0) gives the row-major paths back
 static int64_t g_fused_ln_min_rows = 128 * 192;   // below this the 128-token tiles cannot fill the 256 CUs
-static int64_t g_ln_mfma16 = 1;     // fused projection + LayerNorm kernel: 1 k_gemm_resid_ln_m16 (16x16x32 MFMA), 0 k_gemm_resid_ln (32x32x16)
 static int64_t g_cls_fold = 1;      // last layer without K / V (cls_fold.hpp); convdr_set_option("cls_fold", 0): project K, V + CLS_Q attention
 static int64_t g_cls_fold_min_rows = CLS_FOLD_MIN_ROWS;   // packed rows from which the fold is taken ("cls_fold_min_rows"; tests lower it)
 
@@ -85,15 +84,6 @@ static int gemm_resid_ln(const bf16_t* W, const bf16_t* Wks, const bf16_t* A, in
     a.dbg_skip_epi = dbg_epi == 1;
 #endif
     ProfScope prof(name, st);
-    if (g_ln_mfma16) {
-      static DeviceOnce attr16_done;
-      if (attr16_done.first())
-        CONVDR_CHECK_HIP(
-            hipFuncSetAttribute((const void*)k_gemm_resid_ln_m16, hipFuncAttributeMaxDynamicSharedMemorySize, LN_SMEM_BYTES));
-      hipLaunchKernelGGL(k_gemm_resid_ln_m16, dim3((unsigned)ceil_div64(rows, TileLN::TL)), dim3(512), LN_SMEM_BYTES, st, a);
-      CONVDR_CHECK_LAUNCH("k_gemm_resid_ln_m16");
-      return 0;
-    }
     hipLaunchKernelGGL(k_gemm_resid_ln, dim3((unsigned)ceil_div64(rows, TileLN::TL)), dim3(512), LN_SMEM_BYTES, st, a);
     CONVDR_CHECK_LAUNCH("k_gemm_resid_ln");
     return 0;
@@ -390,14 +380,6 @@ extern "C" int convdr_set_option(const char* name, int64_t value) {
   }
   if (strcmp(name, "hm_blocked") == 0) {   // FFN1 -> FFN2 activation layout (EPI_GELU_BLK): 1 blocked, 0 row-major
     g_hm_blocked = value;
-    return 0;
-  }
-  if (strcmp(name, "mfma16") == 0) {   // blocked FFN1 / QKV tiles of the forward: 1 the 16x16x32 MFMA main loop, 0 the 32x32x16 kernels (gemm_launch.hpp)
-    g_mfma16 = value;
-    return 0;
-  }
-  if (strcmp(name, "ln_mfma16") == 0) {   // fused projection + LayerNorm: 1 the 16x16x32 MFMA kernel (k_gemm_resid_ln_m16), 0 k_gemm_resid_ln (gemm_ln.hpp)
-    g_ln_mfma16 = value;
     return 0;
   }
   if (strcmp(name, "cls_fold") == 0) {   // last layer, CLS pooling: 1 Wk / Wv folded through the CLS query (cls_fold.hpp), 0 K / V projection + CLS_Q attention

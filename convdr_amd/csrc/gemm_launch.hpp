@@ -13,11 +13,6 @@ inline void* g_attn_trace = nullptr;
 inline void* g_clock_probe = nullptr;   // convdr_set_option "clock_probe": [slots][4] uint64, one slot per FFN1 launch (round robin)
 inline int64_t g_clock_probe_slots = 1, g_clock_probe_next = 0;
 
-// convdr_set_option "mfma16": 1 (default) = the inference forward's 256 x 256 FFN1 (EPI_GELU_BLK) and QKV (EPI_QKV with blocked Q / K)
-// tiles run the 16x16x32 MFMA main loop (k_gemm<.., 1>: same LDS image, higher delivered clock; profiles/mfma16_ab.txt),
-// 0 = the 32x32x16 kernels every other launch uses (tests and A/B runs exercise both)
-inline int64_t g_mfma16 = getenv("CONVDR_MFMA16") ? atoi(getenv("CONVDR_MFMA16")) : 1;
-
 template <int EPI, class T, int MSHAPE = 0>
 inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
   static_assert(T::TR == T::TL || EPI != EPI_QKV, "square tiles: the QKV kernel swaps operand roles per tile");
@@ -127,10 +122,16 @@ inline int launch_gemm(GemmArgs a, hipStream_t st, const char* prof_name) {
     }
   }
   if (fits && a.tile_hint == 256) choice = 256;
-  if constexpr (EPI == EPI_GELU_BLK || EPI == EPI_QKV) {
-    if (choice == 256 && g_mfma16 != 0 && (EPI != EPI_QKV || a.qk_blocked)) return launch_gemm_t<EPI, Tile256, 1>(a, st, prof_name);
+  // The inference forward's 256 x 256 FFN1 (EPI_GELU_BLK) and QKV (EPI_QKV with blocked Q / K) tiles run the 16x16x32 MFMA main
+  // loop (k_gemm<.., 1>: same LDS image, higher delivered clock; profiles/mfma16_ab.txt); every other launch the 32x32x16 one.
+  if constexpr (EPI == EPI_GELU_BLK) {
+    if (choice == 256) return launch_gemm_t<EPI, Tile256, 1>(a, st, prof_name);
+  } else {
+    if constexpr (EPI == EPI_QKV) {
+      if (choice == 256 && a.qk_blocked) return launch_gemm_t<EPI, Tile256, 1>(a, st, prof_name);
+    }
+    if (choice == 256) return launch_gemm_t<EPI, Tile256>(a, st, prof_name);
   }
-  if (choice == 256) return launch_gemm_t<EPI, Tile256>(a, st, prof_name);
   if constexpr (WIDE_OK) {
     if (choice == 192) return launch_gemm_t<EPI, TileWide>(a, st, prof_name);
   }

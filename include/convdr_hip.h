@@ -962,11 +962,7 @@ int convdr_adamw_step_packed(float* p, const float* g, float* m, float* v, int64
 /* Tuning / test knobs: "fused_ln_min_rows" = minimum packed rows for the fused GEMM + residual + LayerNorm kernel
  * (default 24576; tests lower it to exercise that kernel on small inputs); "fused_ln_max_k" = largest contraction
  * length it is used for; "hm_blocked" = 0 / 1: row-major / blocked layout of the FFN activation between FFN1 and the
- * fused FFN2 + LayerNorm kernel (default 1; a workspace-internal choice, results are identical); "mfma16" = 1 / 0: the 256 x 256
- * blocked FFN1 and QKV tiles of the inference forward on the 16x16x32 / the 32x32x16 bf16 MFMA shape (default 1: the chip holds
- * a higher clock on it; the same LDS image, identical results; environment CONVDR_MFMA16 sets the default); "ln_mfma16" = 1 / 0: the fused
- * GEMM + residual + LayerNorm kernel on the 16x16x32 / the 32x32x16 bf16 MFMA shape (default 1; the same projection sums, the row
- * statistics reduced from 16 instead of 8 partial sums per token: rounding-level differences in the output); "cls_fold" = 1 / 0: the last
+ * fused FFN2 + LayerNorm kernel (default 1; a workspace-internal choice, results are identical); "cls_fold" = 1 / 0: the last
  * layer of the inference forward with CLS pooling folds Wk and Wv through the CLS query and reads the layer input once (K and
  * V are never formed) / projects K and V of every token and runs the CLS-query attention (default 1; rounding-level
  * differences; "cls_fold_min_rows" = packed rows from which the first form is taken, default 16,384: below, the second is

@@ -1,6 +1,6 @@
 """The 16x16x32 MFMA main loop of the inference forward's 256 x 256 QKV and FFN1 tiles (k_gemm<EPI_QKV / EPI_GELU_BLK, Tile256, 1>:
 csrc/gemm_nt.hpp gemm_nt_mainloop_r3_m16, the blocked and V-third epilogues of csrc/encoder_kernels.hpp) against the stage
-references of tests/encoder_stages.py, every live token, under convdr_set_option("mfma16") = 0 (the 32x32x16 kernels) and = 1.
+references of tests/encoder_stages.py, every live token.
 
 Options of every case: fused_ln_min_rows 1, fused_ln_max_k 2^20, gemm_tile_policy 1, hm_blocked 1 -- Q / K / ctx blocked and
 256 x 256 tiles wherever the shape allows.  Which kernel a case reaches (csrc/encoder.hip, csrc/gemm_launch.hpp):
@@ -15,13 +15,9 @@ Options of every case: fused_ln_min_rows 1, fused_ln_max_k 2^20, gemm_tile_polic
 Bars: the existing ones, nothing new -- stage B (Q, K, V: one rounding of an fp32 sum, ratio < 1) and stage D (Hm, and X_l read
 back through FFN2: c <= 4 c_ref, f <= max(10 f_ref, 1 %) against the fp64 / fp32-accumulating reference pair on the GPU's own
 inputs); margins are recorded with tests.helpers.margin, which asserts them.
-That "mfma16" = 0 IS the parent's path is a statement about code, not about a run: k_gemm<.., 0> is the kernel every other
-launch uses and compiles to the parent's instructions (tools/dbg/isa_identity.py, profiles/mfma16_ab.txt); what a run can
-show, and test_switch does, is that the option reaches the launcher both ways and that the library's default is the
-documented one (a run that leaves the option alone equals the run that sets it to that value, byte for byte).
+The margin tags keep the "m1" of the time when a switch chose between this main loop (1) and the 32x32x16 one (0, retired for
+these tiles).
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -32,7 +28,6 @@ from tests.helpers import margin
 
 pytestmark = pytest.mark.gpu
 
-MFMA16_DEFAULT = 1
 OPTS = dict(fused_ln_min_rows=1, fused_ln_max_k=1 << 20, gemm_tile_policy=1, hm_blocked=1)
 LENS_P = [128] * 59 + [127, 65, 9]
 _CACHE = {}
@@ -43,19 +38,6 @@ def _drop_caches():
     yield
     _CACHE.clear()
     ES._MEMO.clear()
-
-
-@contextlib.contextmanager
-def mfma16(v):
-    """convdr_set_option("mfma16", v) around a run; None leaves the option alone.  Restores the library's default."""
-    from convdr_amd import _lib
-    L = _lib.lib()
-    try:
-        if v is not None:
-            _lib.check(L.convdr_set_option(b"mfma16", int(v)), "convdr_set_option")
-        yield
-    finally:
-        L.convdr_set_option(b"mfma16", MFMA16_DEFAULT)
 
 
 def tower():
@@ -74,11 +56,11 @@ def inputs(name):
     return ES.make_inputs(LENS_P, 1000, 3)
 
 
-def run(inp, l, m16, fresh=False):
-    key = (inp, l, m16)
+def run(inp, l, fresh=False):
+    key = (inp, l)
     if fresh or key not in _CACHE:
         ids, lens = inputs(inp)
-        with ES.options(**OPTS), mfma16(m16):
+        with ES.options(**OPTS):
             r = ES.run_layers(tower()[0], ids, lens, l)
         if fresh:
             return r
@@ -109,58 +91,38 @@ def check_stages(tag, l, prev, cur, lens):
         margin("mfma16/%s/D_%s_f" % (tag, name), f, f_cap)
 
 
-@pytest.mark.parametrize("m16", [0, 1])
 @pytest.mark.parametrize("l", [0, 1, 2])
-def test_single_tile_walk(l, m16):
-    """Input S, layers 0-2, every live token.  Layer 0 is the embedding (no GEMM): it must not depend on the switch."""
-    cur = run("S", l, m16)
+def test_single_tile_walk(l):
+    """Input S, layers 0-2, every live token.  Layer 0 is the embedding (no GEMM): only its layout is checked."""
+    cur = run("S", l)
     lo = cur["layout"]
     assert lo["qk"] and lo["ctx"] and not lo["hm"] and not lo["y_live"]
     if l == 0:
-        assert torch.equal(cur["X_bits"], run("S", 0, 1 - m16)["X_bits"])
         return
     lens = [int(n) for n in inputs("S")[1]]
-    check_stages("S/m%d/l%d" % (m16, l), l, run("S", l - 1, m16), cur, lens)
+    check_stages("S/m1/l%d" % l, l, run("S", l - 1), cur, lens)
 
 
-@pytest.mark.parametrize("m16", [0, 1])
-def test_persistent_walk(m16):
+def test_persistent_walk():
     """Input P, one layer: 279 QKV tiles and 372 blocked FFN1 tiles on 256 workgroups, up to two tiles per workgroup."""
-    cur = run("P", 1, m16)
+    cur = run("P", 1)
     lo = cur["layout"]
     assert lo["qk"] and lo["ctx"] and lo["hm"] and not lo["y_live"]
     lens = [int(n) for n in inputs("P")[1]]
-    check_stages("P/m%d/l1" % m16, 1, run("P", 0, m16), cur, lens)
+    check_stages("P/m1/l1", 1, run("P", 0), cur, lens)
 
 
-@pytest.mark.parametrize("m16", [0, 1])
-def test_stale_memory(m16):
+def test_stale_memory():
     """The persistent case twice, each on a workspace and an output pre-filled with 0xFF bytes (every bf16 / fp32 a NaN; the
     second run's buffers come out of the allocator holding the first run's results until that fill): identical bytes, and
     run_layers itself refuses a live row that is not finite -- no element left unwritten, nothing read before it is written."""
-    a = run("P", 1, m16)
-    b = run("P", 1, m16, fresh=True)
+    a = run("P", 1)
+    b = run("P", 1, fresh=True)
     for k in ("X_bits", "Q", "K", "V", "ctx", "Hm", "out"):
         assert torch.equal(a[k], b[k]), k
 
 
 def test_switch():
-    """The option reaches the launcher, and the library's default is MFMA16_DEFAULT (see the module docstring); the two shapes
-    agree within the stage bars (test_persistent_walk / test_single_tile_walk hold both to them) -- the largest differences
-    are recorded here."""
-    untouched = run("P", 1, None, fresh=True)
-    dflt = run("P", 1, MFMA16_DEFAULT)
-    for k in ("X_bits", "Q", "K", "V", "ctx", "Hm", "out"):
-        assert torch.equal(untouched[k], dflt[k]), k
-    W = tower()[1]
-    for inp in ("S", "P"):   # layer 1: both runs start from the same X_0, so the same reference bounds both
-        a, b, x = run(inp, 1, 0), run(inp, 1, 1), run(inp, 0, 0)["X"]
-        L = W.layers[0]
-        _, bound = ES.memo(("B", id(W), 1), [x], lambda: ES.proj_ref(x, L["wqkv"], L["bqkv"]))
-        for i, k in enumerate(("Q", "K", "V")):   # each within `bound` of one reference, so within 2 bound of each other
-            r = float(((a[k] - b[k]).abs() / bound[:, i * W.H:(i + 1) * W.H]).max())
-            margin("mfma16/switch/%s/l1/%s_diff_over_bound" % (inp, k), r, 2.0)
-        for k in ("Q", "K", "V", "Hm", "X"):
-            d = float((a[k] - b[k]).abs().max())
-            n = int((a[k] != b[k]).sum())
-            print("%s l1 %s: max |mfma16 1 - mfma16 0| %.3g, %d of %d elements differ" % (inp, k, d, n, a[k].numel()))
+    """The switch between this main loop and the 32x32x16 one is gone: its name is an unknown option."""
+    from convdr_amd import _lib
+    assert _lib.lib().convdr_set_option(b"mfma16", 1) != 0
