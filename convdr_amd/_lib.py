@@ -75,6 +75,9 @@ _SIGNATURES = {
     "convdr_digest_host": (C.c_int, [_p, C.c_int64, C.c_uint64, _p]),
     "convdr_ip_debug_counts":(_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
     "convdr_ip_debug_band": (_p, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    # test aids: the raw scan scores of the last shallow search (out-pointers: id / s, T / ld)
+    "convdr_ip_debug_list": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_p), C.POINTER(_p)]),
+    "convdr_ip_debug_sample": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_p), C.POINTER(C.c_int64)]),
 }
 
 

@@ -26,6 +26,7 @@ struct IpBand {
   float eps_coef, eps_abs;   // ip_eps_coef, ip_eps_abs
   float p_scale;             // power of two of the fp16 operand; 1 for bf16
   float norm_limit;          // IP_F16_NORM_LIMIT, or +inf for bf16
+  float norm_floor;          // IP_BF16_NORM_FLOOR, or 0 for fp16 (whose operands are rescaled)
 
   // the largest passage norm in scan units
   __device__ __forceinline__ float pm() const { return p_max_norm[0] * p_scale; }
@@ -35,8 +36,14 @@ struct IpBand {
     return (eps_coef * qn * pmax + eps_abs * (qn + pmax) + eps_abs * eps_abs) * 1.001f + 1e-30f;
   }
   // fp16 scan copy built with a scale too large for this block's norms -- or a query so long that its per-row power-of-two
-  // scale hit the clamp (norm > ~8e34) --: elements of an operand may be inf, and no score of the query proves anything
-  __device__ __forceinline__ bool out_of_range(int q) const { return pm() > norm_limit || qnorm[q] > norm_limit; }
+  // scale hit the clamp (norm > ~8e34) --: elements of an operand may be inf, and no score of the query proves anything.
+  // bf16 scan: a non-zero norm below the floor -- operands or products may be subnormal, which eps (relative terms only) does
+  // not cover (derivation: IP_BF16_NORM_FLOOR, ip_topk.hip).  A zero norm stays in range: every score of the query, or of the
+  // block, is exactly 0, and the + 1e-30f of eps covers it.
+  __device__ __forceinline__ bool out_of_range(int q) const {
+    const float qn = qnorm[q], pmax = pm();
+    return pmax > norm_limit || qn > norm_limit || (pmax > 0.f && pmax < norm_floor) || (qn > 0.f && qn < norm_floor);
+  }
 };
 
 // The certificate of a top-k cut (proof: above k_ip_cut).  cnt: the query's hits, c = min(cnt, cap) of them listed;

@@ -24,12 +24,13 @@ struct IpBlock {
   bool split() const { return p_half_lo != nullptr || two_pass; }         // the query's remainder is an operand: the tighter band
   float scan_scale() const { return kind() == IP_KIND_F16 ? p_scale : 1.f; }   // units of the scan scores and thresholds
   float norm_limit() const { return kind() == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY; }   // above it: CONVDR_IP_RANGE
+  float norm_floor() const { return kind() == IP_KIND_BF16 ? IP_BF16_NORM_FLOOR : 0.f; }       // non-zero and below it: CONVDR_IP_RANGE
   double unscale() const { return rows_f16() ? 1.0 / (double)p_scale : 1.0; }  // one factor on the fp64 sum over scaled rows
   int64_t n_need() const { return row_bits ? n_allowed : n; }   // TOP-K ONLY (range search sets no n_allowed): need = min(k, n_need)
   float eps_coef() const { return ip_eps_coef(d, split(), kind()); }
   float eps_abs() const { return ip_eps_abs(d, split(), kind()); }
   // the error band of this block's scan scores for queries whose norms are at qnorm (device, [nq]): what every finishing kernel takes
-  IpBand band(const float* qnorm) const { return {qnorm, p_max_norm, eps_coef(), eps_abs(), scan_scale(), norm_limit()}; }
+  IpBand band(const float* qnorm) const { return {qnorm, p_max_norm, eps_coef(), eps_abs(), scan_scale(), norm_limit(), norm_floor()}; }
 };
 
 // per-call arguments of the seven top-k entries, in the entries' order
@@ -121,7 +122,8 @@ struct IpPlan : IpPlanHead {
   size_t o_qlo, o_counts_packed, o_T, o_x;
 };
 
-// Layout as before the shared head: qb|qlo|qnorm|tau|counts|counts_packed|m|T|id|s|x, same sizes (id, s, x: no accessor).
+// Layout as before the shared head: qb|qlo|qnorm|tau|counts|counts_packed|m|T|id|s|x, same sizes (T, id, s: convdr_ip_debug_sample /
+// convdr_ip_debug_list; x: no accessor).
 static IpPlan ip_plan(int nq, int64_t n, int d, int cap) {
   IpPlan p{ip_plan_head(nq, n)};
   p.nSt = 0; p.stride = 1; p.nvals = 0; p.npow2 = 2;

@@ -31,7 +31,8 @@ __device__ __forceinline__ float half_hi_to_f32(uint32_t packed) {
 }
 
 // PER_ROW_SCALE (queries of the fp16 scan): every row is multiplied by its own power of two 2^(12 - e), |row| = m 2^e
-// with m in [0.5, 1), so its scaled norm lies in [2^11, 2^12); row_norm receives the SCALED norm.  Otherwise `scale`
+// with m in [0.5, 1) (frexpf of the fp32 norm), so its scaled norm lies in [2^11, 2^12) -- one binade below the block's
+// [2^12, 2^13), see IP_F16_TARGET_EXP; tests/test_scan_error_gpu.py asserts the interval.  row_norm receives the SCALED norm.  Otherwise `scale`
 // (a power of two; 1 for bf16) multiplies every row and row_norm / max_norm are UNSCALED.
 template <int KIND, bool PER_ROW_SCALE>
 __global__ void __launch_bounds__(256) k_rows_to_half(const float* __restrict__ X, int64_t n, int d,

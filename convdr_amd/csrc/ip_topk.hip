@@ -62,8 +62,25 @@ static inline float ip_eps_abs(int d, bool x3, int kind) {   // multiplies (|q| 
   // split scan: hi and lo are both halfs; the remainder x - hi - lo carries at most eta as well
   return (float)((x3 ? 2.0 : 1.0) * IP_F16_ETA * (1.0 + 1.0 / 2048.0) * sqrt((double)d) * 1.0001);
 }
-constexpr float IP_F16_TARGET_EXP = 12.f;    // scales put the (first) max norm into [2^12, 2^13)
+constexpr float IP_F16_TARGET_EXP = 12.f;    // the block's scale puts its (first) max norm into [2^12, 2^13) (convdr_ip_f16_scale),
+                                             // a query's own scale puts its norm into [2^11, 2^12) (k_rows_to_half<F16, true>)
 constexpr float IP_F16_NORM_LIMIT = 60000.f; // scaled norms above this may hold elements that round to inf: CONVDR_IP_RANGE
+// The bf16 scan does not rescale, and its bound has relative terms only.  k_rows_to_half<IP_KIND_BF16> rounds elements below
+// 2^-126 to bf16 SUBNORMALS (quantum 2^-133, no relative precision), and products below 2^-126 lose bits in the fp32
+// accumulator: in the operand-rounding model rows of elements ~2^-129 / 2^-131 / 2^-132 against a query of 2^40 whose signs
+// follow their rounding errors miss the bound by 1.2x / 5.5x / 10x, and exact operands of ~3e-23 on both sides by 30x through
+// the roundings of their products alone (tests/test_scan_error_cpu.py, family `tiny`).  So the bf16 kinds refuse a NON-ZERO
+// norm below a floor -- IpBand::out_of_range, CONVDR_IP_RANGE:
+//   operands   a subnormal rounding adds at most 2^-134 per element, sqrt(d) 2^-134 |q| per score (an MFMA that flushed
+//              subnormal inputs: 2^-126, sqrt(d) 2^-126 |q|); that is negligible against u |q| pm when pm >> sqrt(d) 2^-127.
+//   products   each product below 2^-126 loses at most 2^-150: d 2^-150 per score, negligible against the band when
+//              |q| pm >> d 2^-143.  (An accumulator that flushed such products or partial sums loses less than d 2^-126 <=
+//              2^-114: the + 1e-30f of IpBand::eps covers that at any norm.)
+// With d <= 4096, a floor of 2^-60 on each norm gives pm >= 2^-60 = 2^61 sqrt(d) 2^-127 and |q| pm >= 2^-120 = 2^11 d 2^-143:
+// more than 2^50 of margin on the operand term even if subnormal inputs were flushed, 2^11 on the product term.  2^-60 is 18
+// orders of magnitude below any real embedding norm.  A zero norm stays in range: every score is exactly 0.  The fp16 kinds
+// rescale both operands and are not affected (precision="auto" / "fp16" take such data).
+constexpr float IP_BF16_NORM_FLOOR = 0x1p-60f;
 
 }  // namespace convdr
 
@@ -169,6 +186,25 @@ extern "C" const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq,
 
 extern "C" const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, int64_t n, int d, int k, int cap) {
   return (const uint32_t*)((const char*)workspace + ip_plan(nq, n, d, cap).o_m);
+}
+
+// Test aids: where the last search on this workspace left its raw scan scores (include/convdr_hip.h says when they are whole).
+extern "C" int convdr_ip_debug_list(const void* workspace, int nq, int64_t n, int d, int k, int cap, const uint32_t** id,
+                                    const float** s) {
+  CONVDR_REQUIRE(workspace && id && s && nq > 0 && n >= 0 && d > 0 && cap > 0, "convdr_ip_debug_list: bad arguments");
+  const IpPlan p = ip_plan(nq, n, d, cap);
+  *id = (const uint32_t*)((const char*)workspace + p.o_id);
+  *s = (const float*)((const char*)workspace + p.o_s);
+  return 0;
+}
+
+extern "C" int convdr_ip_debug_sample(const void* workspace, int nq, int64_t n, int d, int k, int cap, const float** T,
+                                      int64_t* ld) {
+  CONVDR_REQUIRE(workspace && T && ld && nq > 0 && n >= 0 && d > 0 && cap > 0, "convdr_ip_debug_sample: bad arguments");
+  const IpPlan p = ip_plan(nq, n, d, cap);
+  *T = p.mode < 0 ? nullptr : (const float*)((const char*)workspace + p.o_T);
+  *ld = p.nq_pad;
+  return 0;
 }
 
 // ---- the half store ------------------------------------------------------------------------------------------------

@@ -168,6 +168,11 @@ class FlatIPIndex(_IndexStore):
             return D, I
         return D, torch.where(I >= 0, self.ids[I.clamp(min=0)], torch.full_like(I, -1))
 
+    # CONVDR_IP_RANGE from a bf16 scan: nothing rebuilds it away (the bf16 copy has no scale), so every entry ends with this
+    _BF16_RANGE = ("CONVDR_IP_RANGE from the bf16 scan: a query or the block has a non-zero norm below 2^-60, where bf16 operands "
+                   "and their products are subnormal and the scan's error bound does not hold; use precision=\"auto\" or "
+                   "\"fp16\", whose scan rescales both operands")
+
     def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
                      deep=False, allowed=None):
         """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth; with a
@@ -337,6 +342,8 @@ class FlatIPIndex(_IndexStore):
         enqueue = functools.partial(getattr(self, depth.enqueue), **kw)
         D, I, status, tau_retry = first
         n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()   # one host round trip
+        if n_range and self.kind != "f16":
+            raise _lib.ConvdrError("convdr_ip_search: " + self._BF16_RANGE)     # no threshold and no retry changes this verdict
         if self.kind == "f16" and n_range:
             self._rebuild_scaled()
             self.stats["rescaled"] = 1
@@ -551,6 +558,8 @@ class FlatIPIndex(_IndexStore):
         (no threshold pass, tau = -inf), so the result is exact by construction."""
         D, I, status, _ = self._enqueue(qq, kq, None, cap, False, rows=rows, rank_target=0)
         if int((status != 0).sum().item()):
+            if self.kind != "f16" and int((status == STATUS_RANGE).sum().item()):
+                raise _lib.ConvdrError("convdr_ip_search: " + self._BF16_RANGE)
             raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % rows[1].shape[0])
         return D, I
 
@@ -845,9 +854,10 @@ class FlatIPIndex(_IndexStore):
             st, cnt, result = one_pass(idx, sub, cap)
             passes, longest = passes + 1, max(longest, cap)
             if (st == STATUS_RANGE).any():
-                if self.kind != "f16" or self.stats["rescaled"]:
-                    raise _lib.ConvdrError("%s: CONVDR_IP_RANGE %s" % (who, "after the scan copy was rebuilt"
-                                           if self.stats["rescaled"] else "from a bf16 scan"))
+                if self.kind != "f16":
+                    raise _lib.ConvdrError("%s: %s" % (who, self._BF16_RANGE))
+                if self.stats["rescaled"]:
+                    raise _lib.ConvdrError("%s: CONVDR_IP_RANGE after the scan copy was rebuilt" % who)
                 self._rebuild_scaled()
                 self.stats["rescaled"] = 1
                 groups.insert(0, (idx, cap))

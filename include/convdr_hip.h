@@ -572,6 +572,28 @@ int convdr_digest_host(const void* buf, int64_t n_bytes, uint64_t word0, uint64_
 const uint32_t* convdr_ip_debug_counts(const void* workspace, int nq, int64_t n, int d, int k, int cap);
 const uint32_t* convdr_ip_debug_band(const void* workspace, int nq, int64_t n, int d, int k, int cap);
 
+/* Test aids: the RAW scan scores S~ of the last shallow search (convdr_ip_search, _f16, _h16, _filtered with deep = 0) on this
+ * workspace, in scan units (fp16 kinds: query scale x p_scale x q . (p - centre)), before any re-score.  Same arguments as the two
+ * accessors above plus out-pointers; both return 0, or a negative code for a NULL pointer or sizes no plan exists for.  The
+ * pointers are device pointers into `workspace`, valid until its next search.
+ * convdr_ip_debug_list    *id / *s: the candidate list [nq, cap], row ids (uint32) and their scan scores (float); query q's
+ *                entries start at q * cap.  The cut REWRITES the list: it compacts the band {S~ >= S~(k) - 2 eps} to the front
+ *                and the rest is left in no defined state.  The list therefore holds the scan score of EVERY row exactly when
+ *                the band is the whole list: k >= n (the cut is -inf), n <= cap (no threshold pass: every row is a candidate)
+ *                and the three-launch chain (convdr_set_option("ip_fused_finish", 0)) -- the plan the exhaustive rung runs.
+ *                Its first convdr_ip_debug_band entries per query are then all n rows, each once, in no particular order (the
+ *                rows past n of the last 256-row tile, which the scan lists with -inf, are dropped by the cut).  With a row
+ *                filter: the allowed rows.  In any other plan only the first convdr_ip_debug_band entries mean anything: the
+ *                band's rows and scores.
+ * convdr_ip_debug_sample  *T: the threshold sample, *ld its pitch (the padded query count): the score of sampled row i for
+ *                query q is T[i * ld + q].  *T is NULL when the plan has no sample (n <= cap).  For cap < n <= 32,768 the
+ *                sample is the whole block (every row's scan score, rows n .. the end of the last 256-row tile -inf) -- provided
+ *                the call estimated its threshold: tau_in == NULL and no row filter that admits at most cap rows; otherwise
+ *                the region is not written.  Above 32,768 rows it holds the two best scores per 64 sampled rows, which steer
+ *                the threshold and prove nothing. */
+int convdr_ip_debug_list(const void* workspace, int nq, int64_t n, int d, int k, int cap, const uint32_t** id, const float** s);
+int convdr_ip_debug_sample(const void* workspace, int nq, int64_t n, int d, int k, int cap, const float** T, int64_t* ld);
+
 /* Two-way merge of per-query result lists: replaces the Python pointer walk of
  *   /root/reference/drivers/run_convdr_inference.py:213-229
  * Da/Ia [nq, na] is the running result (earlier blocks), Db/Ib [nq, nb] the new block's, every row sorted by score

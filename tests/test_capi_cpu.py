@@ -43,6 +43,23 @@ def test_every_ctypes_signature_has_the_declared_parameter_count():
     assert set(UNPARSED) <= set(_lib._SIGNATURES)
 
 
+def test_scan_score_accessors_are_declared_bound_and_refuse_null():
+    """convdr_ip_debug_list / convdr_ip_debug_sample: the argument list of convdr_ip_debug_counts plus two out-pointers."""
+    import ctypes as C
+    from tests import capi_decl
+    L = _lib.lib()
+    head = capi_decl.params("convdr_ip_debug_counts").strip()
+    for name, tail in (("convdr_ip_debug_list", ("const uint32_t** id", "const float** s")),
+                       ("convdr_ip_debug_sample", ("const float** T", "int64_t* ld"))):
+        assert name in _declared() and name in _lib.exported_symbols()
+        params = [p.strip() for p in capi_decl.params(name).split(",")]
+        assert ", ".join(params[:-2]) == ", ".join(p.strip() for p in head.split(",")) and tuple(params[-2:]) == tail, params
+        assert getattr(L, name)(None, 1, 10, 64, 1, 1024, None, None) != 0 and name.encode() in L.convdr_last_error()
+    base, T, ld = 1 << 20, C.c_void_p(), C.c_int64()
+    assert L.convdr_ip_debug_sample(base, 5, 1024, 64, 10, 1024, C.byref(T), C.byref(ld)) == 0 and T.value is None and ld.value == 128
+    assert L.convdr_ip_debug_sample(base, 5, 1025, 64, 10, 1024, C.byref(T), C.byref(ld)) == 0 and T.value > base
+
+
 def test_argument_validation_needs_no_gpu():
     L = _lib.lib()
     assert L.convdr_ip_workspace_bytes(1000, 1_000_000, 768, 100, 4096) > 0

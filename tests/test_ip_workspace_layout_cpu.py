@@ -25,3 +25,21 @@ def test_sizes_and_region_offsets_are_the_recorded_ones():
         assert len(rec[name]) >= 48
         for *args, want in rec[name]:
             assert getattr(L, name)(base, *args) - base == want, (name, args, want)
+    # the raw scan scores (test aids): list ids / scores, and the threshold sample with its pitch (-1: the plan has no sample).
+    # The same coarse grid, plus shapes with cap < n <= 32,768 (the sample is the whole block) -- these offsets depend on n.
+    import ctypes as C
+    for name, second in (("convdr_ip_debug_list", C.c_void_p), ("convdr_ip_debug_sample", C.c_int64)):
+        assert len(rec[name]) >= 48
+        for *args, want_a, want_b in rec[name]:
+            a, b = C.c_void_p(), second()
+            assert getattr(L, name)(base, *args, C.byref(a), C.byref(b)) == 0, (name, args)
+            got_a = -1 if a.value is None else a.value - base
+            got_b = b.value - base if second is C.c_void_p else b.value
+            assert (got_a, got_b) == (want_a, want_b), (name, args, got_a, got_b)
+    assert any(r[-2] == -1 for r in rec["convdr_ip_debug_sample"]) and any(r[-2] > 0 for r in rec["convdr_ip_debug_sample"])
+    # list, sample and the two older accessors describe ONE plan: counts < band < sample <= list ids < list scores
+    for (*args, o_id, o_s), (*_, o_T, ld) in zip(rec["convdr_ip_debug_list"], rec["convdr_ip_debug_sample"]):
+        nq, cap = args[0], args[4]
+        assert o_s - o_id == (nq * cap * 4 + 255) // 256 * 256 and ld >= nq and ld % 128 == 0, args
+        band = L.convdr_ip_debug_band(base, *args) - base
+        assert band < (o_T if o_T >= 0 else o_id) <= o_id, args
