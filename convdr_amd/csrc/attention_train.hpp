@@ -330,12 +330,12 @@ struct AttnBwdArgs {
   // hot key's unnormalised probability exactly 1.0 in the forward, the D that results agrees with the backward's own P dP
   // to fp32 rounding.  Null in every other layer (there the bf16 form is at the bf16-emulating oracle's own distance).
   const float* cls32;     // [B, H] or null
-  unsigned long long* trace;   // TRACE builds (tools/dbg/attn_bwd_trace.py): [workgroup][2][16] s_memtime stamps, or null
+  [[no_unique_address]] TraceKnobs knobs;   // trace library only (trace_knobs.hpp; tools/dbg/attn_bwd_trace.py): trace = [workgroup][2][16] s_memtime stamps, or null
 };
 #ifdef CONVDR_ENABLE_TRACE
 #define CONVDR_ATTB_STAMP(i)                                                                               \
-  if (a.trace && (threadIdx.x == 0 || threadIdx.x == 256))                                                  \
-    a.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + (threadIdx.x >> 8) * 16 + (i)] = __builtin_amdgcn_s_memtime();
+  if (a.knobs.trace() && (threadIdx.x == 0 || threadIdx.x == 256))                                          \
+    a.knobs.trace()[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + (threadIdx.x >> 8) * 16 + (i)] = __builtin_amdgcn_s_memtime();
 #else
 #define CONVDR_ATTB_STAMP(i)
 #endif
@@ -732,9 +732,9 @@ static __global__ void __launch_bounds__(512, 1) k_attention_bwd_fused(const Att
   const int b = a.order ? a.order[blockIdx.y] : (int)blockIdx.y, h = blockIdx.x;
   const int len = a.lens[b];
 #ifdef CONVDR_ENABLE_TRACE
-  if (a.trace && threadIdx.x == 0) {
-    a.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 14] = (unsigned long long)len;
-    a.trace[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 15] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
+  if (a.knobs.trace() && threadIdx.x == 0) {
+    a.knobs.trace()[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 14] = (unsigned long long)len;
+    a.knobs.trace()[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 32 + 15] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
   }
 #endif
   const int64_t base = a.cu[b];

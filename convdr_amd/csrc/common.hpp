@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "trace_knobs.hpp"
+
 namespace convdr {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;

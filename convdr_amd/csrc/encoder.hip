@@ -77,11 +77,11 @@ static int gemm_resid_ln(const bf16_t* W, const bf16_t* Wks, const bf16_t* A, in
     if (attr_done.first())
       CONVDR_CHECK_HIP(
           hipFuncSetAttribute((const void*)k_gemm_resid_ln, hipFuncAttributeMaxDynamicSharedMemorySize, LN_SMEM_BYTES));
-    GemmLnArgs a{W, A, rows, K, bias, R, gamma, beta, eps, X,
-                 K == 768 ? (unsigned long long*)g_gemm_trace_ln : nullptr, Wks, a_blocked ? 1 : 0, 0};
-#ifdef CONVDR_ENABLE_TRACE   // timing experiment that produces garbage results: only in the `make TRACE=1` library
-    static const int dbg_epi = getenv("CONVDR_DBG_SKIP_EPI") ? atoi(getenv("CONVDR_DBG_SKIP_EPI")) : 0;
-    a.dbg_skip_epi = dbg_epi == 1;
+    GemmLnArgs a{W, A, rows, K, bias, R, gamma, beta, eps, X, Wks, a_blocked ? 1 : 0};
+#ifdef CONVDR_ENABLE_TRACE   // stamps of the K = 768 launches; a timing experiment that produces garbage results (trace_knobs.hpp)
+    static const int skip_epi = env_knob("CONVDR_DBG_SKIP_EPI");
+    a.knobs.v_skip_epi = skip_epi == 1;
+    if (K == 768) a.knobs.v_trace = (unsigned long long*)g_gemm_trace_ln;
 #endif
     ProfScope prof(name, st);
     hipLaunchKernelGGL(k_gemm_resid_ln, dim3((unsigned)ceil_div64(rows, TileLN::TL)), dim3(512), LN_SMEM_BYTES, st, a);
@@ -156,7 +156,10 @@ int encoder_layer_forward(const convdr_encoder_config* c, const convdr_layer_wei
   g.qk_blocked = qk_blocked ? 1 : 0;
   if (!cls_only) {
     if (int e = launch_gemm<EPI_QKV>(g, st, "gemm_qkv")) return e;
-    AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.ctx, lse, 0.125f, (unsigned long long*)g_attn_trace};
+    AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.ctx, lse, 0.125f};
+#ifdef CONVDR_ENABLE_TRACE
+    a.knobs.v_trace = (unsigned long long*)g_attn_trace;
+#endif
     ProfScope prof("attention", st);
     if (ctx_blocked && qk_blocked) {
       hipLaunchKernelGGL((k_attention_fwd<false, true, true>), dim3((max_len + 127) / 128, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
@@ -197,7 +200,7 @@ int encoder_layer_forward(const convdr_encoder_config* c, const convdr_layer_wei
       // K and V of every token (a third of the projection and the Q / ctx traffic of the attention saved)
       g.W = (const bf16_t*)w->wqkv + (size_t)H * H; g.bias = w->bqkv + H; g.N = 2 * H; g.third0 = 1;
       if (int e = launch_gemm<EPI_QKV>(g, st, "gemm_qkv")) return e;
-      AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.cls_ctx, nullptr, 0.125f, nullptr};
+      AttnArgs a{p.Q, p.K, p.Vt, p.ldt, cu, lens, H, (int64_t)H, p.cls_ctx, nullptr, 0.125f};
       ProfScope prof("attention", st);
       if (qk_blocked) hipLaunchKernelGGL((k_attention_fwd<true, false, true>), dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
       else hipLaunchKernelGGL(k_attention_fwd<true>, dim3(1, c->heads, B), dim3(256), ATT_SMEM_BYTES, st, a);
@@ -439,6 +442,8 @@ extern "C" int convdr_set_option(const char* name, int64_t value) {
     g_clock_probe_slots = value > 0 ? value : 1;
     return 0;
   }
+  // the three stamp buffers: accepted by both libraries (the tools set them before they know which one is loaded), read by the
+  // trace library only (trace_knobs.hpp)
   if (strcmp(name, "attn_trace") == 0) {
     g_attn_trace = (void*)(uintptr_t)value;
     return 0;

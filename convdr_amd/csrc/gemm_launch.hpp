@@ -6,7 +6,8 @@
 
 namespace convdr {
 
-// experiment hook: when set (convdr_set_option "gemm_trace" = device pointer), FFN1 launches record phase stamps
+// convdr_set_option "gemm_trace" / "gemm_trace_ln" / "attn_trace" = device pointers for the kernels' phase stamps.  Both libraries
+// accept the options (the tools set them before they know which one is loaded); only the trace library reads them (trace_knobs.hpp)
 inline void* g_gemm_trace = nullptr;
 inline void* g_gemm_trace_ln = nullptr;
 inline void* g_attn_trace = nullptr;
@@ -22,18 +23,15 @@ inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
         hipFuncSetAttribute((const void*)k_gemm<EPI, T, MSHAPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             T::WAVES == 8 ? 160 * 1024 : T::SMEM_BYTES + T::TR * 4));
   }
-#ifdef CONVDR_ENABLE_TRACE   // timing experiments that produce garbage results: only in the `make TRACE=1` library
-  static const int dbg = getenv("CONVDR_DBG_SAME_TILE") ? atoi(getenv("CONVDR_DBG_SAME_TILE")) : 0;
-  a.dbg_same_tile = dbg;
-  static const int dbg_epi = getenv("CONVDR_DBG_SKIP_EPI") ? atoi(getenv("CONVDR_DBG_SKIP_EPI")) : 0;
-  a.dbg_skip_epi = dbg_epi;
-  static const int dbg_pre = getenv("CONVDR_DBG_PRELANDED") ? atoi(getenv("CONVDR_DBG_PRELANDED")) : 0;
-  a.dbg_prelanded = dbg_pre;
+#ifdef CONVDR_ENABLE_TRACE   // timing experiments that produce garbage results, and the phase stamps (trace_knobs.hpp)
+  static const int same_tile = env_knob("CONVDR_DBG_SAME_TILE"), skip_epi = env_knob("CONVDR_DBG_SKIP_EPI"),
+                   prelanded = env_knob("CONVDR_DBG_PRELANDED");
+  a.knobs.v_same_tile = same_tile;
+  a.knobs.v_skip_epi = skip_epi;
+  a.knobs.v_prelanded = prelanded;
   static const int trace_epi = getenv("CONVDR_TRACE_EPI") ? atoi(getenv("CONVDR_TRACE_EPI")) : (int)EPI_GELU_BF16;
-#else
-  constexpr int trace_epi = EPI_GELU_BF16;
+  a.knobs.v_trace = (EPI == trace_epi) ? (unsigned long long*)g_gemm_trace : nullptr;
 #endif
-  a.trace = (EPI == trace_epi) ? (unsigned long long*)g_gemm_trace : nullptr;
   a.clock_probe = nullptr;
   if (g_clock_probe && strcmp(prof_name, "gemm_ffn1") == 0) {
     a.clock_probe = (unsigned long long*)g_clock_probe + 4 * (g_clock_probe_next % g_clock_probe_slots);
@@ -59,8 +57,7 @@ inline int launch_gemm_t(GemmArgs a, hipStream_t st, const char* prof_name) {
 #ifdef CONVDR_ENABLE_TRACE
   // CONVDR_DBG_DOUBLE (tools/dbg/double_probe.sh): a class of idempotent launches goes out TWICE -- the step's difference is that
   // class's marginal cost with the product's own operands (1 = the training / inference forward's GEMMs, 2 = data-gradient GEMMs)
-  static const int dbl = getenv("CONVDR_DBG_DOUBLE") ? atoi(getenv("CONVDR_DBG_DOUBLE")) : 0;
-  if (dbl & (strcmp(prof_name, "gemm_dgrad") == 0 ? 2 : strncmp(prof_name, "gemm_", 5) == 0 && strcmp(prof_name, "gemm_cls") != 0 ? 1 : 0))
+  if (double_classes() & (strcmp(prof_name, "gemm_dgrad") == 0 ? 2 : strncmp(prof_name, "gemm_", 5) == 0 && strcmp(prof_name, "gemm_cls") != 0 ? 1 : 0))
     hipLaunchKernelGGL((k_gemm<EPI, T, MSHAPE>), dim3((unsigned)grid, splits), dim3(T::THREADS), lds, st, a);
 #endif
   CONVDR_CHECK_LAUNCH("k_gemm");

@@ -31,14 +31,15 @@ struct GemmLnArgs {
   const float *gamma, *beta;
   float eps;
   bf16_t* X;            // out [rows, 768] (may alias R: a workgroup reads its residual rows before it writes them)
-  unsigned long long* trace;   // experiment: [workgroup][16] s_memtime stamps of thread 0 (or null)
   const bf16_t* Wks;    // W in K-slice-major order [K / 32][768][32] (or null: stream the row-major W)
   int a_blocked;        // A is in the blocked layout [rows / 32][K / 8][32][8] the FFN1 epilogue EPI_GELU_BLK writes
-  int dbg_skip_epi;     // timing experiment (TRACE library only): the kernel ends after its main loop (garbage results)
+  // Trace library only (trace_knobs.hpp; empty in the product).  skip_epi: timing experiment, the kernel ends after its main
+  // loop (garbage results); trace: [workgroup][16] s_memtime stamps of thread 0 (or null)
+  [[no_unique_address]] TraceKnobs knobs;
 };
 #ifdef CONVDR_ENABLE_TRACE   // make TRACE=1: stamps for tools/gemm_trace_ln.py
 #define CONVDR_LN_TRACE(ph) \
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)blockIdx.x * 16 + (ph)] = __builtin_amdgcn_s_memtime();
+  if (a.knobs.trace() && threadIdx.x == 0) a.knobs.trace()[(size_t)blockIdx.x * 16 + (ph)] = __builtin_amdgcn_s_memtime();
 // per-wave stamps of K step 8 (and the top of step 9): trace[2048 * 16 + wg * 64 + wave * 8 + i]
 #define CONVDR_LN_STEP(i)                                                 \
   if (trace && kt == 8 + (i) / 5 && w.lane == 0 && blockIdx.x < 256)      \
@@ -268,9 +269,9 @@ __global__ void __launch_bounds__(512, 2) k_gemm_resid_ln(const GemmLnArgs a) {
   CONVDR_LN_TRACE(0)
   {
     const LnSrc src = ln_sources(a, t0, w);
-    ln_mainloop(src, a.K / LN_SLICE, smem, acc, w, a.trace);
+    ln_mainloop(src, a.K / LN_SLICE, smem, acc, w, a.knobs.trace());
   }
-  if (a.dbg_skip_epi) {   // (keeps the accumulators alive; never true in the product)
+  if (a.knobs.skip_epi()) {   // (keeps the accumulators alive; a constant 0 in the product)
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < MB; ++i)

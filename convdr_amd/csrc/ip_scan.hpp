@@ -31,7 +31,6 @@ struct ScanArgs {
   float* cand_s;     // EMIT: [nq, cap]
   int cap;
   float* T;          // FULL: [nPt*128, nq_pad]; TOP2: [nPt*8, nq_pad]
-  int dbg_prelanded; // timing experiment (TRACE library only): a tile's first K chunks are not waited for (garbage results)
   int two_pass;      // half store (fp16 only): S~ = P Qh + P Ql, the passage operand is exact and has no remainder copy
   const uint32_t* bits;  // row filter (FILT kernels only): row r is allowed iff bit r & 31 of word r >> 5 is set; padded with
                          // zero bits to whole TR-row tiles, word 0 = row 0 of P (a sub-block's pointer advances with its P)
@@ -41,6 +40,9 @@ struct ScanArgs {
   uint32_t* marks;       // MARK: [nq, mark_words], one bit per document and query: some row of it scored S~ >= tau_hi
   int64_t mark_words;    // MARK: words of one query's bitmap (>= ceil(ndocs / 32))
   int64_t ndocs;
+  // Trace library only (trace_knobs.hpp; empty in the product).  prelanded: timing experiment, a tile's first K chunks are not
+  // waited for (garbage results)
+  [[no_unique_address]] TraceKnobs knobs;
 };
 
 // The row filter in the scan epilogues.  A wave's accumulator tile mt covers the 32 rows (wr * MT + mt) * 32 .. + 31 of the
@@ -567,7 +569,7 @@ __global__ void __launch_bounds__(T::THREADS, 2) k_ip_scan_r3(const ScanArgs a) 
     uint32_t fw[T::MT];
 #pragma unroll
     for (int mt = 0; mt < T::MT; ++mt) fw[mt] = fw_next[mt];
-    slots = gemm_nt_mainloop_r3<T, F16, P_AUX>(src, a.d, smem, acc, w, slots, true, false, a.dbg_prelanded != 0);
+    slots = gemm_nt_mainloop_r3<T, F16, P_AUX>(src, a.d, smem, acc, w, slots, true, false, a.knobs.prelanded() != 0);
 #pragma unroll
     for (int nt = 0; nt < T::NT; ++nt) asm volatile("" : "+v"(tau_lane[nt]));
     if constexpr (BAND) {
@@ -616,7 +618,7 @@ static int launch_scan_x(const ScanArgs& a, hipStream_t st) {
     ScanArgs b = a;
 #ifdef CONVDR_ENABLE_TRACE   // timing only (every threshold = +inf: results are garbage): `make TRACE=1` library only
     if (getenv("CONVDR_DBG_SCAN_NOEMIT")) b.nq = 0;
-    if (getenv("CONVDR_DBG_PRELANDED")) b.dbg_prelanded = 1;
+    if (getenv("CONVDR_DBG_PRELANDED")) b.knobs.v_prelanded = 1;
 #endif
     ProfScope prof("ip_scan_emit", st);
     hipLaunchKernelGGL((k_ip_scan_r3<T, F16, FILT>), dim3(std::min(tiles, (unsigned)device_cu_count())), dim3(T::THREADS), R3_SMEM, st, b);

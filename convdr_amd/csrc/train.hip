@@ -160,21 +160,16 @@ static int cur_device_slot() {
   return dev;
 }
 
-// Timing-only experiments (`make TRACE=1` library only: the results are garbage): CONVDR_DBG_SKIP drops whole classes of
+// Timing-only experiments.  They exist in the `make TRACE=1` library only, host and device alike (trace_knobs.hpp is the one place
+// that defines them: in the product skip_classes() and double_classes() are constexpr zeros and every test of them below folds
+// away).  The results are garbage.  CONVDR_DBG_SKIP (skip_classes()) drops whole classes of
 // launches -- 1 gelu', 2 LayerNorm backward, 4 forward attention, 8 weight gradients, 16 attention backward, 32 bias column sums (zero partials instead), 64 forward
 // LayerNorm, 128 the per-layer gradient-norm partials (zeros instead), 256 the transposed-weight refresh (512: that launch twice) -- to measure what each class costs the STEP (tools/dbg/skip_probe.sh, profiles/r04_train_kd_sensitivity.txt).
-// CONVDR_DBG_DOUBLE (same library; tools/dbg/double_probe.sh): a class of IDEMPOTENT launches goes out twice, results unchanged --
+// CONVDR_DBG_DOUBLE (double_classes(); tools/dbg/double_probe.sh): a class of IDEMPOTENT launches goes out twice, results unchanged --
 // the step's difference is the class's marginal cost with the product's own operands (a skipped class leaves stale operands behind,
 // and the GEMMs' time depends on their operands: profiles/r06_ab_transpose.txt).  1 forward GEMMs, 2 data-gradient GEMMs (both in
 // gemm_launch.hpp), 4 weight gradients, 8 forward attention, 16 attention backward, 32 forward LayerNorm, 64 LayerNorm backward,
 // 128 bias column sums + their reductions (storing backward only), 256 gradient-norm partials.
-#ifdef CONVDR_ENABLE_TRACE
-static int dbg_skip() { static const int v = getenv("CONVDR_DBG_SKIP") ? atoi(getenv("CONVDR_DBG_SKIP")) : 0; return v; }
-static int dbg_double() { static const int v = getenv("CONVDR_DBG_DOUBLE") ? atoi(getenv("CONVDR_DBG_DOUBLE")) : 0; return v; }
-#else
-static constexpr int dbg_skip() { return 0; }
-static constexpr int dbg_double() { return 0; }
-#endif   // convdr_train_set_side_stream (before the first backward of the process)
 
 // convdr_encoder_backward_fresh: every parameter gradient except the embedding tables is STORED by the one kernel that completes it
 // (weight-gradient tiles, k_reduce_multi jobs) instead of added to the buffer's contents; set for the duration of that call only
@@ -336,9 +331,9 @@ static int wgrad_launch(const WgradItem* it, int count, int64_t rows, float* sla
   }
   {
     ProfScope prof("gemm_wgrad", st);
-    if (!(dbg_skip() & 8))
+    if (!(skip_classes() & 8))
       hipLaunchKernelGGL((k_gemm_tn<T>), dim3((unsigned)tiles, (unsigned)nsplit), dim3(T::THREADS), TnCfg<T>::SMEM_BYTES, st, g);
-    if ((dbg_double() & 4) && t_bwd_overwrite)   // (stores or slabs: idempotent)
+    if ((double_classes() & 4) && t_bwd_overwrite)   // (stores or slabs: idempotent)
       hipLaunchKernelGGL((k_gemm_tn<T>), dim3((unsigned)tiles, (unsigned)nsplit), dim3(T::THREADS), TnCfg<T>::SMEM_BYTES, st, g);
     CONVDR_CHECK_LAUNCH("k_gemm_tn");
   }
@@ -383,8 +378,8 @@ static int ln_bwd_kernel(const float* dY, const bf16_t* dYadd, const float* Yin,
                          const DropSite drop = DropSite{0u, 0u, 1.f}, const int32_t* row_map = nullptr) {
   int blocks = (int)(ceil_div64(rows, 4) < LN_BWD_BLOCKS ? ceil_div64(rows, 4) : LN_BWD_BLOCKS);
   ProfScope prof("layernorm_bwd", st);
-  if (!(dbg_skip() & 2))
-  for (int rep = 0; rep < ((dbg_double() & 64) ? 2 : 1); ++rep)
+  if (!(skip_classes() & 2))
+  for (int rep = 0; rep < ((double_classes() & 64) ? 2 : 1); ++rep)
   {
     // g_ln_bwd_rows (option "ln_bwd_rows"): 0 = the general kernel everywhere (A/B), 1 = straight-line form without, 2 (default) = with the
     // register prefetch of the next row.  configs[2] step, medians of three alternations on one box: 9.16 ms (0) -> 8.96 (2),
@@ -541,8 +536,8 @@ extern "C" int convdr_encoder_train_forward(const convdr_encoder_config* cfg, co
                       p.order, max_len <= ATTF_MAX_LEN ? s.Mbits : nullptr, cls_tail ? p.c_ctx32 : nullptr};
       ProfScope prof("attention", st);
       const dim3 grid(cls_tail ? 1 : (max_len + 127) / 128, cfg->heads, B);
-      if (!(dbg_skip() & 4))
-        for (int rep = 0; rep < ((dbg_double() & 8) ? 2 : 1); ++rep) {
+      if (!(skip_classes() & 4))
+        for (int rep = 0; rep < ((double_classes() & 8) ? 2 : 1); ++rep) {
           if (a.drop.thresh) hipLaunchKernelGGL(k_attention_train_fwd<true>, grid, dim3(256), 4 * ATT_TILE, st, a);
           else hipLaunchKernelGGL(k_attention_train_fwd<false>, grid, dim3(256), 4 * ATT_TILE, st, a);
         }
@@ -575,8 +570,8 @@ extern "C" int convdr_encoder_train_forward(const convdr_encoder_config* cfg, co
     g.rows = rows; g.W = (const bf16_t*)lw->wo; g.X = s.ctx; g.N = H; g.K = H; g.bias = lw->bo; g.Cf = s.Y1; g.R = s.Xin;
     g.drop = drop_site(dseed, DROP_SITE_ATTN_OUT, l, p_hid);
     if (int e = launch_gemm<EPI_RESID_F32>(g, st, "gemm_attn_out")) return e;
-    if (!(dbg_skip() & 64))
-      for (int rep = 0; rep < ((dbg_double() & 32) ? 2 : 1); ++rep)
+    if (!(skip_classes() & 64))
+      for (int rep = 0; rep < ((double_classes() & 32) ? 2 : 1); ++rep)
         launch_layernorm_bf16(s.Y1, rows, H, lw->ln1_g, lw->ln1_b, cfg->ln_eps, s.X1, st);
     CONVDR_CHECK_LAUNCH("k_layernorm");
     g = GemmArgs{};
@@ -590,8 +585,8 @@ extern "C" int convdr_encoder_train_forward(const convdr_encoder_config* cfg, co
     g.drop = drop_site(dseed, DROP_SITE_FFN_OUT, l, p_hid);
     if (int e = launch_gemm<EPI_RESID_F32>(g, st, "gemm_ffn2")) return e;
     if (l + 1 < cfg->layers) {
-      if (!(dbg_skip() & 64))
-        for (int rep = 0; rep < ((dbg_double() & 32) ? 2 : 1); ++rep)
+      if (!(skip_classes() & 64))
+        for (int rep = 0; rep < ((double_classes() & 32) ? 2 : 1); ++rep)
           launch_layernorm_bf16(s.Y2, rows, H, lw->ln2_g, lw->ln2_b, cfg->ln_eps, P.layers[l + 1].Xin, st);
       CONVDR_CHECK_LAUNCH("k_layernorm");
     } else if (cfg->pool_mean) {   // use_mean = True: masked mean of the whole last layer's output
@@ -748,7 +743,7 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
       } else {
         if (int e = launch_gemm<EPI_BF16>(g, st, "gemm_dgrad")) return e;
         ProfScope prof("dgelu_colsum", st);
-        if (!(dbg_skip() & 1))
+        if (!(skip_classes() & 1))
           hipLaunchKernelGGL(k_dgelu_colsum, dim3((I + 255) / 256, chunks), dim3(256), 0, st, d.dHpre, s.Hpre, rows, I, d.part_b1);
         CONVDR_CHECK_LAUNCH("k_dgelu_colsum");
       }
@@ -816,8 +811,10 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
       // (D[h, t] = dO . O per head is computed by the dQ kernel for its own queries and handed to the dK / dV kernel
       //  through p.Drow: no separate row-dot pass)
       AttnBwdArgs a{s.QKV, p.dctx, rows, s.LSE, cfg->heads, p.Drow, s.ctx, p.Drow, p.ldt, cu_seqlens, seq_lens, H, d.dQKV, 0.125f,
-                    drop_site(dseed, DROP_SITE_ATT_PROBS, l, p_att), last ? 64 : 0, p.order, s.Mbits, last ? p.c_ctx32 : nullptr,
-                    (l == 5) ? (unsigned long long*)g_attn_trace : nullptr};   // (TRACE builds, layer 5: tools/dbg/attn_bwd_trace.py)
+                    drop_site(dseed, DROP_SITE_ATT_PROBS, l, p_att), last ? 64 : 0, p.order, s.Mbits, last ? p.c_ctx32 : nullptr};
+#ifdef CONVDR_ENABLE_TRACE   // (layer 5: tools/dbg/attn_bwd_trace.py)
+      if (l == 5) a.knobs.v_trace = (unsigned long long*)g_attn_trace;
+#endif
       ProfScope prof("attention_bwd", st);
       if (g_attn_bwd_fused && max_len <= ATTF_MAX_LEN) {   // (last layer: q_limit = 64, one query step)
         static DeviceOnce attr_done;
@@ -827,8 +824,8 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
           CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_attention_bwd_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                ATTB_FUSED_SMEM));
         }
-        if (!(dbg_skip() & 16))
-          for (int rep = 0; rep < ((dbg_double() & 16) ? 2 : 1); ++rep) {
+        if (!(skip_classes() & 16))
+          for (int rep = 0; rep < ((double_classes() & 16) ? 2 : 1); ++rep) {
             if (a.drop.thresh) hipLaunchKernelGGL(k_attention_bwd_fused<true>, dim3(cfg->heads, B), dim3(512), ATTB_FUSED_SMEM, st, a);
             else hipLaunchKernelGGL(k_attention_bwd_fused<false>, dim3(cfg->heads, B), dim3(512), ATTB_FUSED_SMEM, st, a);
           }
@@ -841,8 +838,8 @@ static int encoder_backward(const convdr_encoder_config* cfg, const convdr_encod
     }
     // ---- the layer's weight-gradient branch: every operand is complete now; it runs beside the layers below ----
     if (int e = wf.fork()) return e;
-    for (int rep = 0; rep < ((dbg_double() & 128) && t_bwd_overwrite ? 2 : 1); ++rep) {
-      if (dbg_skip() & 32) {   // (timing bound only: zero partials instead of the column sums)
+    for (int rep = 0; rep < ((double_classes() & 128) && t_bwd_overwrite ? 2 : 1); ++rep) {
+      if (skip_classes() & 32) {   // (timing bound only: zero partials instead of the column sums)
         CONVDR_CHECK_HIP(hipMemsetAsync(d.part_bqkv, 0, sizeof(float) * (size_t)chunks * 3 * H, ss));
         if (!last && g_gelu_gp) CONVDR_CHECK_HIP(hipMemsetAsync(d.part_b1, 0, sizeof(float) * (size_t)chunks * I, ss));
       } else {
@@ -1016,9 +1013,9 @@ extern "C" int convdr_grad_norm_clip(float* grads, int64_t n, float max_norm, fl
 
 extern "C" int convdr_grad_sumsq(const float* x, int64_t n, float* partials, int nblocks, convdr_stream_t stream) {
   CONVDR_REQUIRE(n >= 0 && nblocks >= 1 && nblocks <= 1024, "convdr_grad_sumsq: bad n / nblocks (%lld, %d)", (long long)n, nblocks);
-  if (dbg_skip() & 128) CONVDR_CHECK_HIP(hipMemsetAsync(partials, 0, sizeof(float) * (size_t)nblocks, (hipStream_t)stream));   // (timing bound only)
+  if (skip_classes() & 128) CONVDR_CHECK_HIP(hipMemsetAsync(partials, 0, sizeof(float) * (size_t)nblocks, (hipStream_t)stream));   // (timing bound only)
   else
-    for (int rep = 0; rep < ((dbg_double() & 256) ? 2 : 1); ++rep)
+    for (int rep = 0; rep < ((double_classes() & 256) ? 2 : 1); ++rep)
       hipLaunchKernelGGL(k_sumsq_partial, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, x, n, partials);
   CONVDR_CHECK_LAUNCH("k_sumsq_partial");
   return 0;
@@ -1085,8 +1082,8 @@ static int pack_transposed(const void* base, bool src_bf16, int count, const int
       q.tile_end = tiles;
     }
     if (tiles == 0) continue;
-    if (dbg_skip() & 256) continue;   // (timing bound only: the data-gradient GEMMs then run on stale transposed weights)
-    for (int rep = 0; rep < ((dbg_skip() & 512) ? 2 : 1); ++rep) {   // (512, timing only: the launch twice -- what one more of it costs the step)
+    if (skip_classes() & 256) continue;   // (timing bound only: the data-gradient GEMMs then run on stale transposed weights)
+    for (int rep = 0; rep < ((skip_classes() & 512) ? 2 : 1); ++rep) {   // (512, timing only: the launch twice -- what one more of it costs the step)
       if (src_bf16) hipLaunchKernelGGL(k_transpose_bf16_batch<true>, dim3((unsigned)tiles), dim3(256), 0, stream, a);
       else hipLaunchKernelGGL(k_transpose_bf16_batch<false>, dim3((unsigned)tiles), dim3(256), 0, stream, a);
     }

@@ -55,7 +55,7 @@ def bf16_round(t):
 
 
 def gelu_tail_fit(x):
-    """The GELU the FFN1 epilogue evaluates (csrc/encoder_kernels.hpp:gelu_tail): x Phi(x) = max(x, 0) - t Q(t), t = min(|x|, 9),
+    """The GELU the FFN1 epilogue evaluates (csrc/gemm_kernel.hpp:gelu_tail): x Phi(x) = max(x, 0) - t Q(t), t = min(|x|, 9),
     Q(t) = 0.5 exp2(-(c1 t + .. + c4 t^4)); max |error| vs the erf form 8.8e-6 (tests/test_gelu_fit_cpu.py).  Used by the
     bf16-emulating mode so that the value rounded to bf16 is the one the kernel rounds."""
     t = x.abs().clamp(max=9.0)
@@ -67,7 +67,7 @@ def gelu_tail_fit(x):
 
 
 def _attention_bf16(q, k, v, lens, scale, drop_mask):
-    """The attention kernels' arithmetic (csrc/encoder_kernels.hpp:k_attention_fwd, attention_train.hpp): keys in tiles of 64
+    """The attention kernels' arithmetic (csrc/attention_fwd.hpp:k_attention_fwd, attention_train.hpp): keys in tiles of 64
     from the start of the sequence, online softmax in fp32 (base 2), the UNNORMALISED probabilities of a tile rounded to
     bf16 (after dropout) for the P V product, fp32 accumulators rescaled per tile, one division at the end.
     q, k, v [B, h, L, d] (bf16-valued); lens [B]; drop_mask [B, h, L, L] or None."""

@@ -325,7 +325,7 @@ def make_head(H, E, seed=17):
 
 # ---- workspace decoders ----------------------------------------------------------------------------------------------
 def blocked_index(rows, N):
-    """Element offsets of a [rows, N] matrix in the blocked layout (csrc/encoder_kernels.hpp:hm_blocked_offset)."""
+    """Element offsets of a [rows, N] matrix in the blocked layout (csrc/gemm_kernel.hpp:hm_blocked_offset)."""
     t = torch.arange(rows)[:, None]
     f = torch.arange(N)[None, :]
     return ((t >> 5) * (N >> 3) + (f >> 3)) * 256 + (t & 31) * 8 + (f & 7)

@@ -1,4 +1,4 @@
-"""The one-transcendental GELU of the FFN1 epilogue (convdr_amd/csrc/encoder_kernels.hpp: gelu_tail) against the exact erf
+"""The one-transcendental GELU of the FFN1 epilogue (convdr_amd/csrc/gemm_kernel.hpp: gelu_tail) against the exact erf
 form the reference uses (transformers 2.3.0 modeling_bert.gelu, reached from /root/reference/model/models.py:141).
 Same constants, same operation order in fp32 (fused multiply-adds emulated in fp64), all of the activation range."""
 import numpy as np
@@ -32,7 +32,7 @@ def test_gelu_fit_is_within_1e5_of_exact_erf_gelu():
 
 
 def gelu_grad_fp32(x):
-    """encoder_kernels.hpp: gelu_grad (same constants and operation order)."""
+    """gemm_kernel.hpp: gelu_grad (same constants and operation order)."""
     x = x.astype(F)
     t = np.minimum(np.abs(x), F(9.0))
     p = _fma(t, F(0.0041585), F(-0.04571999))
@@ -54,7 +54,7 @@ def test_gelu_grad_fit_is_within_1e4_of_exact_derivative():
 
 
 def gelu_and_grad_shared_tail_fp32(x):
-    """encoder_kernels.hpp: gelu_tail2_gp (EPI_GELU_GP, round 5) -- gelu(x) and gelu'(x) from ONE evaluation of Q(|x|):
+    """gemm_kernel.hpp: gelu_tail2_gp (EPI_GELU_GP, round 5) -- gelu(x) and gelu'(x) from ONE evaluation of Q(|x|):
     gelu' = 0.5 + copysign(0.5 + q m(t), x), m = quartic fit of t phi(t) / Q(t) - 1 against the fitted q."""
     x = x.astype(F)
     t = np.minimum(np.abs(x), F(9.0))

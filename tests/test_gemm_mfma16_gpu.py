@@ -1,5 +1,5 @@
 """The 16x16x32 MFMA main loop of the inference forward's 256 x 256 QKV and FFN1 tiles (k_gemm<EPI_QKV / EPI_GELU_BLK, Tile256, 1>:
-csrc/gemm_nt.hpp gemm_nt_mainloop_r3_m16, the blocked and V-third epilogues of csrc/encoder_kernels.hpp) against the stage
+csrc/gemm_nt.hpp gemm_nt_mainloop_r3_m16, the blocked and V-third epilogues of csrc/gemm_kernel.hpp) against the stage
 references of tests/encoder_stages.py, every live token.
 
 Options of every case: fused_ln_min_rows 1, fused_ln_max_k 2^20, gemm_tile_policy 1, hm_blocked 1 -- Q / K / ctx blocked and

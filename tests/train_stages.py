@@ -144,7 +144,7 @@ def gelu_grad_exact(x):
 
 
 def gelu_grad_fit(x):
-    """gelu_grad of csrc/encoder_kernels.hpp (the tail fit's Q(t) and x phi(x)) in x's dtype."""
+    """gelu_grad of csrc/gemm_kernel.hpp (the tail fit's Q(t) and x phi(x)) in x's dtype."""
     t = x.abs().clamp(max=9.0)
     p = ((t * 0.0041585 - 0.04571999) * t - 0.46495319) * t - 1.14955714
     q = torch.exp2(p * t - 1.0)

@@ -1,22 +1,28 @@
-import re,sys
+# Which device functions of two trees are instruction-identical?
+#   python tools/dbg/isa_identity.py OLD_DIR NEW_DIR [--rename OLD=NEW ...] unit [unit ...]
+# OLD_DIR / NEW_DIR hold unit.s, the device assembly of both trees (hipcc with the Makefile's flags plus -S --cuda-device-only).
+# Per unit: the number of device functions before / after, then one 'removed' / 'DIFF' / 'added' line for every function that is
+# not instruction-identical (labels and comments stripped).  --rename OLD=NEW (repeatable, applied in order to the OLD tree's text
+# only) gives a kernel that was renamed between the trees the name it has in the new one; without it such a kernel shows as a
+# 'removed' / 'added' pair.
+import argparse,re
 def funcs(path, ren):
     s=open(path).read()
     s=re.sub(r'__hip_cuid_[0-9a-f]+','__hip_cuid_X',s)
     for a,b in ren: s=s.replace(a,b)
-    s=re.sub(r'(k_gemmILi\d+ENS_7TileCfgILi\d+ELi\d+ELi\d+ELi\d+EEE)Li0E',r'\1',s)   # k_gemm<EPI, T, 0> is k_gemm<EPI, T> of before the MFMA shape parameter
     d={}
     for m in re.finditer(r'^(_Z\w+):.*?\n(.*?)^\.Lfunc_end\d+:', s, re.S|re.M):
         body=re.sub(r'\.L(BB|tmp|func_begin|func_end)\d+(_\d+)?','.L',m.group(2))
         body=re.sub(r'[ \t]*;.*','',body)   # (and the padding in front of a comment: it follows the label's width)
         d[m.group(1)]=body
     return d
-# renames, applied in order to the FIRST (older) tree only: its name -> the name the kernel has in the second tree
-ren=[('k_attention_fwdILb0ELb0ELb0ELb0EE','k_attention_fwdILb0ELb0ELb0EE'),('k_attention_fwdILb0ELb0ELb1ELb1EE','k_attention_fwdILb0ELb1ELb1EE'),
-     ('k_attention_fwdILb1ELb0ELb0ELb0EE','k_attention_fwdILb1ELb0ELb0EE'),('k_attention_fwdILb1ELb0ELb0ELb1EE','k_attention_fwdILb1ELb0ELb1EE'),
-     ('15k_gemm_resid_lnE','24k_gemm_resid_ln_32x32x16E'),   # the retired 32x32x16 kernel steps aside (it shows as removed) ...
-     ('19k_gemm_resid_ln_m16E','15k_gemm_resid_lnE')]        # ... for the 16x16x32 kernel that took its name
-for f in sys.argv[3:]:
-    a=funcs('%s/%s.s'%(sys.argv[1],f),ren); b=funcs('%s/%s.s'%(sys.argv[2],f),[])
+ap=argparse.ArgumentParser()
+ap.add_argument('old_dir'); ap.add_argument('new_dir'); ap.add_argument('units',nargs='+')
+ap.add_argument('--rename',action='append',default=[],metavar='OLD=NEW',help='substring of a mangled name in the OLD tree -> its name in the new tree')
+args=ap.parse_args()
+ren=[tuple(r.split('=',1)) for r in args.rename]
+for f in args.units:
+    a=funcs('%s/%s.s'%(args.old_dir,f),ren); b=funcs('%s/%s.s'%(args.new_dir,f),[])
     print(f,len(a),len(b))
     for k in a:
         if k not in b: print('  removed',k)

@@ -63,7 +63,7 @@ __device__ __forceinline__ void issue(const Src& s, int kt, char* lds_tile, int 
   }
 }
 
-__device__ __forceinline__ void gelu2(float& x0, float& x1) {   // csrc/encoder_kernels.hpp:gelu_tail2
+__device__ __forceinline__ void gelu2(float& x0, float& x1) {   // csrc/gemm_kernel.hpp:gelu_tail2
   f32x2_t t, r;
   float a, b;
   const float nine = 9.f;
