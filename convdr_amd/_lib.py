@@ -37,6 +37,16 @@ _SIGNATURES = {
     "convdr_ip_search_filtered": (C.c_int, [C.c_int, C.c_int, _p, C.c_int, _p, _p, _p, C.c_float, C.c_int, C.c_int64, C.c_int,
                                             C.c_int, _p, _p, C.c_int, C.c_int, _p, C.c_size_t, _p, C.c_int64, C.c_int64, _p, _p,
                                             _p, _p, _p]),
+    # the 8-bit store (storage="sq8")
+    "convdr_ip_column_absdev": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, _p, _p]),
+    "convdr_ip_store_rows_q8": (C.c_int, [_p, C.c_int64, C.c_int, _p, _p, _p, _p, _p, _p, _p]),
+    "convdr_ip_search_q8": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, _p,
+                                      C.c_size_t, _p, _p, _p, _p, _p]),
+    "convdr_ip_search_deep_q8": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_int, C.c_int, _p, _p, C.c_int, C.c_int, _p,
+                                           C.c_size_t, _p, _p, _p, _p, _p]),
+    "convdr_ip_search_filtered_q8": (C.c_int, [C.c_int, _p, C.c_int, _p, _p, _p, C.c_int64, C.c_int, C.c_int, _p, _p, C.c_int,
+                                               C.c_int, _p, C.c_size_t, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p]),
+    "convdr_ip_score_rows_q8": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, C.c_int, _p, C.c_int, C.c_int64, _p, _p, _p]),
     "convdr_ip_range_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "convdr_ip_range_search": (C.c_int, [C.c_int, _p, C.c_int, _p, _p, C.c_float, _p, C.c_int64, C.c_int, _p, _p, C.c_int, C.c_int,
                                          _p, C.c_int64, _p, C.c_size_t, _p, _p, _p, _p]),

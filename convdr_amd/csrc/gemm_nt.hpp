@@ -97,6 +97,19 @@ __device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8& a, const bf16x8& b
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// The same K step on int8 operands (the 8-bit passage store's scan, ip_scan_q8.hpp): the LDS image and the fragment read do
+// not change -- a lane's 16 bytes are sixteen int8 instead of eight 16-bit words, so one 128-byte K step holds 128 elements and
+// the four sub-steps are v_mfma_i32_32x32x32_i8.  Which k a byte stands for inside the instruction does not matter to a dot
+// product: both operands are read by the same bytes per lane.  Selected by the accumulator's type (GemmAccI8 below); the
+// callers pass rows of d int8 as rows of d / 2 16-bit words.
+typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+template <bool F16>
+__device__ __forceinline__ i32x16 mfma_32x32x16(const bf16x8& a, const bf16x8& b, const i32x16& c) {
+  static_assert(!F16, "the integer K step has one operand type");
+  return __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b), c, 0, 0, 0);
+}
+
 template <int WR_, int WL_, int MT_, int NT_>
 struct TileCfg {
   static constexpr int WR = WR_, WL = WL_, MT = MT_, NT = NT_;
@@ -140,6 +153,19 @@ struct GemmAcc {
       for (int j = 0; j < T::NT; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) c[i][j][r] = 0.f;
+  }
+};
+
+template <class T>
+struct GemmAccI8 {   // int32 accumulators of the int8 K step, same element map as GemmAcc
+  i32x16 c[T::MT][T::NT];
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int i = 0; i < T::MT; ++i)
+#pragma unroll
+      for (int j = 0; j < T::NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) c[i][j][r] = 0;
   }
 };
 
@@ -359,8 +385,8 @@ __device__ __forceinline__ void gemm_r3_prologue(const TileSrcAll<T>& src, int K
 // Returns the slot state for the NEXT tile: once a wave is back from this call, the R slots `rs`, rs + 1 and the L slot
 // `ls` of the returned state are free (the last step read the other ones), so the next tile's prologue may be issued
 // at once -- under this tile's epilogue (prologue_in_flight on the next call).
-template <class T, bool F16 = false, int R_AUX = 0>
-__device__ __forceinline__ R3Slots gemm_nt_mainloop_r3(const TileSrcAll<T>& src, int K, char* smem, GemmAcc<T>& acc,
+template <class T, bool F16 = false, int R_AUX = 0, class ACC = GemmAcc<T>>   // ACC: GemmAcc<T>, or GemmAccI8<T> (int8 operands)
+__device__ __forceinline__ R3Slots gemm_nt_mainloop_r3(const TileSrcAll<T>& src, int K, char* smem, ACC& acc,
                                                        const WavePos<T>& w, R3Slots st = R3Slots{0, 0},
                                                        bool prologue_in_flight = false, bool r1_deferred = false,
                                                        bool stage0_landed = false, unsigned long long* step_trace = nullptr) {

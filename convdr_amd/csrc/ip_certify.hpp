@@ -27,12 +27,14 @@ struct IpBand {
   float p_scale;             // power of two of the fp16 operand; 1 for bf16
   float norm_limit;          // IP_F16_NORM_LIMIT, or +inf for bf16
   float norm_floor;          // IP_BF16_NORM_FLOOR, or 0 for fp16 (whose operands are rescaled)
+  float q8_coef = 0.f;       // 8-bit store: IP_Q8_COEF, and then qnorm holds A(q) and p_max_norm the largest row L1 norm of the codes
 
   // the largest passage norm in scan units
   __device__ __forceinline__ float pm() const { return p_max_norm[0] * p_scale; }
   // (scaled units for the fp16 scan: qnorm is the scaled query norm, pm the scaled largest passage norm)
   __device__ __forceinline__ float eps(int q) const {
     const float qn = qnorm[q], pmax = pm();
+    if (q8_coef > 0.f) return (q8_coef * pmax + qn) * 1.001f + 1e-30f;   // (1/2 + r) max ||c||_1 + A(q): derivation at IP_Q8_COEF
     return (eps_coef * qn * pmax + eps_abs * (qn + pmax) + eps_abs * eps_abs) * 1.001f + 1e-30f;
   }
   // fp16 scan copy built with a scale too large for this block's norms -- or a query so long that its per-row power-of-two
@@ -92,9 +94,33 @@ __device__ __forceinline__ int ip_list_verdict(uint32_t cnt, int cap, uint32_t b
 // commutes with a power-of-two factor (|q| < 2^128, |2^s v| < 2^16, and the smallest non-zero product, 2^-149 2^-24 =
 // 2^-173, is 849 binades above the fp64 subnormals: nothing overflows or loses bits to underflow), so the sum is 2^s times the
 // oracle's sum bit for bit, and ONE multiplication by 2^-s after the butterfly (`unscale`, exact) gives the oracle's value.
-struct f64x4 { double x, y, z, w; };
+// The 8-bit store's rows (PT = int8_t) are not a pointer but codes, centre and step: element j of a row is the fp32 value
+// v_j = fl(centre_j + fl(step_j c_j)) -- one rounded multiplication, one rounded addition, no contraction --, which widens to
+// double exactly.  A lane reads its 4 codes as one 4-byte load; the lane / (j, c) / butterfly order is unchanged.
+struct IpQ8Rows { const int8_t* codes; const float* centre; const float* step; };
+template <class PT> struct IpRows { typedef const PT* type; };       // what a kernel that reads rows of PT takes for them
+template <> struct IpRows<int8_t> { typedef IpQ8Rows type; };
 template <class PT>
-__device__ __forceinline__ f64x4 ip_load4_f64(const PT* p) {
+__device__ __forceinline__ const PT* ip_row_at(const PT* P, int64_t row, int d) { return P + row * d; }
+__device__ __forceinline__ IpQ8Rows ip_row_at(IpQ8Rows P, int64_t row, int d) { P.codes += row * d; return P; }
+
+struct f64x4 { double x, y, z, w; };
+__device__ __forceinline__ f64x4 ip_load4_f64(const IpQ8Rows& p, int e) {
+  const uint32_t raw = *(const uint32_t*)(p.codes + e);
+  const float4 c = *(const float4*)(p.centre + e);
+  const float4 s = *(const float4*)(p.step + e);
+  // (HIP's __fmul_rn / __fadd_rn are the plain operators, which hipcc contracts into ONE fma with a single rounding: the
+  //  product goes through an opaque register, so that it is rounded to fp32 before the addition sees it)
+  auto v = [](float ce, float st, uint32_t byte) {
+    float m = st * (float)(int)(int8_t)byte;
+    asm volatile("" : "+v"(m));
+    return (double)(ce + m);
+  };
+  return {v(c.x, s.x, raw & 255u), v(c.y, s.y, (raw >> 8) & 255u), v(c.z, s.z, (raw >> 16) & 255u), v(c.w, s.w, raw >> 24)};
+}
+template <class PT>
+__device__ __forceinline__ f64x4 ip_load4_f64(const PT* p, int e) {
+  p += e;
   if constexpr (sizeof(PT) == 2) {
     typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
     const uint2 raw = *(const uint2*)p;
@@ -110,12 +136,12 @@ __device__ __forceinline__ f64x4 ip_load4_f64(const PT* p) {
 // device implementation of the order above, and its one multiplication by `unscale` for the half store.  Every re-score
 // calls it: k_ip_rescore, k_ip_finish, k_ip_score_rows and k_ip_score_docs (ip_docs.hpp).  The call is wave-uniform.
 template <class PT>
-__device__ __forceinline__ double ip_row_score(const float* __restrict__ qv, const PT* __restrict__ pv, int d, int lane,
+__device__ __forceinline__ double ip_row_score(const float* __restrict__ qv, typename IpRows<PT>::type pv, int d, int lane,
                                                double unscale) {
   double acc = 0.0;
   for (int e = lane * 4; e < d; e += 256) {
     const float4 x = *(const float4*)(qv + e);
-    const f64x4 y = ip_load4_f64<PT>(pv + e);
+    const f64x4 y = ip_load4_f64(pv, e);
     acc = fma((double)x.x, y.x, acc);
     acc = fma((double)x.y, y.y, acc);
     acc = fma((double)x.z, y.z, acc);
@@ -123,7 +149,7 @@ __device__ __forceinline__ double ip_row_score(const float* __restrict__ qv, con
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if constexpr (sizeof(PT) == 2) acc *= unscale;
+  if constexpr (sizeof(PT) == 2) acc *= unscale;   // (the half store only: no other row type is scaled)
   return acc;
 }
 

@@ -300,8 +300,8 @@ static int ip_search_deep(const char* name, const IpBlock& b, const IpTopkArgs& 
       const int64_t row0 = (int64_t)g * p.nPt / p.nSeg * p.tr;
       const int64_t rows = std::min<int64_t>((int64_t)p.segTiles * p.tr, n - row0);
       ScanArgs a = emit;
-      a.P = emit.P + row0 * b.d;
-      if (emit.Plo) a.Plo = emit.Plo + row0 * b.d;
+      a.P = emit.P + row0 * emit.d;             // (emit.d: the row's 16-bit words -- b.d, or b.d / 2 for rows of int8 codes)
+      if (emit.Plo) a.Plo = emit.Plo + row0 * emit.d;
       if (emit.bits) a.bits = emit.bits + row0 / 32;   // (row0 is a multiple of the tile height: whole words)
       a.n = rows;
       a.nPt = (int)ceil_div64(rows, p.tr);   // = segTiles: only the block's last tile is ragged

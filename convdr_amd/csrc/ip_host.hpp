@@ -6,7 +6,8 @@ namespace convdr {
 
 // ---- the block a call searches (fields in the order of the entries' arguments: they initialise it positionally) ----------
 struct IpBlock {
-  int store;                  // 0: bf16 scan copy, 1: fp16 scan copy, 2: half store (the halves are corpus and scan operand)
+  int store;                  // 0: bf16 scan copy, 1: fp16 scan copy, 2: half store (the halves are corpus and scan operand),
+                              // 3: 8-bit store (p_half: rows of d int8 codes, corpus and scan operand; q8_centre, q8_step)
   const float* p_f32;         // [n, d] fp32 rows the re-score reads; not read for the half store
   const void* p_half;         // [n, d] 16-bit scan operand; the half store: the stored rows 2^s v
   const void* p_half_lo;      // [n, d] remainder copy (the three-pass split scan), or NULL
@@ -18,19 +19,27 @@ struct IpBlock {
   const uint32_t* row_bits;   // row filter (NULL: every row), one bit per row, whole 256-row tiles
   int64_t row_bits_words;     // words the caller says the bitmap holds (checked against n, then not read)
   int64_t n_allowed;          // set bits among rows 0..n-1 (top-k only; read only with row_bits)
+  const float* q8_centre = nullptr;   // 8-bit store: [d] each; p_max_norm is then the largest row L1 norm of the codes
+  const float* q8_step = nullptr;
 
-  int kind() const { return store == 0 ? IP_KIND_BF16 : IP_KIND_F16; }
+  int kind() const { return store == 3 ? IP_KIND_I8 : (store == 0 ? IP_KIND_BF16 : IP_KIND_F16); }
+  bool rows_q8() const { return store == 3; }                             // the re-score reads codes, centre and step
+  IpQ8Rows q8_rows() const { return {(const int8_t*)p_half, q8_centre, q8_step}; }
   bool rows_f16() const { return store == 2; }                            // the re-score reads p_half
   bool split() const { return p_half_lo != nullptr || two_pass; }         // the query's remainder is an operand: the tighter band
   float scan_scale() const { return kind() == IP_KIND_F16 ? p_scale : 1.f; }   // units of the scan scores and thresholds
-  float norm_limit() const { return kind() == IP_KIND_F16 ? IP_F16_NORM_LIMIT : INFINITY; }   // above it: CONVDR_IP_RANGE
+  float norm_limit() const { return kind() == IP_KIND_F16 ? IP_F16_NORM_LIMIT : (kind() == IP_KIND_I8 ? FLT_MAX : INFINITY); }   // above it: CONVDR_IP_RANGE
   float norm_floor() const { return kind() == IP_KIND_BF16 ? IP_BF16_NORM_FLOOR : 0.f; }       // non-zero and below it: CONVDR_IP_RANGE
   double unscale() const { return rows_f16() ? 1.0 / (double)p_scale : 1.0; }  // one factor on the fp64 sum over scaled rows
   int64_t n_need() const { return row_bits ? n_allowed : n; }   // TOP-K ONLY (range search sets no n_allowed): need = min(k, n_need)
   float eps_coef() const { return ip_eps_coef(d, split(), kind()); }
   float eps_abs() const { return ip_eps_abs(d, split(), kind()); }
   // the error band of this block's scan scores for queries whose norms are at qnorm (device, [nq]): what every finishing kernel takes
-  IpBand band(const float* qnorm) const { return {qnorm, p_max_norm, eps_coef(), eps_abs(), scan_scale(), norm_limit(), norm_floor()}; }
+  // (8-bit store: qnorm holds A(q), +inf for a query out of range, and the coefficient of the L1 norm replaces the other two)
+  IpBand band(const float* qnorm) const {
+    if (rows_q8()) return {qnorm, p_max_norm, 0.f, 0.f, 1.f, norm_limit(), 0.f, IP_Q8_COEF};
+    return {qnorm, p_max_norm, eps_coef(), eps_abs(), scan_scale(), norm_limit(), norm_floor()};
+  }
 };
 
 // per-call arguments of the seven top-k entries, in the entries' order
@@ -71,6 +80,11 @@ static bool ip_pow2_scale_ok(float s) {   // a finite power of two
 // The block's own arguments.  Scale: 1 for the bf16 copy (the entries pass it); the half store's copy is 2^s v with s >= 0.
 // Bitmap: one that is there -- whether it may be absent is the entry's rule (filtered top-k: no; range search: NULL, 0).
 static int ip_check_block(const char* name, const IpBlock& b) {
+  CONVDR_REQUIRE(b.store != 3 || (b.d % 128 == 0 && b.d <= IP_Q8_MAX_D),
+                 "%s: the 8-bit store needs d %% 128 == 0 and d <= %d (got %d): one K step is 128 codes, and the integer scan's "
+                 "range is proven up to that width", name, IP_Q8_MAX_D, b.d);
+  CONVDR_REQUIRE(b.store != 3 || b.n == 0 || (b.p_half && b.q8_centre && b.q8_step && b.p_max_norm),
+                 "%s: a NULL block pointer (codes, centre, step, max_l1)", name);
   CONVDR_REQUIRE(ip_pow2_scale_ok(b.p_scale) && (b.store != 2 || b.p_scale >= 1.f), "%s: p_scale must be a power of two%s (got %g)",
                  name, b.store == 2 ? " >= 1" : "", (double)b.p_scale);
   if (!b.row_bits) return 0;
@@ -169,6 +183,12 @@ static int ip_prepare_queries(const IpBlock& b, const IpPlanHead& p, char* ws, c
   float* qnorm = (float*)(ws + p.o_qnorm);
   uint32_t* counts = (uint32_t*)(ws + p.o_counts);
   const int64_t n_count = (int64_t)p.nq_pad * IP_COUNT_STRIDE * counter_sets;
+  if (b.kind() == IP_KIND_I8) {   // hi / lo int8 operands, interleaved, in the place of qb (2 nq_pad rows of d bytes); A(q) for the norm
+    hipLaunchKernelGGL(k_q8_queries, dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, b.d, b.q8_centre, b.q8_step,
+                       (int8_t*)qb, qnorm, (int64_t)p.nq_pad, counts, n_count);
+    CONVDR_CHECK_LAUNCH("k_q8_queries");
+    return 0;
+  }
   if (b.kind() == IP_KIND_F16)
     hipLaunchKernelGGL((k_rows_to_half<IP_KIND_F16, true>), dim3((p.nq_pad + 3) / 4), dim3(256), 0, st, q_f32, (int64_t)nq, b.d,
                        (const float*)nullptr, 1.f, qb, qlo, qnorm, (float*)nullptr, (int64_t)p.nq_pad, counts, n_count);
@@ -203,6 +223,9 @@ static ScanArgs ip_scan_args(const IpBlock& b, const IpPlanHead& p, char* ws, in
   a.T = T;                                                                      // the sample's scores (the sampling scans)
   a.two_pass = b.two_pass ? 1 : 0;
   a.bits = b.row_bits;
+  if (b.kind() == IP_KIND_I8) {   // rows of d int8 are rows of d / 2 16-bit words to the staging; query tiles of 128 (ip_scan_q8.hpp)
+    a.d = b.d / 2;  a.nQt = (nq + 127) / 128;  a.Plo = nullptr;  a.Qlo = nullptr;  a.two_pass = 0;
+  }
   return a;
 }
 
@@ -210,7 +233,9 @@ static ScanArgs ip_scan_args(const IpBlock& b, const IpPlanHead& p, char* ws, in
 // over the scaled rows is multiplied by 1 / p_scale once.  waves: the grid's second dimension, the caller's choice.
 static int ip_rescore(const IpBlock& b, const float* q_f32, int nq, int waves, int cap, const uint32_t* m, const uint32_t* ids,
                       double* x, hipStream_t st) {
-  if (b.rows_f16())
+  if (b.rows_q8())
+    hipLaunchKernelGGL(k_ip_rescore<int8_t>, dim3(nq, waves), dim3(256), 0, st, q_f32, b.q8_rows(), b.d, cap, m, ids, x, b.unscale());
+  else if (b.rows_f16())
     hipLaunchKernelGGL(k_ip_rescore<_Float16>, dim3(nq, waves), dim3(256), 0, st, q_f32, (const _Float16*)b.p_half, b.d, cap, m, ids,
                        x, b.unscale());
   else
@@ -283,10 +308,15 @@ static int ip_search(const char* name, const IpBlock& b, const IpTopkArgs& c, co
     CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_select, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 12));
     CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
     CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
+    CONVDR_CHECK_HIP(hipFuncSetAttribute((const void*)k_ip_finish<int8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16));
   }
   if (g_ip_fused_finish && n > 0) {
     ProfScope prof("ip_finish", st);
-    if (b.rows_f16())
+    if (b.rows_q8())
+      hipLaunchKernelGGL(k_ip_finish<int8_t>, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
+                         cand_id, cand_s, tau, b.band(qnorm), c.q_f32, b.q8_rows(), b.d, band_m, c.status, c.tau_retry, c.D, c.I,
+                         b.unscale());
+    else if (b.rows_f16())
       hipLaunchKernelGGL(k_ip_finish<_Float16>, dim3(nq), dim3(IP_SELECT_THREADS), (size_t)cap * 16, st, b.n_need(), k, cap, counts, counts_packed,
                          cand_id, cand_s, tau, b.band(qnorm), c.q_f32, (const _Float16*)b.p_half, b.d, band_m, c.status, c.tau_retry,
                          c.D, c.I, b.unscale());

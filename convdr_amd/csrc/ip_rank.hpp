@@ -26,7 +26,7 @@ constexpr int IP_RANK_THREADS = 1024;
 // pitch ld; the query of pair (q, j) is row q of Q.
 // An id outside [0, n) yields the score FAISS pads with and P is not touched for it.
 template <class PT>
-__global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__ Q, const PT* __restrict__ P, int64_t n, int d,
+__global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__ Q, typename IpRows<PT>::type P, int64_t n, int d,
                                                        const int64_t* __restrict__ rows, int m, int64_t ld,
                                                        double* __restrict__ X, float* __restrict__ D, double unscale) {
   const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) k_ip_score_rows(const float* __restrict__
   for (int j = blockIdx.y * 4 + wave; j < m; j += gridDim.y * 4) {
     const int64_t id = rows[(int64_t)q * ld + j];
     double acc = -(double)FLT_MAX;
-    if (id >= 0 && id < n) acc = ip_row_score<PT>(qv, P + id * d, d, lane, unscale);        // (wave-uniform)
+    if (id >= 0 && id < n) acc = ip_row_score<PT>(qv, ip_row_at(P, id, d), d, lane, unscale);        // (wave-uniform)
     if (lane == 0) {
       if (X) X[(int64_t)q * ld + j] = acc;
       if (D) D[(int64_t)q * ld + j] = (float)acc;
@@ -184,7 +184,10 @@ static IpRankPlan ip_rank_plan(int np, int64_t n, int d, int cap) {
 static int ip_score_rows_launch(const IpBlock& b, const float* q_f32, int nq, const int64_t* rows, int m, int64_t ld, double* X,
                                 float* D, hipStream_t st) {
   const int chunks = m < 4 ? 1 : (m / 4 < 1024 ? m / 4 : 1024);
-  if (b.rows_f16())
+  if (b.rows_q8())
+    hipLaunchKernelGGL(k_ip_score_rows<int8_t>, dim3(nq, chunks), dim3(256), 0, st, q_f32, b.q8_rows(), b.n, b.d, rows, m, ld, X, D,
+                       b.unscale());
+  else if (b.rows_f16())
     hipLaunchKernelGGL(k_ip_score_rows<_Float16>, dim3(nq, chunks), dim3(256), 0, st, q_f32, (const _Float16*)b.p_half, b.n, b.d, rows,
                        m, ld, X, D, b.unscale());
   else

@@ -661,7 +661,10 @@ static int launch_scan_f(const ScanArgs& a, int tile, int kind, hipStream_t st) 
   return kind == IP_KIND_F16 ? launch_scan_k<MODE, true, FILT>(a, tile, st) : launch_scan_k<MODE, false, FILT>(a, tile, st);
 }
 template <int MODE>
+static int launch_scan_q8(const ScanArgs& a, hipStream_t st);   // the 8-bit store's integer scan (ip_scan_q8.hpp)
+template <int MODE>
 static int launch_scan(const ScanArgs& a, int tile, int kind, hipStream_t st) {   // a.bits selects the filtered kernels
+  if (kind == IP_KIND_I8) return launch_scan_q8<MODE>(a, st);
   return a.bits ? launch_scan_f<MODE, true>(a, tile, kind, st) : launch_scan_f<MODE, false>(a, tile, kind, st);
 }
 

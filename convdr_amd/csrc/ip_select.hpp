@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(1024) k_ip_cut(int64_t n, int k, int cap, cons
 
 // exact rescoring of a band in global memory: one wave per candidate, the canonical fp64 score (ip_row_score)
 template <class PT>
-__global__ void __launch_bounds__(256) k_ip_rescore(const float* __restrict__ Q, const PT* __restrict__ P, int d,
+__global__ void __launch_bounds__(256) k_ip_rescore(const float* __restrict__ Q, typename IpRows<PT>::type P, int d,
                                                     int cap, const uint32_t* __restrict__ m_in,
                                                     const uint32_t* __restrict__ cand_id,
                                                     double* __restrict__ cand_x, double unscale) {
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(256) k_ip_rescore(const float* __restrict__ Q,
   const float* qv = Q + (int64_t)q * d;
   for (uint32_t slot = blockIdx.y * 4 + wave; slot < c; slot += gridDim.y * 4) {
     const uint32_t id = cand_id[(int64_t)q * cap + slot];
-    const double acc = ip_row_score<PT>(qv, P + (int64_t)id * d, d, lane, unscale);
+    const double acc = ip_row_score<PT>(qv, ip_row_at(P, (int64_t)id, d), d, lane, unscale);
     if (lane == 0) cand_x[(int64_t)q * cap + slot] = acc;
   }
 }
@@ -231,7 +231,7 @@ __global__ void __launch_bounds__(IP_SELECT_THREADS) k_ip_finish(int64_t n, int 
                                                    uint32_t* __restrict__ counts_packed,
                                                    const uint32_t* __restrict__ cand_id, const float* __restrict__ cand_s,
                                                    const float* __restrict__ tau, const IpBand band,
-                                                   const float* __restrict__ Q, const PT* __restrict__ P, int d,
+                                                   const float* __restrict__ Q, typename IpRows<PT>::type P, int d,
                                                    uint32_t* __restrict__ m_out, int32_t* __restrict__ status, float* __restrict__ tau_retry,
                                                    float* __restrict__ D, int64_t* __restrict__ I, double unscale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(IP_SELECT_THREADS) k_ip_finish(int64_t n, int 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const float* qv = Q + (int64_t)q * d;
     for (int slot = wave; slot < m; slot += nw) {
-      const double acc = ip_row_score<PT>(qv, P + (int64_t)bid[slot] * d, d, lane, unscale);
+      const double acc = ip_row_score<PT>(qv, ip_row_at(P, (int64_t)bid[slot], d), d, lane, unscale);
       if (lane == 0) sx[slot] = acc;     // (key[] is dead: every thread passed the barrier after the compaction)
     }
   }

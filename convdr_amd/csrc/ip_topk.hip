@@ -82,12 +82,33 @@ constexpr float IP_F16_NORM_LIMIT = 60000.f; // scaled norms above this may hold
 // rescale both operands and are not affected (precision="auto" / "fp16" take such data).
 constexpr float IP_BF16_NORM_FLOOR = 0x1p-60f;
 
+// The 8-bit store (store 3, IP_KIND_I8): rows of int8 codes c_ij, |c_ij| <= 127; the corpus is v_ij = fl(centre_j + fl(step_j c_ij)).
+// The scan is integer and exact: S_i = sum_j Qi_j c_ij with Qi_j = rint(fl(q_j step_j) / t) (k_q8_queries), handed on as the float
+// S~_i = fl(S_i).  Its target is the exact scaled score E_i = (1 / t) sum_j q_j (v_ij - centre_j), which orders the rows of a
+// query as q . v_i does (t > 0, q . centre the same for every row).  With u = 2^-24 and every step_j zero or a normal number
+// (k_colstep_finish), so that each fp32 product below has relative error <= u:
+//   rows      fl(step c) = step c (1 + d1), v = (centre + fl(step c)) (1 + d2), |d1|, |d2| <= u (an fp32 sum is exact in the
+//             subnormal range), hence |v_ij - centre_j - step_j c_ij| <= u (|centre_j| + 127 (2 + u) step_j) =: u rho_j and
+//             |E_i - (1 / t) sum_j q_j step_j c_ij| <= (u / t) sum_j |q_j| rho_j =: A(q)            (k_q8_queries, per query)
+//   query     |Qi_j - q_j step_j / t| <= 1/2 + u (1 + 2u) 16256 + 2^-36: the rint, the rounding of q_j step_j relative to
+//             |fl(q_j step_j)| / t <= 16256, and 2^-150 / t for a product in the subnormal range (t >= 2^-114: queries with
+//             max |fl(q_j step_j)| below 2^-100 are CONVDR_IP_RANGE); times |c_ij| and summed: (1/2 + r0) ||c_i||_1
+//   convert   |fl(S_i) - S_i| <= u |S_i| <= u 16256 ||c_i||_1
+// Together |S~_i - E_i| <= (1/2 + r) max_i ||c_i||_1 + A(q),  r = u 16256 (2 + 2u) + 2^-36 = 0.00193787...; IpBand::eps adds its
+// 1.001.  The largest row L1 norm is kept at add (only ever growing); nothing here depends on d.
+// No integer overflows for d <= 1024 (ip_scan_q8.hpp): |S_i| <= 1024 x 127 x 16256 = 2,114,060,288 < 2^31.
+constexpr int IP_KIND_I8 = 2;
+constexpr int IP_Q8_MAX_D = 1024;
+constexpr float IP_Q8_COEF = (float)((0.5 + (16256.0 * (2.0 + 0x1p-23) * 0x1p-24 + 0x1p-36)) * (1.0 + 1e-6));
+
 }  // namespace convdr
 
 // rows to 16-bit scan operands and norms, the half store, the column mean
 #include "ip_prepare.hpp"
 // the scan: arguments, row filter, epilogues, the two persistent kernels, launch_scan<MODE>
 #include "ip_scan.hpp"
+// the 8-bit store's scan: int8 codes against hi / lo int8 queries on the i8 MFMA, the same epilogues
+#include "ip_scan_q8.hpp"
 // order statistics, threshold select, cut / re-score / select / finish; the certificate (ip_certify.hpp)
 #include "ip_select.hpp"
 // the host side: block descriptor, argument checks, plan head, shared steps and the shallow pipeline (k <= 4096)
@@ -306,4 +327,85 @@ extern "C" int convdr_ip_search_filtered(int store, int deep, const float* q_f32
   CONVDR_REQUIRE(store != 2 || p_half_lo == nullptr, "%s: the half store has no remainder copy", name);
   return ip_topk(name, deep != 0, {store, p_f32, p_half, p_half_lo, store == 0 ? 1.f : p_scale, two_pass != 0, n, d, p_max_norm,
                                    row_bits, row_bits_words, n_allowed}, IP_TOPK_ARGS);
+}
+
+// ---- the 8-bit store -------------------------------------------------------------------------------------------------
+static int q8_check_width(const char* name, int64_t n, int d) {
+  CONVDR_REQUIRE(n >= 0 && d > 0 && d % 128 == 0 && d <= IP_Q8_MAX_D, "%s: need n >= 0, d %% 128 == 0 and d <= %d (got n=%lld d=%d)", name,
+                 IP_Q8_MAX_D, (long long)n, d);
+  return 0;
+}
+
+extern "C" int convdr_ip_column_absdev(const float* p_f32, int64_t n, int d, const float* centre, float* scratch /* >= 1024 * d floats */,
+                                       float* step, convdr_stream_t stream) {
+  CONVDR_REQUIRE(n > 0 && d > 0, "convdr_ip_column_absdev: empty block");
+  CONVDR_REQUIRE(p_f32 && centre && scratch && step, "convdr_ip_column_absdev: a NULL argument (p_f32, centre, scratch, step)");
+  const int chunks = n >= 262144 ? 1024 : (n >= 4096 ? 64 : 1);   // (as convdr_ip_column_mean)
+  hipLaunchKernelGGL(k_colabsdev_f32, dim3((d + 255) / 256, chunks), dim3(256), 0, (hipStream_t)stream, p_f32, n, d, centre, scratch);
+  CONVDR_CHECK_LAUNCH("k_colabsdev_f32");
+  hipLaunchKernelGGL(k_colstep_finish, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, scratch, chunks, d, step);
+  CONVDR_CHECK_LAUNCH("k_colstep_finish");
+  return 0;
+}
+
+extern "C" int convdr_ip_store_rows_q8(const float* src, int64_t n, int d, const float* centre, const float* step, void* codes,
+                                       float* max_l1, int32_t* flags, uint32_t* saturated, convdr_stream_t stream) {
+  const char* name = "convdr_ip_store_rows_q8";
+  if (int e = q8_check_width(name, n, d)) return e;
+  if (n == 0) return 0;
+  CONVDR_REQUIRE(src && centre && step && codes && max_l1 && flags && saturated,
+                 "%s: a NULL argument (src, centre, step, codes, max_l1, flags, saturated)", name);
+  const int64_t blocks = ceil_div64(n, 4);
+  hipLaunchKernelGGL(k_store_rows_q8, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, src, n, d, centre,
+                     step, (int8_t*)codes, max_l1, flags, saturated);
+  CONVDR_CHECK_LAUNCH("k_store_rows_q8");
+  return 0;
+}
+
+static IpBlock q8_block(const void* codes, const float* centre, const float* step, int64_t n, int d, const float* p_max_l1,
+                        const uint32_t* row_bits = nullptr, int64_t row_bits_words = 0, int64_t n_allowed = 0) {
+  IpBlock b = {3, nullptr, codes, nullptr, 1.f, false, n, d, p_max_l1, row_bits, row_bits_words, n_allowed};
+  b.q8_centre = centre;
+  b.q8_step = step;
+  return b;
+}
+
+extern "C" int convdr_ip_search_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step, int64_t n,
+                                   int d, int k, const float* p_max_l1, const float* tau_in, int cap, int rank_target,
+                                   void* workspace, size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                                   convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search_q8", false, q8_block(codes, centre, step, n, d, p_max_l1), IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_search_deep_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step,
+                                        int64_t n, int d, int k, const float* p_max_l1, const float* tau_in, int cap,
+                                        int rank_target, void* workspace, size_t workspace_bytes, float* D, int64_t* I,
+                                        int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  return ip_topk("convdr_ip_search_deep_q8", true, q8_block(codes, centre, step, n, d, p_max_l1), IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_search_filtered_q8(int deep, const float* q_f32, int nq, const void* codes, const float* centre,
+                                            const float* step, int64_t n, int d, int k, const float* p_max_l1, const float* tau_in,
+                                            int cap, int rank_target, void* workspace, size_t workspace_bytes,
+                                            const uint32_t* row_bits, int64_t row_bits_words, int64_t n_allowed, float* D,
+                                            int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream) {
+  const char* name = "convdr_ip_search_filtered_q8";
+  CONVDR_REQUIRE(deep == 0 || deep == 1, "%s: deep must be 0 or 1 (got %d)", name, deep);
+  CONVDR_REQUIRE(row_bits != nullptr, "%s: row_bits is NULL", name);
+  CONVDR_REQUIRE(n_allowed >= 0 && n_allowed <= n, "%s: n_allowed=%lld outside [0, n=%lld]", name, (long long)n_allowed, (long long)n);
+  return ip_topk(name, deep != 0, q8_block(codes, centre, step, n, d, p_max_l1, row_bits, row_bits_words, n_allowed), IP_TOPK_ARGS);
+}
+
+extern "C" int convdr_ip_score_rows_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step,
+                                       int64_t n, int d, const int64_t* rows, int m, int64_t ld, double* X, float* D,
+                                       convdr_stream_t stream) {
+  const char* name = "convdr_ip_score_rows_q8";
+  CONVDR_REQUIRE(nq >= 0 && m >= 0 && ld >= m, "%s: bad sizes nq=%d m=%d ld=%lld (ld >= m)", name, nq, m, (long long)ld);
+  CONVDR_REQUIRE(n < ((int64_t)1 << 31), "%s: bad block size n=%lld (0 <= n < 2^31)", name, (long long)n);
+  if (int e = q8_check_width(name, n, d)) return e;
+  if (nq == 0 || m == 0) return 0;
+  CONVDR_REQUIRE(q_f32 && rows, "%s: a NULL argument (q_f32, rows)", name);
+  CONVDR_REQUIRE(n == 0 || (codes && centre && step), "%s: a NULL block pointer (codes, centre, step)", name);
+  if (!X && !D) return 0;
+  return ip_score_rows_launch(q8_block(codes, centre, step, n, d, nullptr), q_f32, nq, rows, m, ld, X, D, (hipStream_t)stream);
 }

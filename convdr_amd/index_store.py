@@ -9,8 +9,13 @@ import numpy as np
 from . import _lib
 from .staging import _STAGING, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _staging, _staging_key
 
-_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16"}
+_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16", "i8": "i8"}
 _HALF_PRECISIONS = ("auto", "fp16", "fp16x2")    # the rungs of a half store (storage="fp16")
+_SQ8_PRECISIONS = ("auto", "i8")                 # the one rung of an 8-bit store (storage="sq8"): the two-operand integer scan
+SQ8_MAX_D = 1024                                 # csrc/ip_topk.hip: IP_Q8_MAX_D (the int32 range of the integer scan)
+SQ8_REFUSED = ("range_search", "range_search_tensors", "range_count", "rank_rows", "rank_rows_tensors", "rank_ids",
+               "rank_ids_tensors", "excluding", "score_ids", "score_ids_tensors", "search_docs", "search_distinct", "update_rows",
+               "upsert", "upsert_docs")           # entries the 8-bit store does not offer (README, "8-bit passage store")
 HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM_LIMIT
 
 RESERVED_ID = -(1 << 63)    # INT64_MIN: the free-slot marker of the key set (csrc/ip_keys.hpp), no legal row id
@@ -143,10 +148,21 @@ class _IndexStore:
     # operations' workspace, the H2D stream of the streamed add; a reservation; "auto" starts on the split scan
     _sid = _sid_spare = _key_ws = _copy_stream = None
     _reserved = _x3_first = False
+    _sq8 = False                # the 8-bit store (storage="sq8"); the constructor sets it
 
     def __init__(self, d, device=None, cap=4096, rank_target=0, precision="auto", center=None, prepin=True, storage="fp32"):
-        if storage not in ("fp32", "fp16"):
-            raise ValueError("FlatIPIndex: storage must be 'fp32' or 'fp16' (got %r)" % (storage,))
+        if storage not in ("fp32", "fp16", "sq8"):
+            raise ValueError("FlatIPIndex: storage must be 'fp32', 'fp16' or 'sq8' (got %r)" % (storage,))
+        if storage == "sq8":
+            if precision not in _SQ8_PRECISIONS:
+                raise ValueError("FlatIPIndex(storage='sq8'): precision must be one of %s (got %r)" % (_SQ8_PRECISIONS, precision))
+            if center is not None and not center:
+                raise ValueError("FlatIPIndex(storage='sq8'): the 8-bit store is always centred (center=False)")
+            if (int(d) + 127) // 128 * 128 > SQ8_MAX_D:
+                raise ValueError("FlatIPIndex(storage='sq8'): d = %d, at most %d" % (int(d), SQ8_MAX_D))
+            center = True
+        elif precision == "i8":
+            raise ValueError("FlatIPIndex(storage=%r): precision 'i8' belongs to storage='sq8'" % (storage,))
         if storage == "fp16":
             if precision not in _HALF_PRECISIONS:
                 raise ValueError("FlatIPIndex(storage='fp16'): precision must be one of %s (got %r)" % (_HALF_PRECISIONS, precision))
@@ -159,16 +175,18 @@ class _IndexStore:
         if not torch.cuda.is_available():
             raise _lib.ConvdrError("FlatIPIndex needs a GPU (no CPU fallback)")
         assert precision in _KINDS and (storage == "fp16" or precision != "fp16x2"), precision
-        self.storage, self._half = storage, storage == "fp16"
+        self.storage, self._half, self._sq8 = storage, storage == "fp16", storage == "sq8"
         _lib.lib()
-        # the scan contracts in 64-wide K steps: other widths get zero columns, which add exact zeros to every score
+        # the scan contracts in 64-wide K steps (128 for the 8-bit store: one K step is 128 bytes): other widths get zero
+        # columns, which add exact zeros to every score
         self.d_in = int(d)
-        self.d = (self.d_in + 63) // 64 * 64
+        kstep = 128 if self._sq8 else 64
+        self.d = (self.d_in + kstep - 1) // kstep * kstep
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.cap, self.rank_target = int(cap), int(rank_target)
         self.precision, self.center = precision, bool(center)
-        self.kind = _KINDS[precision]
-        self._half_dtype = torch.float16 if self.kind == "f16" else torch.bfloat16
+        self.kind = "i8" if self._sq8 else _KINDS[precision]
+        self._half_dtype = torch.int8 if self._sq8 else (torch.float16 if self.kind == "f16" else torch.bfloat16)
         self.host_chunk_bytes = 64 << 20       # staging-buffer size of the streamed host -> HBM path (add); 64 MB x 16
                                                # threads measured best on the bench host (tools/dbg/block_load_sweep.py)
         self.host_copy_threads = 16            # file reads / memcpy slices in flight while filling a staging buffer
@@ -205,9 +223,14 @@ class _IndexStore:
         """An empty index with this one's parameters (search_one_by_one keeps two blocks in flight: one being searched, one
         being loaded)."""
         t = type(self)(self.d_in, device=self.device, cap=self.cap, rank_target=self.rank_target, precision=self.precision,
-                         center=None if self._half else self.center, prepin=False, storage=self.storage)
+                         center=None if self._one_buffer else self.center, prepin=False, storage=self.storage)
         t.host_chunk_bytes, t.host_copy_threads, t.host_stage_buffers = self.host_chunk_bytes, self.host_copy_threads, self.host_stage_buffers
         return t
+
+    @property
+    def _one_buffer(self):
+        """the store is corpus and scan operand at once (half store, 8-bit store): no fp32 block, no remainder copy"""
+        return self._half or self._sq8
 
     # -- faiss-like surface ---------------------------------------------------
     @property
@@ -229,8 +252,8 @@ class _IndexStore:
 
     @property
     def _rows(self):
-        """The rows the canonical re-score reads: the fp32 block, or the half store itself."""
-        return self._pbf if self._half else self._p32
+        """The rows the canonical re-score reads: the fp32 block, or the half / 8-bit store itself."""
+        return self._pbf if self._one_buffer else self._p32
 
     @property
     def store(self):
@@ -239,7 +262,7 @@ class _IndexStore:
 
     def _row_pair(self, sel):
         """(re-score rows, scan copy) of a slice or an index vector of the resident rows, contiguous"""
-        if self._half:
+        if self._one_buffer:
             r = self._pbf[sel].contiguous()
             return r, r
         return self._p32[sel].contiguous(), self._pbf[sel].contiguous()
@@ -279,6 +302,12 @@ class _IndexStore:
         self._centre = None
         self._scale = 1.0                       # power of two applied to the fp16 scan copy (1 for bf16)
         self._max_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self._sq8:
+            # the largest row L1 norm of the codes (in _max_norm's role), the flag word and the saturation count of
+            # convdr_ip_store_rows_q8 side by side: ONE host read at the end of an add()
+            self._step, self._saturated = None, 0
+            self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self._max_norm, self._flags, self._sat = self._mf[:1], self._mf[1:2].view(torch.int32), self._mf[2:].view(torch.int32)
         if self._half:
             # max norm and the flag word of convdr_ip_store_rows_f16 side by side: ONE host read at the end of an add()
             self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
@@ -296,7 +325,7 @@ class _IndexStore:
         `lo`, default: only if the precision pins it; + the id column of an index that carries ids).  Existing rows are kept."""
         import torch
         held = {"_s16": self._half_dtype}          # the buffers this index holds: a half store keeps its 16-bit rows and nothing else
-        if not self._half:
+        if not self._one_buffer:
             held["_s32"] = torch.float32
             if self._slo is not None or ((self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)):
                 held["_slo"] = self._half_dtype
@@ -461,6 +490,8 @@ class _IndexStore:
         chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
         if self._half:
             return self._add_half(x, chunk_bytes)
+        if self._sq8:
+            return self._add_sq8(x, chunk_bytes)
         t, reader = self._source(x, chunk_bytes, np.float32, (torch.float32,))
         m = int(t.shape[0])
         if m == 0:
@@ -493,6 +524,76 @@ class _IndexStore:
                     dst32.copy_(t)
                 self._prepare_into(dst32, dst16, dstlo)
         self._n += m
+
+    # -- the 8-bit store (storage="sq8") -----------------------------------------
+    def _refuse_sq8(self, who):
+        """ValueError for an entry the 8-bit store does not offer, before anything is launched"""
+        if self._sq8:
+            raise ValueError("FlatIPIndex(storage='sq8').%s: not offered by the 8-bit store (storage='sq8'); use storage='fp32' or "
+                             "'fp16'" % who)
+
+    def _add_sq8(self, x, chunk_bytes):
+        """add() of an 8-bit store: fp32 rows (fp16 rows are widened, exactly) -> int8 codes, convdr_ip_store_rows_q8.
+        The FIRST add fixes the centre (column mean) and the step (largest column deviation / 127) from ITS rows, all of them,
+        so a host array of a first add is streamed into a transient device buffer of the add's size (4 d bytes per row for
+        fp32 input, 2 d for fp16) before anything is quantised: build a large index from a first block it can afford.
+        LATER adds of a host array (fp32 or fp16, through the staging buffers) are quantised chunk by chunk under the next
+        chunk's copy: the transient memory is one window of host_stage_buffers chunks, whatever the add's size.  The L1 norm,
+        the flag word and the saturation count are read ONCE, at the end: a value that is not finite refuses the add and
+        leaves the index exactly as it was (the codes it wrote lie behind ntotal)."""
+        import torch
+        src = x.array if hasattr(x, "array") else x
+        is16 = getattr(src, "dtype", None) in (np.float16, torch.float16) and self.d == self.d_in
+        t, reader = self._source(x, chunk_bytes, np.float16 if is16 else np.float32, (torch.float32, torch.float16))
+        m = int(t.shape[0])
+        if m == 0:
+            return
+        L, ptr = _lib.lib(), _lib.ptr
+        n0, first = self._n, self._n == 0
+
+        def quantise(rows, dst):
+            rows = rows if rows.dtype == torch.float32 else rows.float()
+            _lib.check(L.convdr_ip_store_rows_q8(ptr(rows), int(rows.shape[0]), self.d, ptr(self._centre), ptr(self._step), ptr(dst),
+                                                 ptr(self._max_norm), ptr(self._flags), ptr(self._sat), _lib.stream_ptr()),
+                       "convdr_ip_store_rows_q8")
+        with torch.cuda.device(self.device):
+            state0 = (self._centre, self._step, self._mf.clone())
+            dst = self._grow_for(m)[1]
+            if isinstance(t, np.ndarray) and not first:
+                # windows of the staging ring's size: the copy stream waits for the main stream at the start of every window
+                # (_stream_rows), i.e. for the quantisation of the window before, so ONE bounce buffer serves them all
+                per = max(1, int(chunk_bytes) // (4 * self.d)) * 4 // t.dtype.itemsize
+                win = per * max(2, int(self.host_stage_buffers))
+                tmp = torch.empty((min(win, m), self.d), dtype=torch.float16 if is16 else torch.float32, device=self.device)
+                for a in range(0, m, win):
+                    b = min(m, a + win)
+                    rd = None if reader is None else (lambda buf, s, e, a=a, **kw: reader(buf, a + s, a + e, **kw))
+                    self._stream_rows(t[a:b], tmp[:b - a], rd, chunk_bytes,
+                                      lambda ci, s, e, a=a: quantise(tmp[s:e], dst[a + s:a + e]))
+            else:
+                if isinstance(t, np.ndarray):
+                    tmp = torch.empty((m, self.d), dtype=torch.float16 if is16 else torch.float32, device=self.device)
+                    self._stream_rows(t, tmp, reader, chunk_bytes, lambda ci, s, e: None)
+                    t = tmp
+                if t.dtype != torch.float32:
+                    t = t.float()
+                if first:
+                    self._set_centre(t)
+                    self._step = torch.empty(self.d, dtype=torch.float32, device=self.device)
+                    scratch = torch.empty(1024 * self.d, dtype=torch.float32, device=self.device)
+                    _lib.check(L.convdr_ip_column_absdev(ptr(t), m, self.d, ptr(self._centre), ptr(scratch), ptr(self._step),
+                                                         _lib.stream_ptr()), "convdr_ip_column_absdev")
+                quantise(t, dst)
+            got = self._mf[1:].view(torch.int32).cpu()                      # the one host read of this add()
+            fl, sat = int(got[0]), int(got[1]) & 0xffffffff
+            self._mf[1:].zero_()
+            if fl & 1:
+                self._centre, self._step = state0[0], state0[1]
+                self._mf.copy_(state0[2])
+                raise _lib.ConvdrError("FlatIPIndex(storage='sq8').add: a value is not finite; the index is unchanged (%d rows)" % n0)
+            self._saturated += sat
+            self.stats["sq8_saturated"] = self._saturated
+            self._n = n0 + m
 
     # -- the half store (storage="fp16") ----------------------------------------
     def _store_rows(self, src, dst, scale, fold_norm=True, flags=None):
@@ -648,6 +749,7 @@ class _IndexStore:
         """Overwrite rows [row0, row0 + len(emb)) of the resident block with freshly encoded embeddings
         (device fp32 [m, d]) and refresh their scan copy / the block's max norm.  No sync."""
         import torch
+        self._refuse_sq8("update_rows")
         m = int(emb.shape[0])
         assert emb.dtype == torch.float32 and emb.is_contiguous() and row0 + m <= self.ntotal
         if self._half:
@@ -936,6 +1038,7 @@ class _IndexStore:
         (n_updated, n_added).  A list that repeats an id, or an id that sits on more than one row (chunk rows: which one?),
         raises ValueError BEFORE anything is written -- one host read, the one that also splits the list."""
         import torch
+        self._refuse_sq8("upsert")
         t, first, count, dup, ws, status = self._locate("upsert", ids, want_dup=True)
         m = int(t.numel())
         self._emb_arg("upsert", emb, m)
@@ -1132,6 +1235,7 @@ class _IndexStore:
         removed and others added, so a RowFilter built before the call must not be reused even where ntotal happens to come
         out equal -- the staleness check compares ntotal only.  Side tables in row order are cut as for keep_rows."""
         import torch
+        self._refuse_sq8("upsert_docs")
         self._need_ids("upsert_docs")
         t = self._id_list("upsert_docs", ids)
         m = int(t.numel())
@@ -1189,6 +1293,9 @@ class _IndexStore:
         if self._rows is None:
             return torch.empty(tuple(t.shape) + (self.d_in,), dtype=torch.float32, device=self.device)
         r = self._rows[t.reshape(-1)][:, :self.d_in]
+        if self._sq8:
+            # v = fl(centre + fl(step c)): two torch ops, each rounded to fp32 (nothing fuses them)
+            r = self._centre[:self.d_in] + self._step[:self.d_in] * r.float()
         if self._half:
             r = r.float() * (1.0 / float(self._scale))     # (a power of two: exact)
         return r.reshape(tuple(t.shape) + (self.d_in,)).contiguous()
@@ -1214,11 +1321,13 @@ class _IndexStore:
     # are rebuilt by load as add builds them; RowFilter / DocOrdinals are derived and stale across a save / load.
     def _sections(self):
         """[(name, device tensor of the used rows or None, rows, row_bytes)] of what a snapshot holds, in file order"""
-        secs = [("rows", self._rows, self._n, self.d * (2 if self._half else 4))]
+        secs = [("rows", self._rows, self._n, self.d * (1 if self._sq8 else (2 if self._half else 4)))]
         if self._sid is not None:
             secs.append(("ids", self.ids, self._n, 8))
         if self._centre is not None:
             secs.append(("centre", self._centre, 1, self.d * 4))
+        if self._sq8 and self._step is not None:
+            secs.append(("step", self._step, 1, self.d * 4))
         return secs
 
     def _digest_into(self, t, rows, row_bytes, word0, window_rows, out):
@@ -1238,7 +1347,7 @@ class _IndexStore:
             at += c
         dg = torch.zeros((at + 1, 2), dtype=torch.int64, device=self.device)
         for name, t, rows, rb in secs:
-            w0 = 0 if name == "centre" else word0_rows * (rb // 8)
+            w0 = 0 if name in ("centre", "step") else word0_rows * (rb // 8)
             self._digest_into(t, rows, rb, w0, window_rows, dg[spans[name][0]:spans[name][1]])
         dg[at, :1].copy_(self._max_norm.view(torch.int32))
         return dg, spans
@@ -1262,8 +1371,10 @@ class _IndexStore:
             got, mn = self._digest_read(dg, spans)
         fp = {"d_in": self.d_in, "storage": self.storage, "precision": self.precision, "center": self.center, "n": self._n,
               "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "%08x" % mn}
-        for name in ("rows", "ids", "centre"):
+        for name in ("rows", "ids", "centre") + (("step",) if self._sq8 else ()):
             fp[name] = None if name not in got else (got[name][0] if got[name] else (0, 0))
+        if self._sq8:
+            fp["sq8_saturated"] = self._saturated
         return fp
 
     def _stage_bytes(self, total):
@@ -1384,6 +1495,8 @@ class _IndexStore:
         meta = {"d_in": self.d_in, "d": self.d, "storage": self.storage, "precision": self.precision, "center": self.center,
                 "n": self._n, "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "0" * 8,
                 "x3_first": bool(self._x3_first), "has_ids": self._sid is not None, "window_rows": w}
+        if self._sq8:       # (max_norm holds the largest row L1 norm of the codes)
+            meta["sq8_saturated"] = int(self._saturated)
         timings = {}
         with torch.cuda.device(self.device):
             dg, spans = self._digest_sections(secs, w)
@@ -1427,19 +1540,21 @@ class _IndexStore:
         if not (0 <= r0 <= r1 <= n_file) or r0 % w or (r1 % w and r1 != n_file):
             raise ValueError("load: rows=(%d, %d) must lie in [0, n = %d], r0 a multiple of the file's window_rows = %d and r1 a "
                              "multiple of it or n" % (r0, r1, n_file, w))
-        half = h["storage"] == "fp16"
+        half, sq8 = h["storage"] == "fp16", h["storage"] == "sq8"
         precision = h["precision"] if precision is None else precision
-        if precision not in _KINDS or (not half and precision == "fp16x2"):
+        if (precision not in _SQ8_PRECISIONS) if sq8 else (precision not in _KINDS or precision == "i8" or (not half and precision == "fp16x2")):
             raise ValueError("load: precision %r is none of the %s store's" % (precision, h["storage"]))
         idx = cls(int(h["d_in"]), device=device, cap=cap, rank_target=rank_target, precision=precision,
-                  center=None if half else bool(h["center"]), prepin=prepin, storage=h["storage"])
-        n, esz = r1 - r0, 2 if half else 4
+                  center=None if (half or sq8) else bool(h["center"]), prepin=prepin, storage=h["storage"])
+        n, esz = r1 - r0, 1 if sq8 else (2 if half else 4)
         rb = idx.d * esz
         want = {"rows": (n_file * rb, rb)}
         if h["has_ids"]:
             want["ids"] = (n_file * 8, 8)
         if "centre" in secs:
             want["centre"] = (idx.d * 4, idx.d * 4)
+        if sq8 and n_file:
+            want["step"] = (idx.d * 4, idx.d * 4)
         for name, (nbytes, rbytes) in want.items():
             if name not in secs or (secs[name]["bytes"], secs[name]["row_bytes"]) != (nbytes, rbytes) or int(h["d"]) != idx.d:
                 raise _lib.ConvdrError("load %s: section %r does not have the %d bytes of %d-byte rows the header's n, d and storage "
@@ -1459,6 +1574,12 @@ class _IndexStore:
                     c = np.empty(idx.d, dtype=np.float32)
                     snapshot.pread_into(fd, memoryview(c).cast("B"), secs["centre"]["offset"])
                     idx._centre = torch.from_numpy(c).to(idx.device)
+                if sq8 and "step" in secs:
+                    c = np.empty(idx.d, dtype=np.float32)
+                    snapshot.pread_into(fd, memoryview(c).cast("B"), secs["step"]["offset"])
+                    idx._step = torch.from_numpy(c).to(idx.device)
+                    idx._saturated = int(h.get("sq8_saturated", 0))
+                    idx.stats["sq8_saturated"] = idx._saturated
                 idx._scale, idx._x3_first = scale, bool(h["x3_first"])
                 # (copy_ INTO the tensor: the half store's max norm is a view of its (norm, flags) triple and must stay one)
                 idx._max_norm.copy_(torch.tensor([mn_bits - (1 << 32) if mn_bits >> 31 else mn_bits], dtype=torch.int32).view(torch.float32))
@@ -1468,7 +1589,7 @@ class _IndexStore:
                     idx._reserved = reserve is not None
                 if n:
                     src = snapshot.FileRows(fd, secs["rows"]["offset"], rb, r0, n, idx.d)
-                    if half:
+                    if half or sq8:
                         idx._stream_rows(src, idx._s16[:n], src.read_rows_into, idx.host_chunk_bytes, lambda ci, s, e: None, t0)
                     else:
                         p32, p16, plo = idx._s32[:n], idx._s16[:n], None if idx._slo is None else idx._slo[:n]
@@ -1484,7 +1605,7 @@ class _IndexStore:
                     dg, spans = idx._digest_sections(idx._sections(), w, word0_rows=r0)
                     got, _ = idx._digest_read(dg, spans)
                     for name in sorted(got):
-                        first = 0 if name == "centre" else r0 // w
+                        first = 0 if name in ("centre", "step") else r0 // w
                         for j, pair in enumerate(got[name]):
                             if pair != secs[name]["digests"][first + j]:
                                 raise _lib.ConvdrError("load %s: section %r, window %d: what landed on the device has digest %016x %016x, "
@@ -1494,6 +1615,6 @@ class _IndexStore:
                     torch.cuda.current_stream().synchronize()       # (the call returns when the index is in place)
         finally:
             os.close(fd)
-        idx.stats["load_bytes"] = sum(secs[name]["bytes"] if name == "centre" else n * want[name][1] for name in want)
+        idx.stats["load_bytes"] = sum(secs[name]["bytes"] if name in ("centre", "step") else n * want[name][1] for name in want)
         idx.stats["load_s"] = time.perf_counter() - t0
         return idx

@@ -74,7 +74,13 @@ class FlatIPIndex(_IndexStore):
     rows are kept bit for bit, fp32 rows are rounded to nearest even once, at add) and ``search`` returns the exact,
     certified top-k of those halves widened to fp32.  Its precisions are "auto" (single pass, then the two-pass rung
     P Qh + P Ql, then the exhaustive rung; `stats["x2_queries"]`), "fp16" and "fp16x2"; add() refuses (ConvdrError, index
-    unchanged) rows with a value that is not finite as a half or with a norm above 60,000."""
+    unchanged) rows with a value that is not finite as a half or with a norm above 60,000.
+    "sq8" is the 8-BIT STORE: the passage is kept once, as d int8 codes of a scalar quantiser (centre = the first add's column
+    mean, step = its largest column deviation / 127, both fixed then; later rows outside saturate, `stats["sq8_saturated"]`), and
+    the codes are both the corpus and the operand of an exact integer scan (include/convdr_hip.h, "8-bit store").  The corpus is
+    DEFINED as the reconstructed rows fl32(centre + fl32(step * code)) -- what ``reconstruct_n`` returns -- and ``search`` is the
+    exact, certified top-k of those.  d is padded to a multiple of 128 and at most 1,024; precisions "auto" / "i8"; always
+    centred; add() refuses a value that is not finite; `index_store.SQ8_REFUSED` lists the entries it does not offer."""
 
     def _ids_arg(self, who, q, ids):
         """(queries as a tensor, ids as a tensor, the shape of `ids`) of a (queries, document ids) call; the checks that need
@@ -111,6 +117,7 @@ class FlatIPIndex(_IndexStore):
         the id -1.  Re-ranking a list of documents (BM25 candidates, a known positive) needs no id -> row map on the host:
         one key set and one CSR over the flattened list, one score launch, one host read (the CSR's size)."""
         import torch
+        self._refuse_sq8("score_ids")
         self._need_ids("score_ids")
         qt, it, shape = self._ids_arg("score_ids", q, ids)
         nq, m = int(qt.shape[0]), (shape[1] if len(shape) == 2 else 1)
@@ -147,6 +154,7 @@ class FlatIPIndex(_IndexStore):
         return self._search_docs(q, k, allowed, depth, strict, max_depth, None)
 
     def _search_docs(self, q, k, allowed, depth, strict, max_depth, exclude):
+        self._refuse_sq8("search_docs")
         self._need_ids("search_docs")
         D, I, K, counts = self._search_distinct_rows(q, k, self.ids, depth, strict, max_depth, allowed, exclude)
         return D, K, I, counts
@@ -173,11 +181,30 @@ class FlatIPIndex(_IndexStore):
                    "and their products are subnormal and the scan's error bound does not hold; use precision=\"auto\" or "
                    "\"fp16\", whose scan rescales both operands")
 
+    _SQ8_RANGE = ("CONVDR_IP_RANGE from the 8-bit store's scan: a query holds a value that is not finite, or its largest |q_j step_j| "
+                  "is non-zero and below 2^-100, where the integer query operand has no relative precision")
+
+    @property
+    def _range_message(self):
+        return self._SQ8_RANGE if self._sq8 else self._BF16_RANGE
+
     def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
                      deep=False, allowed=None):
         """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth; with a
         RowFilter, convdr_ip_search_filtered with the same operands."""
         ptr = _lib.ptr
+        if self._sq8:
+            # the 8-bit store's entries: codes, centre, step; the largest row L1 norm of the codes in the max norm's place
+            L, ent = _lib.lib(), "convdr_ip_search_deep_q8" if deep else "convdr_ip_search_q8"
+            rows = (ptr(p16), ptr(self._centre), ptr(self._step), n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target,
+                    ptr(ws), ws.numel())
+            out = (ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr())
+            if allowed is not None:
+                _lib.check(L.convdr_ip_search_filtered_q8(int(bool(deep)), ptr(q), nq, *rows, ptr(allowed.bits), allowed.bits.numel(),
+                                                          allowed.n_allowed, *out), "convdr_ip_search_filtered_q8")
+            else:
+                _lib.check(getattr(L, ent)(ptr(q), nq, *rows, *out), ent)
+            return
         store, r32, r16, scale, _ = self._operands((p32, p16))
         rlo, split = None if self._half else ptr(plo), int(bool(split)) if self._half else 0
         if allowed is not None:
@@ -343,14 +370,16 @@ class FlatIPIndex(_IndexStore):
         D, I, status, tau_retry = first
         n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()   # one host round trip
         if n_range and self.kind != "f16":
-            raise _lib.ConvdrError("convdr_ip_search: " + self._BF16_RANGE)     # no threshold and no retry changes this verdict
+            raise _lib.ConvdrError("convdr_ip_search: " + self._range_message)     # no threshold and no retry changes this verdict
         if self.kind == "f16" and n_range:
             self._rebuild_scaled()
             self.stats["rescaled"] = 1
             D, I, status, tau_retry = enqueue(qt, k, cap=cap, x3=x3)
             n_bad = int((status != 0).sum().item())
         self.stats["retried"] = int(n_bad)
-        second = self.precision == "auto" and not x3        # the split scan is still ahead
+        if self._sq8:       # queries the first integer pass certified; the values later adds saturated
+            self.stats.update(sq8_first_pass=nq - int(n_bad), sq8_saturated=self._saturated)
+        second = self.precision == "auto" and not x3 and not self._sq8      # the split scan is still ahead (the 8-bit store has one rung)
         bad = []
         if n_bad and second and depth.shortcut:
             # a band that already covers every emitted candidate only grows with a lower threshold: those queries go
@@ -401,6 +430,8 @@ class FlatIPIndex(_IndexStore):
         for each call.  ``idx.excluding(ex).search(Q, k, allowed=f)`` is the exact top-k of the (allowed) rows that query j does
         not exclude; likewise search_tensors, search_begin, search_ids(_tensors), search_docs, range_search(_tensors),
         range_count and rank_rows(_tensors)."""
+        if getattr(self, "_sq8", False):    # (getattr: tests/test_exclude_cpu.py calls this method on a plain string)
+            self._refuse_sq8("excluding")
         return ExcludedSearch(self, exclude)
 
     def _search_begin_excluded(self, q, k, allowed, exclude):
@@ -469,6 +500,7 @@ class FlatIPIndex(_IndexStore):
         exclude (``excluding(ex).search_docs``): per-query exclusions handed to the row search, sub-selected to the open queries.  The list
         that comes back is a complete prefix of the residual order, so the certificate is the same one."""
         import torch
+        self._refuse_sq8("search_distinct")
         qt = torch.as_tensor(q)
         k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
         max_depth = _check_max_depth("search_distinct", max_depth)
@@ -559,7 +591,7 @@ class FlatIPIndex(_IndexStore):
         D, I, status, _ = self._enqueue(qq, kq, None, cap, False, rows=rows, rank_target=0)
         if int((status != 0).sum().item()):
             if self.kind != "f16" and int((status == STATUS_RANGE).sum().item()):
-                raise _lib.ConvdrError("convdr_ip_search: " + self._BF16_RANGE)
+                raise _lib.ConvdrError("convdr_ip_search: " + self._range_message)
             raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % rows[1].shape[0])
         return D, I
 
@@ -682,11 +714,13 @@ class FlatIPIndex(_IndexStore):
         the device by the fp64 scores.  Memory bound of that rung: the result itself (fp64 score, row and query number per
         result row while merging) beside one call's workspace, which stays under DEEP_WS_BYTES.
         ``stats``: range_results, range_rounds (passes), range_cap (the longest list used), range_chunked_queries."""
+        self._refuse_sq8("range_search")
         return self._range(q, radius, allowed, False)
 
     def range_count(self, q, radius, allowed=None):
         """int64 numpy [nq]: how many rows ``range_search`` would return per query, without ordering or packing them
         (1 + range_count(q, score of a known positive) is that positive's exact rank in the whole index)."""
+        self._refuse_sq8("range_count")
         return self._range(q, radius, allowed, True)
 
     def _excluded_ahead(self, ex, f, qt, pairq, x_thr, row_thr):
@@ -940,6 +974,12 @@ class FlatIPIndex(_IndexStore):
         X = torch.empty((nq, m), dtype=torch.float64, device=self.device)
         if nq and m:
             n = self.ntotal
+            if self._sq8:
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().convdr_ip_score_rows_q8(_lib.ptr(qt), nq, _lib.ptr(self._pbf), _lib.ptr(self._centre),
+                                                                  _lib.ptr(self._step), n, self.d, _lib.ptr(rt), m, m, _lib.ptr(X),
+                                                                  _lib.ptr(D), _lib.stream_ptr()), "convdr_ip_score_rows_q8")
+                return D.reshape(shape), X.reshape(shape)
             store, r32, r16, scale, _ = self._operands(None if n else (None, None))     # (an empty index passes no rows)
             with torch.cuda.device(self.device):
                 _lib.check(_lib.lib().convdr_ip_score_rows(store, _lib.ptr(qt), nq, r32, r16, scale, n, self.d, _lib.ptr(rt), m, m,
@@ -968,6 +1008,7 @@ class FlatIPIndex(_IndexStore):
     def _rank_rows_tensors(self, q, rows, allowed, exclude):
         """rank_rows_tensors, with per-query exclusions (``excluding(ex).rank_rows_tensors``) or None"""
         import torch
+        self._refuse_sq8("rank_rows")
         qt, rt, shape = self._rows_arg("rank_rows", q, rows)
         f = self._filter(allowed)
         ex = self._exclusions(exclude, int(qt.shape[0]))
@@ -1123,6 +1164,7 @@ class FlatIPIndex(_IndexStore):
         ``stats``: rank_rounds, rank_cap, rank_band_rows (band entries re-scored, all passes), rank_above (ROWS marked without
         a re-score, final passes), rank_fallback_pairs, rescaled, ndocs."""
         import torch
+        self._refuse_sq8("rank_ids")
         self._need_ids("rank_ids")
         qt, it, shape = self._ids_arg("rank_ids", q, ids)
         f = self._filter(allowed)

@@ -204,6 +204,60 @@ int convdr_ip_search_filtered(int store, int deep, const float* q_f32, int nq, c
                               const uint32_t* row_bits, int64_t row_bits_words, int64_t n_allowed, float* D, int64_t* I,
                               int32_t* status, float* tau_retry, convdr_stream_t stream);
 
+/* 8-bit store: the passage is stored ONCE, as d int8 codes, and that buffer is both the corpus and the scan operand (768
+ * bytes per passage at d = 768).  A scalar quantiser with one centre and one step per column (FAISS IndexScalarQuantizer,
+ * QT_8bit), and an EXACT search over what it stores.
+ *   corpus    THE RECONSTRUCTED ROWS  v[i, j] = fl32(centre[j] + fl32(step[j] * c[i, j])): one fp32 multiplication rounded, one
+ *             fp32 addition rounded, never contracted (numpy's float32 arithmetic gives the same bits).
+ *   codes     c = clamp(rint((p - centre) / step), -127, 127) in fp32 (subtraction, IEEE division, round half to even); a
+ *             column with step 0 has code 0; -128 is never stored.  centre: convdr_ip_column_mean of the first rows; step:
+ *             convdr_ip_column_absdev of the same rows.  Both are fixed then; later rows outside the range saturate.
+ *   result    what the fp32 entries return for the corpus v, bit for bit: canonical fp64 summation order, ranking by
+ *             (score desc, index asc), D = the fp64 score rounded to fp32, padding -FLT_MAX / -1.
+ *   scan      integer and exact: per query q'[j] = fl32(q[j] * step[j]), t the power of two with max |q'| / t in (8128, 16256],
+ *             Qi = rint(q' / t) = 128 hi + lo with hi in [-127, 127], lo in [-64, 63]; S = 128 sum hi c + sum lo c on
+ *             v_mfma_i32_32x32x32_i8 (no int32 overflows for d <= 1024), S~ = (float)S.  Thresholds, tau_retry and the lists of
+ *             convdr_ip_debug_* are in these units.
+ *   band      |S~ - E| <= (1/2 + r) max_i ||c_i||_1 + A(q) for E = (1 / t) sum_j q[j] (v[i, j] - centre[j]), r = 0.001938, A(q) =
+ *             (2^-24 / t) sum_j |q[j]| (|centre[j]| + 254 step[j]): the query's rounding, the two fp32 roundings of v, the
+ *             int-to-float conversion (derivation: csrc/ip_topk.hip, IP_Q8_COEF).  max_l1: device float, the largest row sum of
+ *             |c| (an upper bound is enough).
+ *   status    as for convdr_ip_search; CONVDR_IP_RANGE: the query holds a value that is not finite, or its largest |q'| is non-zero
+ *             and below 2^-100 -- no threshold helps.
+ *   sizes     d % 128 == 0 (one K step is 128 codes) and d <= 1024 (the int32 range above); otherwise those of the matching
+ *             fp32 entry, whose workspace size (convdr_ip_workspace_bytes / convdr_ip_deep_workspace_bytes) and layout serve as
+ *             they are: the two int8 query operands take the place of the 16-bit one.
+ * Arguments are validated before anything touches a device.
+ *
+ * convdr_ip_column_absdev: step[j] = max_i |p[i, j] - centre[j]| / 127 as fp32 (a quotient below FLT_MIN counts as 0: a constant
+ * column).  scratch: >= 1024 * d floats, as for convdr_ip_column_mean. */
+int convdr_ip_column_absdev(const float* p_f32, int64_t n, int d, const float* centre, float* scratch, float* step,
+                            convdr_stream_t stream);
+/* codes[i] = the codes of the fp32 row src[i] (n rows of d int8).  *max_l1 (device float, atomic max: the caller zeroes it once
+ * per index) takes the largest row sum of |c|; *flags (device int32, the caller zeroes it) |= 1 for a value that is not finite;
+ * *saturated (device uint32, the caller zeroes it) counts the values the clamp moved. */
+int convdr_ip_store_rows_q8(const float* src, int64_t n, int d, const float* centre, const float* step, void* codes, float* max_l1,
+                            int32_t* flags, uint32_t* saturated, convdr_stream_t stream);
+/* convdr_ip_search / convdr_ip_search_deep over an 8-bit store. */
+int convdr_ip_search_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step, int64_t n, int d,
+                        int k, const float* p_max_l1, const float* tau_in, int cap, int rank_target, void* workspace,
+                        size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry, convdr_stream_t stream);
+int convdr_ip_search_deep_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step, int64_t n,
+                             int d, int k, const float* p_max_l1, const float* tau_in, int cap, int rank_target, void* workspace,
+                             size_t workspace_bytes, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                             convdr_stream_t stream);
+/* The two above restricted to the rows of a bitmap: row_bits, row_bits_words, n_allowed and deep as for
+ * convdr_ip_search_filtered. */
+int convdr_ip_search_filtered_q8(int deep, const float* q_f32, int nq, const void* codes, const float* centre, const float* step,
+                                 int64_t n, int d, int k, const float* p_max_l1, const float* tau_in, int cap, int rank_target,
+                                 void* workspace, size_t workspace_bytes, const uint32_t* row_bits, int64_t row_bits_words,
+                                 int64_t n_allowed, float* D, int64_t* I, int32_t* status, float* tau_retry,
+                                 convdr_stream_t stream);
+/* convdr_ip_score_rows over an 8-bit store: the canonical score of (query, reconstructed row), one device function with the
+ * search's re-score. */
+int convdr_ip_score_rows_q8(const float* q_f32, int nq, const void* codes, const float* centre, const float* step, int64_t n, int d,
+                            const int64_t* rows, int m, int64_t ld, double* X, float* D, convdr_stream_t stream);
+
 /* Range search: every row of the block whose score EXCEEDS a per-query radius (IndexFlatIP.range_search, with one radius
  * per query), exact and ragged.
  *   result       with X the canonical fp64 score of the search entries (same summation order, same corpus per store: the
