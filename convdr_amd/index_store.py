@@ -8,15 +8,7 @@ import numpy as np
 
 from . import _lib
 from .staging import _STAGING, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _staging, _staging_key
-
-_KINDS = {"auto": "f16", "fp16": "f16", "fp16x3": "f16", "bf16": "bf16", "bf16x3": "bf16", "fp16x2": "f16", "i8": "i8"}
-_HALF_PRECISIONS = ("auto", "fp16", "fp16x2")    # the rungs of a half store (storage="fp16")
-_SQ8_PRECISIONS = ("auto", "i8")                 # the one rung of an 8-bit store (storage="sq8"): the two-operand integer scan
-SQ8_MAX_D = 1024                                 # csrc/ip_topk.hip: IP_Q8_MAX_D (the int32 range of the integer scan)
-SQ8_REFUSED = ("range_search", "range_search_tensors", "range_count", "rank_rows", "rank_rows_tensors", "rank_ids",
-               "rank_ids_tensors", "excluding", "score_ids", "score_ids_tensors", "search_docs", "search_distinct", "update_rows",
-               "upsert", "upsert_docs")           # entries the 8-bit store does not offer (README, "8-bit passage store")
-HALF_NORM_LIMIT = 60000.0                        # csrc/ip_topk.hip: IP_F16_NORM_LIMIT
+from .stores import _HALF_PRECISIONS, _KINDS, HALF_NORM_LIMIT, SQ8_MAX_D, SQ8_REFUSED, STORES
 
 RESERVED_ID = -(1 << 63)    # INT64_MIN: the free-slot marker of the key set (csrc/ip_keys.hpp), no legal row id
 KEY_ST_LIST, KEY_ST_PROBE, KEY_ST_COLUMN, KEY_ST_NOSET = 1, 2, 4, 8      # status bits of convdr_keyset_build / the row passes
@@ -148,45 +140,27 @@ class _IndexStore:
     # operations' workspace, the H2D stream of the streamed add; a reservation; "auto" starts on the split scan
     _sid = _sid_spare = _key_ws = _copy_stream = None
     _reserved = _x3_first = False
-    _sq8 = False                # the 8-bit store (storage="sq8"); the constructor sets it
+    _store = STORES["fp32"]     # (the default storage's, for an index built without the constructor; the constructor sets its own)
 
     def __init__(self, d, device=None, cap=4096, rank_target=0, precision="auto", center=None, prepin=True, storage="fp32"):
-        if storage not in ("fp32", "fp16", "sq8"):
+        if storage not in STORES:
             raise ValueError("FlatIPIndex: storage must be 'fp32', 'fp16' or 'sq8' (got %r)" % (storage,))
-        if storage == "sq8":
-            if precision not in _SQ8_PRECISIONS:
-                raise ValueError("FlatIPIndex(storage='sq8'): precision must be one of %s (got %r)" % (_SQ8_PRECISIONS, precision))
-            if center is not None and not center:
-                raise ValueError("FlatIPIndex(storage='sq8'): the 8-bit store is always centred (center=False)")
-            if (int(d) + 127) // 128 * 128 > SQ8_MAX_D:
-                raise ValueError("FlatIPIndex(storage='sq8'): d = %d, at most %d" % (int(d), SQ8_MAX_D))
-            center = True
-        elif precision == "i8":
-            raise ValueError("FlatIPIndex(storage=%r): precision 'i8' belongs to storage='sq8'" % (storage,))
-        if storage == "fp16":
-            if precision not in _HALF_PRECISIONS:
-                raise ValueError("FlatIPIndex(storage='fp16'): precision must be one of %s (got %r)" % (_HALF_PRECISIONS, precision))
-            if center:
-                raise ValueError("FlatIPIndex(storage='fp16'): the half store is not centred (center=True)")
-            center = False
-        elif center is None:
-            center = True
+        self.storage, self._store = storage, STORES[storage]
+        center = self._store.admit(precision, center, d)
         import torch
         if not torch.cuda.is_available():
             raise _lib.ConvdrError("FlatIPIndex needs a GPU (no CPU fallback)")
-        assert precision in _KINDS and (storage == "fp16" or precision != "fp16x2"), precision
-        self.storage, self._half, self._sq8 = storage, storage == "fp16", storage == "sq8"
+        assert precision in self._store.precisions, precision
         _lib.lib()
         # the scan contracts in 64-wide K steps (128 for the 8-bit store: one K step is 128 bytes): other widths get zero
         # columns, which add exact zeros to every score
-        self.d_in = int(d)
-        kstep = 128 if self._sq8 else 64
+        self.d_in, kstep = int(d), self._store.kstep
         self.d = (self.d_in + kstep - 1) // kstep * kstep
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.cap, self.rank_target = int(cap), int(rank_target)
-        self.precision, self.center = precision, bool(center)
-        self.kind = "i8" if self._sq8 else _KINDS[precision]
-        self._half_dtype = torch.int8 if self._sq8 else (torch.float16 if self.kind == "f16" else torch.bfloat16)
+        self.precision, self.center = precision, center
+        self.kind = self._store.kind or _KINDS[precision]
+        self._scan_dtype = {"f16": torch.float16, "bf16": torch.bfloat16, "i8": torch.int8}[self.kind]
         self.host_chunk_bytes = 64 << 20       # staging-buffer size of the streamed host -> HBM path (add); 64 MB x 16
                                                # threads measured best on the bench host (tools/dbg/block_load_sweep.py)
         self.host_copy_threads = 16            # file reads / memcpy slices in flight while filling a staging buffer
@@ -223,14 +197,9 @@ class _IndexStore:
         """An empty index with this one's parameters (search_one_by_one keeps two blocks in flight: one being searched, one
         being loaded)."""
         t = type(self)(self.d_in, device=self.device, cap=self.cap, rank_target=self.rank_target, precision=self.precision,
-                         center=None if self._one_buffer else self.center, prepin=False, storage=self.storage)
+                         center=None if self._store.centred is not None else self.center, prepin=False, storage=self.storage)
         t.host_chunk_bytes, t.host_copy_threads, t.host_stage_buffers = self.host_chunk_bytes, self.host_copy_threads, self.host_stage_buffers
         return t
-
-    @property
-    def _one_buffer(self):
-        """the store is corpus and scan operand at once (half store, 8-bit store): no fp32 block, no remainder copy"""
-        return self._half or self._sq8
 
     # -- faiss-like surface ---------------------------------------------------
     @property
@@ -253,29 +222,25 @@ class _IndexStore:
     @property
     def _rows(self):
         """The rows the canonical re-score reads: the fp32 block, or the half / 8-bit store itself."""
-        return self._pbf if self._one_buffer else self._p32
+        return self._pbf if self._s32 is None else self._p32
 
     @property
     def store(self):
         """storage="fp16": the resident halves [ntotal, d] = 2^s x the stored passages (s: ``_scale``)."""
-        return self._pbf if self._half else None
+        return getattr(self, self._store.store_view) if self._store.store_view else None
 
     def _row_pair(self, sel):
         """(re-score rows, scan copy) of a slice or an index vector of the resident rows, contiguous"""
-        if self._one_buffer:
-            r = self._pbf[sel].contiguous()
-            return r, r
-        return self._p32[sel].contiguous(), self._pbf[sel].contiguous()
+        r = self._rows[sel].contiguous()
+        return (r, r) if self._s32 is None else (r, self._pbf[sel].contiguous())
 
     def _operands(self, rows=None):
-        """What a block looks like to the C ABI: (store code 0 bf16 / 1 fp16 / 2 half store, fp32 rows or NULL, 16-bit operand,
-        scale of that operand, centre or NULL) of the resident block, or of `rows` = (re-score rows, scan copy) of a slice.  The
-        half store has no fp32 rows and no centre, the bf16 copy no scale."""
-        ptr = _lib.ptr
+        """What a block looks like to the C ABI: (store code 0 bf16 / 1 fp16 / 2 half store / 3 8-bit store, fp32 rows or NULL,
+        scan operand, scale of that operand -- the 8-bit store: its step vector --, centre or NULL) of the resident block, or of
+        `rows` = (re-score rows, scan copy) of a slice.  The half store has no fp32 rows and no centre, the bf16 copy no scale;
+        the 8-bit store's largest row L1 norm of the codes travels in the max norm's place."""
         p32, p16 = (self._rows, self._pbf) if rows is None else rows
-        store = 2 if self._half else (1 if self.kind == "f16" else 0)
-        return (store, None if self._half else ptr(p32), ptr(p16), float(self._scale) if store else 1.0,
-                None if self._half else ptr(self._centre))
+        return self._store.block(self, p32, p16)
 
     def _queries(self, q, padded_ok=False):
         """The queries as every entry reads them: fp32 [nq, d] on the index's device, contiguous, the zero columns of a padded
@@ -302,17 +267,15 @@ class _IndexStore:
         self._centre = None
         self._scale = 1.0                       # power of two applied to the fp16 scan copy (1 for bf16)
         self._max_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
-        if self._sq8:
-            # the largest row L1 norm of the codes (in _max_norm's role), the flag word and the saturation count of
-            # convdr_ip_store_rows_q8 side by side: ONE host read at the end of an add()
-            self._step, self._saturated = None, 0
+        if self._store.words:
+            # the max norm (the 8-bit store: the largest row L1 norm of the codes, in its role) and the store's words side by
+            # side: ONE host read at the end of an add()
             self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
-            self._max_norm, self._flags, self._sat = self._mf[:1], self._mf[1:2].view(torch.int32), self._mf[2:].view(torch.int32)
-        if self._half:
-            # max norm and the flag word of convdr_ip_store_rows_f16 side by side: ONE host read at the end of an add()
-            self._mf = torch.zeros(3, dtype=torch.float32, device=self.device)
-            self._max_norm, self._flags = self._mf[:1], self._mf[1:2].view(torch.int32)
-            self._uflags = self._mf[2:].view(torch.int32)       # update_rows has a flag word of its own: update_flags()
+            self._max_norm = self._mf[:1]
+            for j, name in enumerate(self._store.words, 1):
+                setattr(self, name, self._mf[j:j + 1].view(torch.int32))
+        for name, value in self._store.fields:
+            setattr(self, name, value)
         self._ws = None
         self._x3_first = False
 
@@ -324,11 +287,10 @@ class _IndexStore:
         """Backing storage for n passages (fp32 block + 16-bit scan copy, + the remainder copy of the split scan when
         `lo`, default: only if the precision pins it; + the id column of an index that carries ids).  Existing rows are kept."""
         import torch
-        held = {"_s16": self._half_dtype}          # the buffers this index holds: a half store keeps its 16-bit rows and nothing else
-        if not self._one_buffer:
-            held["_s32"] = torch.float32
-            if self._slo is not None or ((self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)):
-                held["_slo"] = self._half_dtype
+        # the buffers this index holds: a half or 8-bit store keeps its one buffer and nothing else
+        held = {name: torch.float32 if name == "_s32" else self._scan_dtype for name in self._store.buffers}
+        if "_slo" in held and self._slo is None and not ((self.precision in ("bf16x3", "fp16x3")) if lo is None else bool(lo)):
+            del held["_slo"]
         rows = max(int(n), 0 if self._s16 is None else self._s16.shape[0])      # (all of them keep one row count)
         with torch.cuda.device(self.device):
             for name, dtype in held.items():
@@ -361,9 +323,10 @@ class _IndexStore:
                                              ptr(self._max_norm), _lib.stream_ptr()), name)
 
     def _first_rows(self, t):
-        """The first rows an empty index sees fix its centring vector and, for the fp16 scan, the power-of-two scale of the
-        scan copy (from these rows' largest centred norm: one extra pass over them and one host read per index
-        lifetime; later rows may be up to 7x longer before the copy has to be rebuilt, see _rebuild_scaled)."""
+        """The first rows an empty index sees (of a streamed add: the first chunk, >= 40 k passages) fix its centring vector --
+        any centre keeps the search exact, it only has to be close to the mean to shrink the rounding-error band -- and, for the
+        fp16 scan, the power-of-two scale of the scan copy (from these rows' largest centred norm: one extra pass over them and one
+        host read per index lifetime; later rows may be up to 7x longer before the copy has to be rebuilt, see _rebuild_scaled)."""
         if self.center:
             self._set_centre(t)
         if self.kind == "f16":
@@ -371,25 +334,14 @@ class _IndexStore:
             _lib.check(L.convdr_ip_prepare_block_f16(_lib.ptr(t), t.shape[0], self.d, _lib.ptr(self._centre), 1.0, None, None,
                                                      _lib.ptr(self._max_norm), _lib.stream_ptr()), "convdr_ip_prepare_block_f16")
             self._scale = float(L.convdr_ip_f16_scale(float(self._max_norm.item())))
+        return t
 
     def _rebuild_scaled(self):
-        """CONVDR_IP_RANGE: rows added after the scale was fixed are more than 7x longer than the first block's longest.
-        Re-derive the scale from the block's max norm and rebuild the fp16 copies from the resident fp32 rows."""
+        """CONVDR_IP_RANGE: rows added after the scale was fixed are more than 7x longer than the first block's longest: the scale
+        is re-derived from the block's max norm and the scan copy rebuilt, or the half store's rows rescaled in place."""
         import torch
-        if self._half:
-            # the half store is rescaled IN PLACE by 2^(s_new - s_old) <= 1, s_new >= 0: exact (convdr_ip_store_rows_f16)
-            new = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
-            with torch.cuda.device(self.device):
-                if self._n and new != self._scale:
-                    self._store_rows(self._pbf, self._pbf, new / self._scale, fold_norm=False)
-                    if int(self._flags.item()):
-                        raise _lib.ConvdrError("half store: the in-place rescale %g -> %g was not exact" % (self._scale, new))
-            self._scale = new
-            return
         with torch.cuda.device(self.device):
-            self._scale = float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item())))
-            if self._n:
-                self._prepare_into(self._p32, self._pbf, self._plo)
+            self._store.rescale(self)
 
     def _grow_for(self, m, want_lo=False):
         """rows [n, n + m) of the backing storage (fp32 block, scan copy, remainder copy; None for a buffer the index does not
@@ -484,118 +436,66 @@ class _IndexStore:
         return t.to(self.device).contiguous()
 
     def _add_rows(self, x, chunk_bytes=None):
-        """add() without the id column"""
+        """add() without the id column, for every store.  The description supplies what differs (stores.py): the dtypes a source may
+        keep, the room for the new rows (the fp32 store adopts the caller's device tensor as its first block), what the first rows of
+        an empty index fix, where streamed chunks land (in the store itself; later adds of the 8-bit store: one window of the staging
+        ring at a time), how rows are written, and the verdict after the add's ONE host read -- keep, refuse and restore, or, for
+        the half store only, lower the scale and write once more."""
         import time
         import torch
+        s = self._store
         chunk_bytes = int(chunk_bytes or self.host_chunk_bytes)
-        if self._half:
-            return self._add_half(x, chunk_bytes)
-        if self._sq8:
-            return self._add_sq8(x, chunk_bytes)
-        t, reader = self._source(x, chunk_bytes, np.float32, (torch.float32,))
-        m = int(t.shape[0])
+        have = str(getattr(x.array if hasattr(x, "array") else x, "dtype", "")).replace("torch.", "")
+        t, reader = self._source(x, chunk_bytes, np.dtype(have if have in s.streams and self.d == self.d_in else s.streams[-1]),
+                                 tuple(getattr(torch, name) for name in s.keeps))
+        m, n0 = int(t.shape[0]), self._n
         if m == 0:
             return
-        want_lo = self.precision in ("bf16x3", "fp16x3") or self._slo is not None
         with torch.cuda.device(self.device):
-            if isinstance(t, np.ndarray):
-                t0 = time.perf_counter()
-                p32, p16, plo = self._grow_for(m, want_lo)
-                first = self._n == 0
+            t0 = time.perf_counter() if s.clock_growth else None
+            state0 = ({a: getattr(self, a) for a in s.fixes}, self._mf.clone()) if s.words else None
+            host = isinstance(t, np.ndarray)
+            bounce = functools.partial(torch.empty, dtype=getattr(torch, t.dtype.name), device=self.device) if host else None
+            if host and n0 == 0 and s.first_needs_all:
+                # a host array goes whole into a transient buffer of the add's size (the 8-bit store: 4 d bytes per row for fp32
+                # input, 2 d for fp16 -- build a large index from a first block it can afford)
+                tmp = bounce((m, self.d))
+                self._stream_rows(t, tmp, reader, chunk_bytes, lambda ci, lo, hi: None)
+                t, host = tmp, False
+            dst = s.room(self, t, m)
 
-                def prepare(ci, s, e):
-                    if first and ci == 0:
-                        # centre = column mean of the first chunk (>= 40 k passages): any centre keeps the search exact -- it
-                        # shifts every score of a query by the same constant -- it only has to be close to the mean to shrink
-                        # the rounding-error band; likewise the fp16 scale comes from the first chunk's norms
-                        self._first_rows(p32[s:e])
-                    self._prepare_into(p32[s:e], p16[s:e], plo[s:e] if plo is not None else None)
-                self._stream_rows(t, p32, reader, chunk_bytes, prepare, t0)
-            else:
-                if self._n == 0:
-                    self._first_rows(t)
-                if self._s32 is None and not want_lo:
-                    # first block of an unreserved index: adopt the caller's device tensor instead of copying it
-                    self._s32 = t
-                    self._s16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
-                    dst32, dst16, dstlo = self._s32, self._s16, None
+            def resident(rows, lo, hi):         # landed rows -> rows [lo, hi) of the new resident ones
+                p32, p16, plo = (None if b is None else b[lo:hi] for b in dst)
+                if p32 is not None and rows.data_ptr() != p32.data_ptr():       # (streamed chunks landed in the block, an adopted
+                    p32.copy_(rows)                                             #  tensor is the block)
+                s.write(self, rows if p32 is None else p32, p16, plo)
+            for attempt in (0, 1):
+                fresh = n0 == 0 and not attempt
+                if host:
+                    land, win = s.landing(self, t, dst, chunk_bytes)
+                    land = bounce((min(win, m), self.d)) if land is None else land
+                    for a in range(0, m, win):
+                        def each(ci, lo, hi, a=a):
+                            if fresh and a == 0 and ci == 0:
+                                s.first(self, land[lo:hi])
+                            resident(land[lo:hi], a + lo, a + hi)
+                        rd = None if reader is None else (lambda buf, lo, hi, a=a, **kw: reader(buf, a + lo, a + hi, **kw))
+                        self._stream_rows(t[a:a + win], land[:min(m, a + win) - a], rd, chunk_bytes, each, t0)
                 else:
-                    dst32, dst16, dstlo = self._grow_for(m, want_lo)
-                    dst32.copy_(t)
-                self._prepare_into(dst32, dst16, dstlo)
-        self._n += m
-
-    # -- the 8-bit store (storage="sq8") -----------------------------------------
-    def _refuse_sq8(self, who):
-        """ValueError for an entry the 8-bit store does not offer, before anything is launched"""
-        if self._sq8:
-            raise ValueError("FlatIPIndex(storage='sq8').%s: not offered by the 8-bit store (storage='sq8'); use storage='fp32' or "
-                             "'fp16'" % who)
-
-    def _add_sq8(self, x, chunk_bytes):
-        """add() of an 8-bit store: fp32 rows (fp16 rows are widened, exactly) -> int8 codes, convdr_ip_store_rows_q8.
-        The FIRST add fixes the centre (column mean) and the step (largest column deviation / 127) from ITS rows, all of them,
-        so a host array of a first add is streamed into a transient device buffer of the add's size (4 d bytes per row for
-        fp32 input, 2 d for fp16) before anything is quantised: build a large index from a first block it can afford.
-        LATER adds of a host array (fp32 or fp16, through the staging buffers) are quantised chunk by chunk under the next
-        chunk's copy: the transient memory is one window of host_stage_buffers chunks, whatever the add's size.  The L1 norm,
-        the flag word and the saturation count are read ONCE, at the end: a value that is not finite refuses the add and
-        leaves the index exactly as it was (the codes it wrote lie behind ntotal)."""
-        import torch
-        src = x.array if hasattr(x, "array") else x
-        is16 = getattr(src, "dtype", None) in (np.float16, torch.float16) and self.d == self.d_in
-        t, reader = self._source(x, chunk_bytes, np.float16 if is16 else np.float32, (torch.float32, torch.float16))
-        m = int(t.shape[0])
-        if m == 0:
-            return
-        L, ptr = _lib.lib(), _lib.ptr
-        n0, first = self._n, self._n == 0
-
-        def quantise(rows, dst):
-            rows = rows if rows.dtype == torch.float32 else rows.float()
-            _lib.check(L.convdr_ip_store_rows_q8(ptr(rows), int(rows.shape[0]), self.d, ptr(self._centre), ptr(self._step), ptr(dst),
-                                                 ptr(self._max_norm), ptr(self._flags), ptr(self._sat), _lib.stream_ptr()),
-                       "convdr_ip_store_rows_q8")
-        with torch.cuda.device(self.device):
-            state0 = (self._centre, self._step, self._mf.clone())
-            dst = self._grow_for(m)[1]
-            if isinstance(t, np.ndarray) and not first:
-                # windows of the staging ring's size: the copy stream waits for the main stream at the start of every window
-                # (_stream_rows), i.e. for the quantisation of the window before, so ONE bounce buffer serves them all
-                per = max(1, int(chunk_bytes) // (4 * self.d)) * 4 // t.dtype.itemsize
-                win = per * max(2, int(self.host_stage_buffers))
-                tmp = torch.empty((min(win, m), self.d), dtype=torch.float16 if is16 else torch.float32, device=self.device)
-                for a in range(0, m, win):
-                    b = min(m, a + win)
-                    rd = None if reader is None else (lambda buf, s, e, a=a, **kw: reader(buf, a + s, a + e, **kw))
-                    self._stream_rows(t[a:b], tmp[:b - a], rd, chunk_bytes,
-                                      lambda ci, s, e, a=a: quantise(tmp[s:e], dst[a + s:a + e]))
-            else:
-                if isinstance(t, np.ndarray):
-                    tmp = torch.empty((m, self.d), dtype=torch.float16 if is16 else torch.float32, device=self.device)
-                    self._stream_rows(t, tmp, reader, chunk_bytes, lambda ci, s, e: None)
-                    t = tmp
-                if t.dtype != torch.float32:
-                    t = t.float()
-                if first:
-                    self._set_centre(t)
-                    self._step = torch.empty(self.d, dtype=torch.float32, device=self.device)
-                    scratch = torch.empty(1024 * self.d, dtype=torch.float32, device=self.device)
-                    _lib.check(L.convdr_ip_column_absdev(ptr(t), m, self.d, ptr(self._centre), ptr(scratch), ptr(self._step),
-                                                         _lib.stream_ptr()), "convdr_ip_column_absdev")
-                quantise(t, dst)
-            got = self._mf[1:].view(torch.int32).cpu()                      # the one host read of this add()
-            fl, sat = int(got[0]), int(got[1]) & 0xffffffff
-            self._mf[1:].zero_()
-            if fl & 1:
-                self._centre, self._step = state0[0], state0[1]
-                self._mf.copy_(state0[2])
-                raise _lib.ConvdrError("FlatIPIndex(storage='sq8').add: a value is not finite; the index is unchanged (%d rows)" % n0)
-            self._saturated += sat
-            self.stats["sq8_saturated"] = self._saturated
+                    resident(s.first(self, t) if fresh else t, 0, m)
+                if s.verdict(self, n0, state0, attempt):
+                    break
             self._n = n0 + m
 
-    # -- the half store (storage="fp16") ----------------------------------------
+    def _restore(self, state0):
+        """what a refused add puts back: what the first rows fixed, and the max norm with its words"""
+        for name, value in state0[0].items():
+            setattr(self, name, value)
+        self._mf.copy_(state0[1])
+
+    def _add_half(self, x, chunk_bytes):
+        return self._add_rows(x, chunk_bytes)
+
     def _store_rows(self, src, dst, scale, fold_norm=True, flags=None):
         """convdr_ip_store_rows_f16: dst = half(src) * scale (dst None: norms and the non-finite flag only)"""
         import torch
@@ -613,50 +513,7 @@ class _IndexStore:
         """An empty half store takes its scale from the first rows' largest norm (one pass, one host read), never below 1."""
         self._store_rows(src, None, 1.0)
         self._scale = max(1.0, float(_lib.lib().convdr_ip_f16_scale(float(self._max_norm.item()))))
-
-    def _add_half(self, x, chunk_bytes):
-        """add() of a half store.  `write(dst)` below puts the new rows into dst = store[n, n + m) (rounded, scaled, norms
-        and flags folded); the flag word and the max norm are read ONCE, at the end, and decide: keep, refuse (the index is
-        left exactly as it was), or -- a scaled value overflowed: the new rows are too long for the scale -- lower the scale,
-        rescale the resident rows in place and write the new rows once more (the only case with a second read)."""
-        import torch
-        t, reader = self._source(x, chunk_bytes, np.float16, (torch.float16, torch.float32))
-        m = int(t.shape[0])
-
-        def write(dst, first):
-            if not isinstance(t, np.ndarray):
-                if first:
-                    self._half_first_scale(t)
-                return self._store_rows(t, dst, self._scale)
-
-            def scale_in_place(ci, s, e):       # the copy stream wrote the halves straight into the store
-                if first and ci == 0:
-                    self._half_first_scale(dst[s:e])
-                self._store_rows(dst[s:e], dst[s:e], self._scale)
-            self._stream_rows(t, dst, reader, chunk_bytes, scale_in_place)
-        if m == 0:
-            return
-        n0, scale0 = self._n, self._scale
-        with torch.cuda.device(self.device):
-            mn0 = self._max_norm.clone()
-            dst = self._grow_for(m)[1]
-            for attempt in (0, 1):
-                write(dst, n0 == 0 and attempt == 0)
-                got = self._mf[:2].cpu()                                    # the one host read of this add()
-                mn, fl = float(got[0]), int(got.view(torch.int32)[1])
-                self._flags.zero_()
-                if (fl & 1) or not mn <= HALF_NORM_LIMIT:
-                    self._scale = scale0
-                    self._max_norm.copy_(mn0)
-                    raise _lib.ConvdrError("FlatIPIndex(storage='fp16').add: %s; the index is unchanged (%d rows)"
-                                           % ("a value is not finite as a half" if fl & 1 else
-                                              "a row's norm %g exceeds %g" % (mn, HALF_NORM_LIMIT), n0))
-                if not (fl & 2):
-                    break
-                if attempt:
-                    raise _lib.ConvdrError("half store: scaled values overflow at scale %g, max norm %g" % (self._scale, mn))
-                self._rebuild_scaled()          # the scale that fits the new max norm; rows [0, n0) rescaled in place
-            self._n = n0 + m
+        return src
 
     def _stream_rows(self, arr, dst, reader, chunk_bytes, each, t0=None):
         """Host rows `arr` -> device rows `dst` (same shape and element type) through the pinned staging buffers -- viewed as
@@ -678,8 +535,7 @@ class _IndexStore:
         stage = [b.view(dst.dtype).view(-1, d) for b in stage]
         cs = self._copy_stream
         cs.wait_stream(main)                    # (allocation order / the copy of the old rows in _grow_for)
-        avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-        threads = max(1, min(int(self.host_copy_threads), avail))
+        threads = self._copy_threads()
         pool = _copy_pool(threads * (nbuf - 1), self.device)
         chunks = [(s, min(n, s + rows_per)) for s in range(0, n, rows_per)]
 
@@ -730,18 +586,22 @@ class _IndexStore:
         return torch.nn.functional.pad(t, (0, self.d - self.d_in))
 
     def _set_centre(self, t):
+        self._centre = self._max_norm.new_empty(self.d)         # (fp32, on the index's device)
+        self._column_pass("convdr_ip_column_mean", t, (), self._centre)
+
+    def _column_pass(self, name, t, given, out):
+        """convdr_ip_column_mean / _absdev over the fp32 rows `t` into out [d]; given: the vector arguments before the scratch"""
         import torch
-        self._centre = torch.empty(self.d, dtype=torch.float32, device=self.device)
         scratch = torch.empty(1024 * self.d, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().convdr_ip_column_mean(_lib.ptr(t), t.shape[0], self.d, _lib.ptr(scratch),
-                                                   _lib.ptr(self._centre), _lib.stream_ptr()), "convdr_ip_column_mean")
+        _lib.check(getattr(_lib.lib(), name)(_lib.ptr(t), t.shape[0], self.d, *given, _lib.ptr(scratch), _lib.ptr(out),
+                                             _lib.stream_ptr()), name)
 
     def _ensure_lo(self):
         """Remainder copy for the split scan, built on first use."""
         import torch
-        if not self._half and self._slo is None and self._s32 is not None:
+        if self._slo is None and self._s32 is not None:      # (a store without an fp32 block has no remainder copy)
             with torch.cuda.device(self.device):
-                self._slo = torch.empty((self._s32.shape[0], self.d), dtype=self._half_dtype, device=self.device)
+                self._slo = torch.empty((self._s32.shape[0], self.d), dtype=self._scan_dtype, device=self.device)
                 if self._n:
                     self._prepare_into(self._p32, self._pbf, self._plo)
 
@@ -749,21 +609,19 @@ class _IndexStore:
         """Overwrite rows [row0, row0 + len(emb)) of the resident block with freshly encoded embeddings
         (device fp32 [m, d]) and refresh their scan copy / the block's max norm.  No sync."""
         import torch
-        self._refuse_sq8("update_rows")
+        self._store.refuse(self, "update_rows")
         m = int(emb.shape[0])
         assert emb.dtype == torch.float32 and emb.is_contiguous() and row0 + m <= self.ntotal
-        if self._half:
-            # the new rows are rounded to half and scaled; a row the store cannot hold is an error AFTER the write (the caller
-            # owns the rows it overwrites), a scale the rows outgrow is CONVDR_IP_RANGE at the next search, as for add()
-            src = emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))
-            with torch.cuda.device(self.device):
-                self._store_rows(src.contiguous(), self._pbf[row0:row0 + m], self._scale, flags=self._uflags)
-            return
-        dst32, dstbf = self._p32[row0:row0 + m], self._pbf[row0:row0 + m]
-        dstlo = None if self._slo is None else self._plo[row0:row0 + m]
-        dst32[:, :self.d_in].copy_(emb)      # (zero columns of a padded width stay zero)
+        dst16, dstlo = self._pbf[row0:row0 + m], None if self._slo is None else self._plo[row0:row0 + m]
+        if self._s32 is None:
+            # the half store: the new rows are rounded to half and scaled; a row the store cannot hold is an error AFTER the write
+            # (the caller owns the rows it overwrites), a scale the rows outgrow is CONVDR_IP_RANGE at the next search, as for add()
+            src = (emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))).contiguous()
+        else:
+            src = self._p32[row0:row0 + m]
+            src[:, :self.d_in].copy_(emb)        # (zero columns of a padded width stay zero)
         with torch.cuda.device(self.device):
-            self._prepare_into(dst32, dstbf, dstlo)
+            self._store.write(self, src, dst16, dstlo, update=True)
 
     def row_filter(self, mask):
         """A RowFilter of this index from a bool / uint8 vector [ntotal] (numpy or torch, host or device; non-zero = allowed):
@@ -1038,7 +896,7 @@ class _IndexStore:
         (n_updated, n_added).  A list that repeats an id, or an id that sits on more than one row (chunk rows: which one?),
         raises ValueError BEFORE anything is written -- one host read, the one that also splits the list."""
         import torch
-        self._refuse_sq8("upsert")
+        self._store.refuse(self, "upsert")
         t, first, count, dup, ws, status = self._locate("upsert", ids, want_dup=True)
         m = int(t.numel())
         self._emb_arg("upsert", emb, m)
@@ -1064,17 +922,12 @@ class _IndexStore:
         import torch
         m = int(emb.shape[0])
         src = (emb if self.d == self.d_in else torch.nn.functional.pad(emb, (0, self.d - self.d_in))).contiguous()
-        t16 = torch.empty((m, self.d), dtype=self._half_dtype, device=self.device)
-        if self._half:
-            self._store_rows(src, t16, self._scale, flags=self._uflags)
-            self._s16.index_copy_(0, rows, t16)
-            return
+        t16 = torch.empty((m, self.d), dtype=self._scan_dtype, device=self.device)
         tlo = None if self._slo is None else torch.empty_like(t16)
-        self._prepare_into(src, t16, tlo)
-        self._s32.index_copy_(0, rows, src)
-        self._s16.index_copy_(0, rows, t16)
-        if tlo is not None:
-            self._slo.index_copy_(0, rows, tlo)
+        self._store.write(self, src, t16, tlo, update=True)
+        for buf, new in ((self._s32, src), (self._s16, t16), (self._slo, tlo)):
+            if buf is not None:
+                buf.index_copy_(0, rows, new)
 
     # -- documents by id: a document is EVERY row that carries one id (the chunk rows of a MaxP block share theirs) ----------
     # Two device primitives (include/convdr_hip.h, "Documents by id"): all rows of the listed ids as a CSR
@@ -1235,7 +1088,7 @@ class _IndexStore:
         removed and others added, so a RowFilter built before the call must not be reused even where ntotal happens to come
         out equal -- the staleness check compares ntotal only.  Side tables in row order are cut as for keep_rows."""
         import torch
-        self._refuse_sq8("upsert_docs")
+        self._store.refuse(self, "upsert_docs")
         self._need_ids("upsert_docs")
         t = self._id_list("upsert_docs", ids)
         m = int(t.numel())
@@ -1293,11 +1146,7 @@ class _IndexStore:
         if self._rows is None:
             return torch.empty(tuple(t.shape) + (self.d_in,), dtype=torch.float32, device=self.device)
         r = self._rows[t.reshape(-1)][:, :self.d_in]
-        if self._sq8:
-            # v = fl(centre + fl(step c)): two torch ops, each rounded to fp32 (nothing fuses them)
-            r = self._centre[:self.d_in] + self._step[:self.d_in] * r.float()
-        if self._half:
-            r = r.float() * (1.0 / float(self._scale))     # (a power of two: exact)
+        r = self._store.widen(self, r)
         return r.reshape(tuple(t.shape) + (self.d_in,)).contiguous()
 
     def reconstruct(self, i):
@@ -1321,13 +1170,10 @@ class _IndexStore:
     # are rebuilt by load as add builds them; RowFilter / DocOrdinals are derived and stale across a save / load.
     def _sections(self):
         """[(name, device tensor of the used rows or None, rows, row_bytes)] of what a snapshot holds, in file order"""
-        secs = [("rows", self._rows, self._n, self.d * (1 if self._sq8 else (2 if self._half else 4)))]
+        secs = [("rows", self._rows, self._n, self.d * self._store.esize)]
         if self._sid is not None:
             secs.append(("ids", self.ids, self._n, 8))
-        if self._centre is not None:
-            secs.append(("centre", self._centre, 1, self.d * 4))
-        if self._sq8 and self._step is not None:
-            secs.append(("step", self._step, 1, self.d * 4))
+        secs += [(name, getattr(self, "_" + name), 1, self.d * 4) for name in self._store.vectors if getattr(self, "_" + name) is not None]
         return secs
 
     def _digest_into(self, t, rows, row_bytes, word0, window_rows, out):
@@ -1371,10 +1217,9 @@ class _IndexStore:
             got, mn = self._digest_read(dg, spans)
         fp = {"d_in": self.d_in, "storage": self.storage, "precision": self.precision, "center": self.center, "n": self._n,
               "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "%08x" % mn}
-        for name in ("rows", "ids", "centre") + (("step",) if self._sq8 else ()):
+        for name in ("rows", "ids") + self._store.vectors:
             fp[name] = None if name not in got else (got[name][0] if got[name] else (0, 0))
-        if self._sq8:
-            fp["sq8_saturated"] = self._saturated
+        fp.update({key: getattr(self, attr) for key, attr in self._store.counters})
         return fp
 
     def _stage_bytes(self, total):
@@ -1495,8 +1340,8 @@ class _IndexStore:
         meta = {"d_in": self.d_in, "d": self.d, "storage": self.storage, "precision": self.precision, "center": self.center,
                 "n": self._n, "scale": "%08x" % struct.unpack("<I", struct.pack("<f", float(self._scale)))[0], "max_norm": "0" * 8,
                 "x3_first": bool(self._x3_first), "has_ids": self._sid is not None, "window_rows": w}
-        if self._sq8:       # (max_norm holds the largest row L1 norm of the codes)
-            meta["sq8_saturated"] = int(self._saturated)
+        # (the 8-bit store: max_norm holds the largest row L1 norm of the codes, and the saturation count rides along)
+        meta.update({key: int(getattr(self, attr)) for key, attr in self._store.counters})
         timings = {}
         with torch.cuda.device(self.device):
             dg, spans = self._digest_sections(secs, w)
@@ -1540,21 +1385,19 @@ class _IndexStore:
         if not (0 <= r0 <= r1 <= n_file) or r0 % w or (r1 % w and r1 != n_file):
             raise ValueError("load: rows=(%d, %d) must lie in [0, n = %d], r0 a multiple of the file's window_rows = %d and r1 a "
                              "multiple of it or n" % (r0, r1, n_file, w))
-        half, sq8 = h["storage"] == "fp16", h["storage"] == "sq8"
+        store = STORES[h["storage"]]
         precision = h["precision"] if precision is None else precision
-        if (precision not in _SQ8_PRECISIONS) if sq8 else (precision not in _KINDS or precision == "i8" or (not half and precision == "fp16x2")):
+        if precision not in store.precisions:
             raise ValueError("load: precision %r is none of the %s store's" % (precision, h["storage"]))
         idx = cls(int(h["d_in"]), device=device, cap=cap, rank_target=rank_target, precision=precision,
-                  center=None if (half or sq8) else bool(h["center"]), prepin=prepin, storage=h["storage"])
-        n, esz = r1 - r0, 1 if sq8 else (2 if half else 4)
-        rb = idx.d * esz
+                  center=None if store.centred is not None else bool(h["center"]), prepin=prepin, storage=h["storage"])
+        n, rb = r1 - r0, idx.d * store.esize
         want = {"rows": (n_file * rb, rb)}
         if h["has_ids"]:
             want["ids"] = (n_file * 8, 8)
-        if "centre" in secs:
-            want["centre"] = (idx.d * 4, idx.d * 4)
-        if sq8 and n_file:
-            want["step"] = (idx.d * 4, idx.d * 4)
+        for name in store.vectors:      # (the centre of an index that has one; the vectors behind it whenever there are rows)
+            if name in secs if name == "centre" else n_file:
+                want[name] = (idx.d * 4, idx.d * 4)
         for name, (nbytes, rbytes) in want.items():
             if name not in secs or (secs[name]["bytes"], secs[name]["row_bytes"]) != (nbytes, rbytes) or int(h["d"]) != idx.d:
                 raise _lib.ConvdrError("load %s: section %r does not have the %d bytes of %d-byte rows the header's n, d and storage "
@@ -1564,22 +1407,20 @@ class _IndexStore:
         L = _lib.lib()
         mn_bits = int(h["max_norm"], 16)
         scale = struct.unpack("<f", struct.pack("<I", int(h["scale"], 16)))[0]
-        if not half and idx.kind != _KINDS[h["precision"]]:
+        if idx.kind != (store.kind or _KINDS[h["precision"]]):
             # another scan kind: the scale that fits the saved max norm, as _rebuild_scaled derives it (bf16 has none)
             scale = float(L.convdr_ip_f16_scale(struct.unpack("<f", struct.pack("<I", mn_bits))[0])) if idx.kind == "f16" else 1.0
         fd = os.open(path, os.O_RDONLY)
         try:
             with torch.cuda.device(idx.device):
-                if "centre" in secs:
-                    c = np.empty(idx.d, dtype=np.float32)
-                    snapshot.pread_into(fd, memoryview(c).cast("B"), secs["centre"]["offset"])
-                    idx._centre = torch.from_numpy(c).to(idx.device)
-                if sq8 and "step" in secs:
-                    c = np.empty(idx.d, dtype=np.float32)
-                    snapshot.pread_into(fd, memoryview(c).cast("B"), secs["step"]["offset"])
-                    idx._step = torch.from_numpy(c).to(idx.device)
-                    idx._saturated = int(h.get("sq8_saturated", 0))
-                    idx.stats["sq8_saturated"] = idx._saturated
+                for name in store.vectors:
+                    if name in secs:
+                        c = np.empty(idx.d, dtype=np.float32)
+                        snapshot.pread_into(fd, memoryview(c).cast("B"), secs[name]["offset"])
+                        setattr(idx, "_" + name, torch.from_numpy(c).to(idx.device))
+                for key, attr in (store.counters if store.vectors[-1] in secs else ()):     # (they travel with the last vector)
+                    setattr(idx, attr, int(h.get(key, 0)))
+                    idx.stats[key] = getattr(idx, attr)
                 idx._scale, idx._x3_first = scale, bool(h["x3_first"])
                 # (copy_ INTO the tensor: the half store's max norm is a view of its (norm, flags) triple and must stay one)
                 idx._max_norm.copy_(torch.tensor([mn_bits - (1 << 32) if mn_bits >> 31 else mn_bits], dtype=torch.int32).view(torch.float32))
@@ -1589,14 +1430,12 @@ class _IndexStore:
                     idx._reserved = reserve is not None
                 if n:
                     src = snapshot.FileRows(fd, secs["rows"]["offset"], rb, r0, n, idx.d)
-                    if half or sq8:
-                        idx._stream_rows(src, idx._s16[:n], src.read_rows_into, idx.host_chunk_bytes, lambda ci, s, e: None, t0)
-                    else:
-                        p32, p16, plo = idx._s32[:n], idx._s16[:n], None if idx._slo is None else idx._slo[:n]
-
-                        def prepare(ci, s, e):              # (never _first_rows: centre and scale are the saved ones)
-                            idx._prepare_into(p32[s:e], p16[s:e], None if plo is None else plo[s:e])
-                        idx._stream_rows(src, p32, src.read_rows_into, idx.host_chunk_bytes, prepare, t0)
+                    # (never the store's `first`: centre and scale are the saved ones; rows that are the store land in it and no
+                    #  kernel runs)
+                    dst = tuple(None if b is None else b[:n] for b in (idx._s32, idx._s16, idx._slo))
+                    each = (lambda ci, s, e: None) if dst[0] is None else (
+                        lambda ci, s, e: idx._prepare_into(*(None if b is None else b[s:e] for b in dst)))
+                    idx._stream_rows(src, dst[1] if dst[0] is None else dst[0], src.read_rows_into, idx.host_chunk_bytes, each, t0)
                 idx._n = n
                 if h["has_ids"]:
                     idx._sid, idx._sid_spare = torch.empty(max(room, 0), dtype=torch.int64, device=idx.device), None

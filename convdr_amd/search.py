@@ -21,7 +21,7 @@ from . import _lib
 from .block_search import (EvalDevQuery, _check_distinct_certificate, _load_collection, _Passages, _search_block_list, load_block,
                            search_distinct_one_by_one, search_one_by_one)
 from .index_store import (_HALF_PRECISIONS, _KINDS, EXCLUDE_MAX, HALF_NORM_LIMIT, KEY_ST_COLUMN, KEY_ST_LIST, KEY_ST_NOSET, KEY_ST_PROBE,
-                          RESERVED_ID, ROW_FILTER_TILE, DocOrdinals, QueryExclusions, RowFilter, _IndexStore, pack_exclusions, pack_row_mask)
+                          RESERVED_ID, ROW_FILTER_TILE, STORES, DocOrdinals, QueryExclusions, RowFilter, _IndexStore, pack_exclusions, pack_row_mask)
 from .snapshot import read_header as snapshot_info, verify_file as verify_snapshot
 from .staging import (_NUMA, _POOLS, _STAGING, _STAGING_BUILD, _STAGING_LOCK, _STAGING_THREADS, _copy_pool, _on_cpus, _staging, _staging_key,
                       gpu_numa_cpus, pinned_near)
@@ -117,7 +117,7 @@ class FlatIPIndex(_IndexStore):
         the id -1.  Re-ranking a list of documents (BM25 candidates, a known positive) needs no id -> row map on the host:
         one key set and one CSR over the flattened list, one score launch, one host read (the CSR's size)."""
         import torch
-        self._refuse_sq8("score_ids")
+        self._store.refuse(self, "score_ids")
         self._need_ids("score_ids")
         qt, it, shape = self._ids_arg("score_ids", q, ids)
         nq, m = int(qt.shape[0]), (shape[1] if len(shape) == 2 else 1)
@@ -154,7 +154,7 @@ class FlatIPIndex(_IndexStore):
         return self._search_docs(q, k, allowed, depth, strict, max_depth, None)
 
     def _search_docs(self, q, k, allowed, depth, strict, max_depth, exclude):
-        self._refuse_sq8("search_docs")
+        self._store.refuse(self, "search_docs")
         self._need_ids("search_docs")
         D, I, K, counts = self._search_distinct_rows(q, k, self.ids, depth, strict, max_depth, allowed, exclude)
         return D, K, I, counts
@@ -176,49 +176,23 @@ class FlatIPIndex(_IndexStore):
             return D, I
         return D, torch.where(I >= 0, self.ids[I.clamp(min=0)], torch.full_like(I, -1))
 
-    # CONVDR_IP_RANGE from a bf16 scan: nothing rebuilds it away (the bf16 copy has no scale), so every entry ends with this
-    _BF16_RANGE = ("CONVDR_IP_RANGE from the bf16 scan: a query or the block has a non-zero norm below 2^-60, where bf16 operands "
-                   "and their products are subnormal and the scan's error bound does not hold; use precision=\"auto\" or "
-                   "\"fp16\", whose scan rescales both operands")
-
-    _SQ8_RANGE = ("CONVDR_IP_RANGE from the 8-bit store's scan: a query holds a value that is not finite, or its largest |q_j step_j| "
-                  "is non-zero and below 2^-100, where the integer query operand has no relative precision")
-
-    @property
-    def _range_message(self):
-        return self._SQ8_RANGE if self._sq8 else self._BF16_RANGE
-
     def _search_call(self, q, nq, p32, p16, plo, n, k, tau_in, cap, rank_target, ws, D, I, status, tau_retry, split=False,
                      deep=False, allowed=None):
-        """One call of convdr_ip_search[_deep][_f16 | _h16]: the entry of this index's scan copy and of the depth; with a
-        RowFilter, convdr_ip_search_filtered with the same operands."""
+        """One call of convdr_ip_search[_deep][_f16 | _h16 | _q8]: the entry of this index's scan copy and of the depth, each with
+        the operands it declares (the store description's `call`); with a RowFilter, convdr_ip_search_filtered[_q8] with the same
+        operands."""
         ptr = _lib.ptr
-        if self._sq8:
-            # the 8-bit store's entries: codes, centre, step; the largest row L1 norm of the codes in the max norm's place
-            L, ent = _lib.lib(), "convdr_ip_search_deep_q8" if deep else "convdr_ip_search_q8"
-            rows = (ptr(p16), ptr(self._centre), ptr(self._step), n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target,
-                    ptr(ws), ws.numel())
-            out = (ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr())
-            if allowed is not None:
-                _lib.check(L.convdr_ip_search_filtered_q8(int(bool(deep)), ptr(q), nq, *rows, ptr(allowed.bits), allowed.bits.numel(),
-                                                          allowed.n_allowed, *out), "convdr_ip_search_filtered_q8")
-            else:
-                _lib.check(getattr(L, ent)(ptr(q), nq, *rows, *out), ent)
-            return
-        store, r32, r16, scale, _ = self._operands((p32, p16))
-        rlo, split = None if self._half else ptr(plo), int(bool(split)) if self._half else 0
+        what = "search" if allowed is None else "filtered"
+        suffix, head, rows = self._store.call(what, self._operands((p32, p16)), plo, split)
+        tail = (n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target, ptr(ws), ws.numel())
+        out = (ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr())
         if allowed is not None:
-            _lib.check(_lib.lib().convdr_ip_search_filtered(
-                store, int(bool(deep)), ptr(q), nq, r32, r16, rlo, scale, split, n, self.d, k, ptr(self._max_norm),
-                ptr(tau_in), cap, rank_target, ptr(ws), ws.numel(), ptr(allowed.bits), allowed.bits.numel(), allowed.n_allowed,
-                ptr(D), ptr(I), ptr(status), ptr(tau_retry), _lib.stream_ptr()), "convdr_ip_search_filtered")
-            return
-        # the direct entry of the store code, each with the operands it declares
-        name, rows = (("", (r32, r16, rlo)), ("_f16", (r32, r16, rlo, scale)), ("_h16", (r16, scale, split)))[store]
-        name = "convdr_ip_search" + ("_deep" if deep else "") + name
-        _lib.check(getattr(_lib.lib(), name)(ptr(q), nq, *rows, n, self.d, k, ptr(self._max_norm), ptr(tau_in), cap, rank_target,
-                                             ptr(ws), ws.numel(), ptr(D), ptr(I), ptr(status), ptr(tau_retry),
-                                             _lib.stream_ptr()), name)
+            name = "convdr_ip_search_filtered" + suffix
+            _lib.check(getattr(_lib.lib(), name)(*head, int(bool(deep)), ptr(q), nq, *rows, *tail, ptr(allowed.bits), allowed.bits.numel(),
+                                                 allowed.n_allowed, *out), name)
+        else:
+            name = "convdr_ip_search" + ("_deep" if deep else "") + suffix
+            _lib.check(getattr(_lib.lib(), name)(ptr(q), nq, *rows, *tail, *out), name)
 
     def _enqueue(self, q, k, tau_in, cap, x3, deep=False, rows=None, rank_target=None, allowed=None):
         """One enqueue of the kernel pipeline, shallow or deep, over the resident block or over `rows` = (re-score rows, scan
@@ -369,17 +343,16 @@ class FlatIPIndex(_IndexStore):
         enqueue = functools.partial(getattr(self, depth.enqueue), **kw)
         D, I, status, tau_retry = first
         n_range, n_bad = torch.stack([(status == STATUS_RANGE).sum(), (status != 0).sum()]).tolist()   # one host round trip
-        if n_range and self.kind != "f16":
-            raise _lib.ConvdrError("convdr_ip_search: " + self._range_message)     # no threshold and no retry changes this verdict
-        if self.kind == "f16" and n_range:
+        if n_range and self._store.final_range(self):
+            raise _lib.ConvdrError("convdr_ip_search: " + self._store.final_range(self))     # no threshold and no retry changes this verdict
+        if n_range:
             self._rebuild_scaled()
             self.stats["rescaled"] = 1
             D, I, status, tau_retry = enqueue(qt, k, cap=cap, x3=x3)
             n_bad = int((status != 0).sum().item())
         self.stats["retried"] = int(n_bad)
-        if self._sq8:       # queries the first integer pass certified; the values later adds saturated
-            self.stats.update(sq8_first_pass=nq - int(n_bad), sq8_saturated=self._saturated)
-        second = self.precision == "auto" and not x3 and not self._sq8      # the split scan is still ahead (the 8-bit store has one rung)
+        self.stats.update(self._store.search_stats(self, nq, n_bad))
+        second = self.precision == "auto" and not x3 and self._store.second_rung      # the split scan is still ahead
         bad = []
         if n_bad and second and depth.shortcut:
             # a band that already covers every emitted candidate only grows with a lower threshold: those queries go
@@ -430,8 +403,7 @@ class FlatIPIndex(_IndexStore):
         for each call.  ``idx.excluding(ex).search(Q, k, allowed=f)`` is the exact top-k of the (allowed) rows that query j does
         not exclude; likewise search_tensors, search_begin, search_ids(_tensors), search_docs, range_search(_tensors),
         range_count and rank_rows(_tensors)."""
-        if getattr(self, "_sq8", False):    # (getattr: tests/test_exclude_cpu.py calls this method on a plain string)
-            self._refuse_sq8("excluding")
+        self._store.refuse(self, "excluding")
         return ExcludedSearch(self, exclude)
 
     def _search_begin_excluded(self, q, k, allowed, exclude):
@@ -500,7 +472,7 @@ class FlatIPIndex(_IndexStore):
         exclude (``excluding(ex).search_docs``): per-query exclusions handed to the row search, sub-selected to the open queries.  The list
         that comes back is a complete prefix of the residual order, so the certificate is the same one."""
         import torch
-        self._refuse_sq8("search_distinct")
+        self._store.refuse(self, "search_distinct")
         qt = torch.as_tensor(q)
         k, nq, nt = int(k), int(qt.shape[0]), self.ntotal
         max_depth = _check_max_depth("search_distinct", max_depth)
@@ -557,7 +529,7 @@ class FlatIPIndex(_IndexStore):
     @property
     def _split_key(self):
         """stats key that counts the queries of the second rung: the three-pass split scan, or the half store's two passes"""
-        return "x2_queries" if self._half else "x3_queries"
+        return self._store.split_key
 
     MAX_K, DEEP_MAX_K = MAX_K, DEEP_MAX_K        # convdr_ip_search / _deep: k <= cap / 2, cap <= 8192 / 131072
     DEEP_MIN_CAP, DEEP_MAX_CAP = 16384, 131072
@@ -590,8 +562,8 @@ class FlatIPIndex(_IndexStore):
         (no threshold pass, tau = -inf), so the result is exact by construction."""
         D, I, status, _ = self._enqueue(qq, kq, None, cap, False, rows=rows, rank_target=0)
         if int((status != 0).sum().item()):
-            if self.kind != "f16" and int((status == STATUS_RANGE).sum().item()):
-                raise _lib.ConvdrError("convdr_ip_search: " + self._range_message)
+            if self._store.final_range(self) and int((status == STATUS_RANGE).sum().item()):
+                raise _lib.ConvdrError("convdr_ip_search: " + self._store.final_range(self))
             raise _lib.ConvdrError("convdr_ip_search: exhaustive slice of %d rows not certified" % rows[1].shape[0])
         return D, I
 
@@ -714,13 +686,13 @@ class FlatIPIndex(_IndexStore):
         the device by the fp64 scores.  Memory bound of that rung: the result itself (fp64 score, row and query number per
         result row while merging) beside one call's workspace, which stays under DEEP_WS_BYTES.
         ``stats``: range_results, range_rounds (passes), range_cap (the longest list used), range_chunked_queries."""
-        self._refuse_sq8("range_search")
+        self._store.refuse(self, "range_search")
         return self._range(q, radius, allowed, False)
 
     def range_count(self, q, radius, allowed=None):
         """int64 numpy [nq]: how many rows ``range_search`` would return per query, without ordering or packing them
         (1 + range_count(q, score of a known positive) is that positive's exact rank in the whole index)."""
-        self._refuse_sq8("range_count")
+        self._store.refuse(self, "range_count")
         return self._range(q, radius, allowed, True)
 
     def _excluded_ahead(self, ex, f, qt, pairq, x_thr, row_thr):
@@ -888,8 +860,8 @@ class FlatIPIndex(_IndexStore):
             st, cnt, result = one_pass(idx, sub, cap)
             passes, longest = passes + 1, max(longest, cap)
             if (st == STATUS_RANGE).any():
-                if self.kind != "f16":
-                    raise _lib.ConvdrError("%s: %s" % (who, self._BF16_RANGE))
+                if self._store.final_range(self):
+                    raise _lib.ConvdrError("%s: %s" % (who, self._store.final_range(self)))
                 if self.stats["rescaled"]:
                     raise _lib.ConvdrError("%s: CONVDR_IP_RANGE after the scan copy was rebuilt" % who)
                 self._rebuild_scaled()
@@ -974,16 +946,12 @@ class FlatIPIndex(_IndexStore):
         X = torch.empty((nq, m), dtype=torch.float64, device=self.device)
         if nq and m:
             n = self.ntotal
-            if self._sq8:
-                with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().convdr_ip_score_rows_q8(_lib.ptr(qt), nq, _lib.ptr(self._pbf), _lib.ptr(self._centre),
-                                                                  _lib.ptr(self._step), n, self.d, _lib.ptr(rt), m, m, _lib.ptr(X),
-                                                                  _lib.ptr(D), _lib.stream_ptr()), "convdr_ip_score_rows_q8")
-                return D.reshape(shape), X.reshape(shape)
-            store, r32, r16, scale, _ = self._operands(None if n else (None, None))     # (an empty index passes no rows)
+            ops = self._operands(None if n else (None, None))      # (an empty index passes no rows)
+            suffix, head, rows = self._store.call("score", ops)
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().convdr_ip_score_rows(store, _lib.ptr(qt), nq, r32, r16, scale, n, self.d, _lib.ptr(rt), m, m,
-                                                           _lib.ptr(X), _lib.ptr(D), _lib.stream_ptr()), "convdr_ip_score_rows")
+                name = "convdr_ip_score_rows" + suffix
+                _lib.check(getattr(_lib.lib(), name)(*head, _lib.ptr(qt), nq, *rows, n, self.d, _lib.ptr(rt), m, m, _lib.ptr(X), _lib.ptr(D),
+                                                     _lib.stream_ptr()), name)
         return D.reshape(shape), X.reshape(shape)
 
     def rank_rows(self, q, rows, allowed=None):
@@ -1008,7 +976,7 @@ class FlatIPIndex(_IndexStore):
     def _rank_rows_tensors(self, q, rows, allowed, exclude):
         """rank_rows_tensors, with per-query exclusions (``excluding(ex).rank_rows_tensors``) or None"""
         import torch
-        self._refuse_sq8("rank_rows")
+        self._store.refuse(self, "rank_rows")
         qt, rt, shape = self._rows_arg("rank_rows", q, rows)
         f = self._filter(allowed)
         ex = self._exclusions(exclude, int(qt.shape[0]))
@@ -1164,7 +1132,7 @@ class FlatIPIndex(_IndexStore):
         ``stats``: rank_rounds, rank_cap, rank_band_rows (band entries re-scored, all passes), rank_above (ROWS marked without
         a re-score, final passes), rank_fallback_pairs, rescaled, ndocs."""
         import torch
-        self._refuse_sq8("rank_ids")
+        self._store.refuse(self, "rank_ids")
         self._need_ids("rank_ids")
         qt, it, shape = self._ids_arg("rank_ids", q, ids)
         f = self._filter(allowed)

@@ -72,7 +72,9 @@ def test_the_view_offers_every_exact_entry_with_the_index_s_own_arguments():
         assert inspect.signature(getattr(S.ExcludedSearch, name)) == inspect.signature(getattr(S.FlatIPIndex, name)), name
     for name in ("rank_ids", "rank_ids_tensors", "search_device", "search_deep_device", "search_distinct"):        # out of scope
         assert not hasattr(S.ExcludedSearch, name), name
-    view = S.FlatIPIndex.excluding("index", "lists")
+    index = type("Named", (str,), {})("index")          # a plain string that carries the one attribute excluding() asks
+    index._store = S.STORES["fp32"]
+    view = S.FlatIPIndex.excluding(index, "lists")
     assert isinstance(view, S.ExcludedSearch) and (view.index, view.exclude) == ("index", "lists")
     assert S._Pending(1, 2, 3, 4, 5, 6).allowed is None and S._PendingExcluded(1, 2, 3).k == 3
     assert callable(S.FlatIPIndex.exclude_rows) and callable(S.FlatIPIndex.exclude_ids) and S.QueryExclusions is QueryExclusions

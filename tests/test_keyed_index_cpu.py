@@ -128,7 +128,7 @@ class KeyedStub(S.FlatIPIndex):
 
     def __init__(self, d=8):
         self.device = torch.device("cpu")
-        self._half, self.d_in, self.d = False, d, d
+        self._store, self.d_in, self.d = S.STORES["fp32"], d, d
         self._n, self.stats = 0, {}
         self._s32 = self._s16 = self._slo = self._sid = self._sid_spare = None
         self.refuse = False

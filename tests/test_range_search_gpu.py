@@ -346,7 +346,7 @@ def test_c_abi_overflow_counts_and_untouched_tails(torch_cuda, storage, precisio
     idx = _index(shape, storage, precision)
     cap, pad = 1024, 777
     L, ptr = _lib.lib(), _lib.ptr
-    store = 2 if idx._half else (1 if idx.kind == "f16" else 0)
+    store = 2 if idx.storage == "fp16" else (1 if idx.kind == "f16" else 0)
     need = L.convdr_ip_range_workspace_bytes(nq, n, d, cap)
     q, r = torch.from_numpy(Q).cuda(), torch.from_numpy(rad).cuda()
     runs = {}
@@ -355,8 +355,8 @@ def test_c_abi_overflow_counts_and_untouched_tails(torch_cuda, storage, precisio
         cnt = fill_bytes(torch.empty(nq, dtype=torch.int64, device="cuda"), fill, 10)
         lims = fill_bytes(torch.empty(nq + 1, dtype=torch.int64, device="cuda"), fill, 11)
         st = fill_bytes(torch.empty(nq, dtype=torch.int32, device="cuda"), fill, 12)
-        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx._half else ptr(idx._rows), ptr(idx._pbf),
-                                            float(idx._scale) if store else 1.0, None if idx._half else ptr(idx._centre), n, d,
+        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx.storage == "fp16" else ptr(idx._rows), ptr(idx._pbf),
+                                            float(idx._scale) if store else 1.0, None if idx.storage == "fp16" else ptr(idx._centre), n, d,
                                             ptr(idx._max_norm), ptr(r), cap, 0, None, 0, ptr(ws), need, ptr(cnt), ptr(lims), ptr(st),
                                             _lib.stream_ptr()), "convdr_ip_range_search")
         total = int(lims[-1].item())
@@ -375,8 +375,8 @@ def test_c_abi_overflow_counts_and_untouched_tails(torch_cuda, storage, precisio
         cnt2 = fill_bytes(torch.empty(nq, dtype=torch.int64, device="cuda"), fill, 16)
         st2 = fill_bytes(torch.empty(nq, dtype=torch.int32, device="cuda"), fill, 17)
         fill_bytes(ws, fill, 18)
-        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx._half else ptr(idx._rows), ptr(idx._pbf),
-                                            float(idx._scale) if store else 1.0, None if idx._half else ptr(idx._centre), n, d,
+        _lib.check(L.convdr_ip_range_search(store, ptr(q), nq, None if idx.storage == "fp16" else ptr(idx._rows), ptr(idx._pbf),
+                                            float(idx._scale) if store else 1.0, None if idx.storage == "fp16" else ptr(idx._centre), n, d,
                                             ptr(idx._max_norm), ptr(r), cap, 1, None, 0, ptr(ws), need, ptr(cnt2), None, ptr(st2),
                                             _lib.stream_ptr()), "convdr_ip_range_search")
         np.testing.assert_array_equal(cnt2.cpu().numpy(), runs[fill][0])

@@ -117,7 +117,7 @@ class RankStub(S.FlatIPIndex):
 
     def __init__(self, band, cap=4096, kind="f16", n=1000, range_first=0):
         self.device = torch.device("cpu")
-        self.kind, self._half = kind, False
+        self.kind, self._store = kind, S.STORES["fp32"]
         self.cap, self._n = int(cap), int(n)
         self.d = self.d_in = 64
         self.stats = {}

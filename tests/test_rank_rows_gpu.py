@@ -312,7 +312,7 @@ def test_c_entry_directly(torch_cuda, storage, precision):
     S, order = _scores(shape), _order(shape)
     idx = _index(shape, storage, precision)
     L, ptr = _lib.lib(), _lib.ptr
-    store = 2 if idx._half else (1 if idx.kind == "f16" else 0)
+    store = 2 if idx.storage == "fp16" else (1 if idx.kind == "f16" else 0)
     cap = 1024
     Qp = np.concatenate([Q[:5], np.zeros((1, d), np.float32)])
     tgt = np.asarray([order[0, 0], order[1, 7], order[2, n - 1], -1, n, 99], np.int64)
@@ -329,8 +329,8 @@ def test_c_entry_directly(torch_cuda, storage, precision):
 
     def call(ws_bytes=need, outs=None):
         o = [rank, X, cnt, above, st] if outs is None else outs
-        return L.convdr_ip_rank_rows(store, ptr(q), npairs, ptr(t), None if idx._half else ptr(idx._rows), ptr(idx._pbf),
-                                     float(idx._scale) if store else 1.0, None if idx._half else ptr(idx._centre), n, d,
+        return L.convdr_ip_rank_rows(store, ptr(q), npairs, ptr(t), None if idx.storage == "fp16" else ptr(idx._rows), ptr(idx._pbf),
+                                     float(idx._scale) if store else 1.0, None if idx.storage == "fp16" else ptr(idx._centre), n, d,
                                      ptr(idx._max_norm), None, 0, 0, cap, ptr(ws), ws_bytes, *[ptr(x) for x in o], _lib.stream_ptr())
     assert call(ws_bytes=need - 1) < 0 and b"workspace too small" in L.convdr_last_error()
     for i in range(5):

@@ -109,7 +109,7 @@ class CompactStub(S.FlatIPIndex):
 
     def __init__(self, n=1000, d_in=60, half=False, scale=4.0):
         self.device = torch.device("cpu")
-        self.kind, self._half = "f16", half
+        self.kind, self._store = "f16", S.STORES["fp16" if half else "fp32"]
         self._n, self.d_in, self.d = int(n), d_in, 64
         self.compact_window_rows = 512
         self.stats = {}

@@ -32,7 +32,7 @@ class LadderStub(S.FlatIPIndex):
     def __init__(self, precision="auto", half=False, cap=4096, n=100000, script=(), default=OK, counts=None):
         self.device = torch.device("cpu")
         self.precision, self.kind = precision, S._KINDS[precision]
-        self._half = bool(half)
+        self._store = S.STORES["fp16" if half else "fp32"]
         self.cap, self._n = int(cap), int(n)
         self.d = self.d_in = 64
         self.stats = {}

@@ -118,10 +118,10 @@ def test_constructor_checks_come_before_the_device():
 
 
 def test_refused_entries_raise_naming_the_storage():
-    from convdr_amd import index_store
+    from convdr_amd import index_store, stores
     from convdr_amd.search import FlatIPIndex
     idx = object.__new__(FlatIPIndex)           # no device: every refusal comes before anything else is touched
-    idx._sq8, idx.storage = True, "sq8"
+    idx._store, idx.storage = stores.STORES["sq8"], "sq8"
     q, v = np.zeros((1, 128), dtype=f32), np.zeros(1, dtype=np.int64)
     calls = {"range_search": (q, 0.0), "range_search_tensors": (q, 0.0), "range_count": (q, 0.0), "rank_rows": (q, v),
              "rank_rows_tensors": (q, v), "rank_ids": (q, v), "rank_ids_tensors": (q, v), "excluding": ([[0]],),
